@@ -8,6 +8,12 @@ Contract (one JSON line on rank 0):
   value    = total timed tokens of all ranks / max-over-ranks wall time of K steps  (whole-job tokens/s).
   N > 1    = N independent replicas (the token loop is sequential, SURVEY 8e: replicas only, no data-path
              collective); torch.distributed is used for the barrier and the max-over-ranks only.
+  ms_per_step = max-over-ranks wall time of the K timed steps / K.
+A plain run sets up, warms up, times the K steps and prints the line; with --dump-outputs DIR it also writes what the last
+timed step computed (rank 0): DIR/tokens.npy (the token ring the generation returns, prompt included) and DIR/logits.npy (the
+logits of its last position), both float32. The inputs are seeded, so two builds compare output for output.
+--full adds the legs below (roofline, kernels, cpu_baseline + parity_vs_cpu_restatement, extra_configs); a plain run reports
+them as null / empty.
   roofline = the decode path's dominant kernel (fused rmsnorm + gate/up int4 GEMV + SiLU): algorithmic bytes per
              launch / its average launch duration, measured here with HIP events (dispatch timestamps on the launch
              stream) on every gate/up launch of 16 eager decode steps of the same network (in context: x comes
@@ -98,6 +104,8 @@ def main():
     ap.add_argument("--model", default="7b", help="geometry name in llama_cu_awq_amd.synth.GEOMETRIES")
     ap.add_argument("--ntok", type=int, default=256, help="the CLI's -n")
     ap.add_argument("--model-dir", default=os.environ.get("Q4_MODEL_DIR", "/tmp"))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's token ring and logits as DIR/tokens.npy, DIR/logits.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run the roofline / per-kernel timings, the cpu_baseline and parity leg and the extra_configs leg")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-steps", type=int, default=32, help="decode steps of the CPU restatement timed for cpu_baseline (~0.4 s each at 7B on 16 cores)")
     ap.add_argument("--f64-steps", type=int, default=10, help="positions of the unrounded double forward used as parity yardstick")
@@ -106,6 +114,8 @@ def main():
     ap.add_argument("--no-graphs", action="store_true", help="eager launches with the graph path's sequence-length bins: what the graphs run, one launch "
                                                                "at a time (rocprofv3 kernel tracing crashes inside hipGraph capture)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step: needs --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched without torch.distributed.run: this process becomes the launcher of --gpus replicas of itself (replicas only,
@@ -209,12 +219,16 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed, total_tokens = replicas.aggregate(elapsed, timed_tokens, dist if use_dist else None, device=dist_device)
     value = total_tokens / elapsed
+    if args.dump_outputs and rank == 0:     # before the --full legs, which run the network again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), toks.astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), tr.logits().astype(np.float32))
 
     # ---- per-kernel durations (dispatch timestamps, ring over the layers' weights) ------------------
     kb = kernel_bytes(cfg)
     kernels = {}
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         tr.reset(PROMPT_IDS)          # the timed kernels address the KV cache at the device position: back to 0 (after -n 2048 it is seq_len)
         pair = L.q4_get_fusion() >= 4 and L.q4_ffn_pair_covers(cfg.dim, cfg.hidden_dim) == 1    # the FFN half of a layer runs as one launch
         three = pair and L.q4_get_fusion() >= 5 and cfg.n_kv_heads == cfg.n_heads and cfg.dim // cfg.n_heads == 128   # ... with the next layer's QKV inside (csrc/gemv_ffn_pair.hip ffn_qkv_covers)
@@ -358,7 +372,7 @@ def main():
     # ---- CPU baseline (rank 0, N == 1 only): the oracle restating run_llama_network ------------------
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         import oracle
         m = oracle.Model(path)
         nthreads = oracle.lib().orc_num_threads()
@@ -431,7 +445,7 @@ def main():
     # ---- BASELINE configs 3 and 4 beside the headline (rank 0, N == 1): 13B -n 256 and 7B -n 2048, same rule ------------
     extra = None
     GB_PER_TOKEN = {("7b", 256): 3.695, ("13b", 256): 7.026, ("7b", 2048): 4.164}      # weights + average KV traffic
-    if rank == 0 and world == 1 and not args.no_extra and args.model == "7b" and ntok == 256:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.model == "7b" and ntok == 256:
         extra = {}
         tr.close()
         for mname, n in (("7b", 2048), ("13b", 256), ("13b", 2048)):

@@ -5,7 +5,7 @@ built by `make -C oracle` into oracle/_ref/). Nothing here is read at test time 
 
   tokenizer_goldens.json : encode()/decode() of the REFERENCE tokenizer on a list of strings (tokenizer.h:68-223)
   packer_goldens.json    : sha256 of the reference weight_packer's output (padding nibbles of `zeros` masked,
-                           SURVEY P7) on seeded synthetic AWQ dumps, old and new format
+                           SURVEY P7) on seeded synthetic AWQ dumps, old and new format, MHA and GQA
   convert_goldens.json   : sha256 of every file the reference convert_awq_to_bin.py writes for a seeded state-dict
   rng_goldens.json       : output of the reference's own random_u32 / random_f32 (sampler.h:31-40, cut out where the file
                            lies, compiled with gcc in a scratch directory)
@@ -69,6 +69,13 @@ def packer_goldens():
             subprocess.check_call([ref_bin, os.path.join(d, "config.json"), os.path.join(d, "dump"), dst, str(fmt)], stdout=subprocess.DEVNULL)
             data = packer_util.mask_zero_padding(open(dst, "rb").read(), cfg)
             out["old_format_%d" % fmt] = {"bytes": len(data), "sha256_masked": hashlib.sha256(data).hexdigest(), "config": cfg}
+    for fmt, seed in packer_util.GQA_CASES:
+        with tempfile.TemporaryDirectory() as d:
+            cfg = packer_util.write_awq_dump(d, old_format=bool(fmt), seed=seed, cfg=packer_util.CFG_GQA)
+            dst = os.path.join(d, "out.bin")
+            subprocess.check_call([ref_bin, os.path.join(d, "config.json"), os.path.join(d, "dump"), dst, str(fmt)], stdout=subprocess.DEVNULL)
+            data = packer_util.mask_zero_padding(open(dst, "rb").read(), cfg)
+            out["gqa_old_format_%d_seed%d" % (fmt, seed)] = {"bytes": len(data), "sha256_masked": hashlib.sha256(data).hexdigest(), "config": cfg}
     json.dump(out, open(os.path.join(HERE, "packer_goldens.json"), "w"), indent=1)
 
 

@@ -6,6 +6,9 @@ import numpy as np
 
 CFG = {"hidden_size": 256, "intermediate_size": 384, "num_hidden_layers": 1, "num_attention_heads": 2,
        "num_key_value_heads": 2, "vocab_size": 64, "max_position_embeddings": 32, "rope_theta": 10000.0}
+# grouped-query attention, two layers; (old_format, seed) of the dumps whose reference packer output tests/golden/packer_goldens.json pins
+CFG_GQA = dict(CFG, hidden_size=384, intermediate_size=256, num_hidden_layers=2, num_attention_heads=6, num_key_value_heads=2)
+GQA_CASES = [(1, 5), (0, 6)]
 GROUP = 128
 MATS = ["self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.up_proj", "mlp.gate_proj", "mlp.down_proj"]
 
