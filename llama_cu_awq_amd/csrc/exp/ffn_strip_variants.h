@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_variant_kernel(con
     for (int k = 0; k < D0; k++)
         if (k < npieces) issue2(k / TS, k % TS);
 
-    // ---- x chain (gemv_q4_body's staging, one 8-half chunk per thread of waves 0..7)
+    // ---- x chain (q4_stage_chunk's staging, one 8-half chunk per thread of waves 0..7)
     u32x4* xs = reinterpret_cast<u32x4*>(smem + L::XS);
     float* sx = reinterpret_cast<float*>(smem + L::SX);
     float* part = reinterpret_cast<float*>(smem + L::PART);
@@ -113,6 +113,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_variant_kernel(con
         const unsigned sgn = q4_stage_sign_bits(tid);      // odd units are staged negated (gemv_q4.h, q4_stage_sign_bits)
         if (NORM) v = rms_apply8(v, wraw, q4_signed_scale(ss, sgn));
         else v = q4_signed_x(v, sgn);
+        // q4_stage_chunk's arithmetic (gemv_q4.h), kept as written: the call costs five NORM instantiations one instruction
         const u32x4 pv = permute_x8(v);
         const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
         float cb = 0.f;
@@ -184,19 +185,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_variant_kernel(con
                     const unsigned zw = *reinterpret_cast<const unsigned*>(zbase + (unsigned)i * (8u * ZW * 4u) + (hs ? 16 - (int)(upper ? 4u : 0u) : ks * 8));
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads are done: the entry may be refilled
                     if (!PACED && j + D < npieces) issue2(i + (ks + D) / TS, (ks + D) % TS);
-                    float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const unsigned ww = w[d];
-                        const unsigned tt = ww >> 8;
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[ks][d][0]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[ks][d][1]), acc_o, false);
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[ks][d][2]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[ks][d][3]), acc_o, false);
-                    }
-                    const float zf = (float)((zw >> zsh) & 0xFu);
-                    float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-                    t = __builtin_fmaf(zf, corr[ks], t);
+                    const float t = q4_dot_unit(w, X[ks], zw, zsh, corr[ks]);
                     if (hs) {       // gemv_q4.h's half slot: a product and a sum (not an fma), only on the half of the wave that serves this column
                         const float v = h2f(sc) * t;
                         c += (upper == odd) ? v : 0.f;

@@ -319,17 +319,8 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
             if (gathA) {
                 u32x4 av = {0u, 0u, 0u, 0u};
                 gather_vec(la.agran, av, wraw, true);       // (the attention output: whole lines, line_slot)
-                // stage: gemv_q4_body's layout for a vector that is multiplied as it is (odd units negated)
-                const unsigned sgn = q4_stage_sign_bits(tid);
-                const u32x4 pv = permute_x8(q4_signed_x(av, sgn));
-                const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
-                float cb = 0.f;
-#pragma unroll
-                for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
-                cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);
-                const unsigned j = tid >> 2, d = tid & 3u;
-                xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
-                if (d == 0) sx[j] = cb * -9.5367431640625e-07f;
+                // stage: q4_stage_chunk's layout for a vector that is multiplied as it is (odd units negated)
+                q4_stage_chunk(xs, sx, tid, q4_signed_x(av, q4_stage_sign_bits(tid)));
             }
             block_barrier_lds();
             if (wave == 0) FPSTAMP2(41);
@@ -343,7 +334,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
 #pragma unroll
                 for (int c = 0; c < 2; c++) {
                     const u32x4 w = ow[c][ks];
-                    float acc_e = 0.f, acc_o = 0.f;
+                    float acc_e = 0.f, acc_o = 0.f;         // q4_dot_unit's arithmetic (gemv_q4.h), kept as written: the call moves waits and dot products of the QKV forms
 #pragma unroll
                     for (int d = 0; d < 4; d++) {
                         const unsigned ww = w[d], tt = ww >> 8;
@@ -403,6 +394,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
         const unsigned sgn = q4_stage_sign_bits(tid);
         if (NORM) v = rms_apply8(v, wraw, q4_signed_scale(ss, sgn));
         else v = q4_signed_x(v, sgn);
+        // q4_stage_chunk's arithmetic (gemv_q4.h), here and at both seams kept as written: the call changes this kernel's instruction stream, and its ISA is pinned
         const u32x4 pv = permute_x8(v);
         const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
         float cb = 0.f;
@@ -479,19 +471,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
                             if (j + D < npieces) issue2(i + (ks + D) / TS, (ks + D) % TS);
                             else if (j + D < nstream) issue_down(j + D - npieces);                // ... and behind the last gate/up piece the stream goes on
                         }
-                        float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                        for (int d = 0; d < 4; d++) {
-                            const unsigned ww = w[d];
-                            const unsigned tt = ww >> 8;
-                            acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[ks][d][0]), acc_e, false);
-                            acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[ks][d][1]), acc_o, false);
-                            acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[ks][d][2]), acc_e, false);
-                            acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[ks][d][3]), acc_o, false);
-                        }
-                        const float zf = (float)((zw >> zsh) & 0xFu);
-                        float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-                        t = __builtin_fmaf(zf, corr[ks], t);
+                        const float t = q4_dot_unit(w, X[ks], zw, zsh, corr[ks]);
                         c = __builtin_fmaf(h2f(sc), t, c);
                     }
                     cs[r] = c;
@@ -534,17 +514,8 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
                 u32x4 w = {0u, 0u, 0u, 0u};
                 if (i < nu2) w = *reinterpret_cast<const u32x4*>(smem + P::DW + (lc * (unsigned)p.pw4 + uj) * 16u);
                 if (i == 1 && ks == 2) { wlast = w; asm volatile("" : "+v"(wlast)); continue; }
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    const unsigned ww = w[d], tt = ww >> 8;
-                    pm[i][ks][4 * d + 0] = ww & 0x000F000Fu;
-                    pm[i][ks][4 * d + 1] = ww & 0x00F000F0u;
-                    pm[i][ks][4 * d + 2] = tt & 0x000F000Fu;
-                    pm[i][ks][4 * d + 3] = tt & 0x00F000F0u;
-                }
                 // the masks are computed HERE, while the wave waits for the vector: left alone hipcc sinks them behind barrier B, next to the dot products (seen in the ISA)
-                asm volatile("" : "+v"(pm[i][ks][0]), "+v"(pm[i][ks][1]), "+v"(pm[i][ks][2]), "+v"(pm[i][ks][3]), "+v"(pm[i][ks][4]), "+v"(pm[i][ks][5]), "+v"(pm[i][ks][6]), "+v"(pm[i][ks][7]),
-                             "+v"(pm[i][ks][8]), "+v"(pm[i][ks][9]), "+v"(pm[i][ks][10]), "+v"(pm[i][ks][11]), "+v"(pm[i][ks][12]), "+v"(pm[i][ks][13]), "+v"(pm[i][ks][14]), "+v"(pm[i][ks][15]));
+                q4_unpack_masks(w, pm[i][ks]);
             }
         }
     };
@@ -612,7 +583,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
         if (failed && dead == 0u && lane == 0) __hip_atomic_store(p.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unpack(1, 1);
         if (STAMPS) { FPSTAMP(16 + wave); if (wave == 1) { FPSTAMP(7); if (lane == 0) st[12] = passes; } }
-        // stage: down_strip_kernel's (gemv_q4_body's) permuted layout, odd units negated
+        // stage: down_strip_kernel's (q4_stage_chunk's) permuted layout, odd units negated
         u32x4* xs2 = reinterpret_cast<u32x4*>(smem + P::XS2);
         float* sx2 = reinterpret_cast<float*>(smem + P::SX2);
         const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
@@ -689,6 +660,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
                     const unsigned lc = ((unsigned)wave >> 1) + 8u * (unsigned)i;
                     const uint16_t sc = *reinterpret_cast<const uint16_t*>(smem + P::DSIDE_S + (lc * (unsigned)p.sh + (uj >> 2)) * 2u);
                     const unsigned zw = *reinterpret_cast<const unsigned*>(smem + P::DSIDE_Z + (lc * (unsigned)p.pzh + (uj >> 5)) * 4u);
+                    // q4_dot_unit's arithmetic on unpacked masks, here and in phase 3 written out: as a function it moves every piece's v_bfe_u32 and lgkmcnt wait
                     float acc_e = 0.f, acc_o = 0.f;
 #pragma unroll
                     for (int d = 0; d < 4; d++) {
@@ -748,16 +720,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
                 for (int ks = 0; ks < 2; ks++) {
                     const u32x4 w = *reinterpret_cast<const u32x4*>(smem + P::DW + ((3u * (unsigned)wave + (unsigned)j) * 128u + 64u * (unsigned)ks + lane) * 16u);
                     if (j == 2 && ks == 1) { wlast3 = w; asm volatile("" : "+v"(wlast3)); continue; }
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const unsigned ww = w[d], tt = ww >> 8;
-                        pm3[j][ks][4 * d + 0] = ww & 0x000F000Fu;
-                        pm3[j][ks][4 * d + 1] = ww & 0x00F000F0u;
-                        pm3[j][ks][4 * d + 2] = tt & 0x000F000Fu;
-                        pm3[j][ks][4 * d + 3] = tt & 0x00F000F0u;
-                    }
-                    asm volatile("" : "+v"(pm3[j][ks][0]), "+v"(pm3[j][ks][1]), "+v"(pm3[j][ks][2]), "+v"(pm3[j][ks][3]), "+v"(pm3[j][ks][4]), "+v"(pm3[j][ks][5]), "+v"(pm3[j][ks][6]), "+v"(pm3[j][ks][7]),
-                                 "+v"(pm3[j][ks][8]), "+v"(pm3[j][ks][9]), "+v"(pm3[j][ks][10]), "+v"(pm3[j][ks][11]), "+v"(pm3[j][ks][12]), "+v"(pm3[j][ks][13]), "+v"(pm3[j][ks][14]), "+v"(pm3[j][ks][15]));
+                    q4_unpack_masks(w, pm3[j][ks]);
                 }
         };
         wait_vmcnt<0>();                                 // this wave's q / k / v pieces have landed (wave 0: its stores are acknowledged)

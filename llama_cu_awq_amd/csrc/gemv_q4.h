@@ -182,6 +182,62 @@ __device__ __forceinline__ float reduce4_q4(float v0, float v1, float v2, float 
     return v;
 }
 
+// ---- The unit arithmetic of the int4 GEMV family, defined ONCE: the kernels that multiply packed weights (this header, gemv_strip.h, gemv_strip_down.h,
+// layer_attn.h, gemv_ffn_pair.h, exp/ffn_strip_variants.h) call these, so "the same arithmetic in the same order" holds by construction. A few sites of the
+// default token path keep their own copy, each with a comment: there the call compiled to a different instruction stream, and those kernels' ISA is pinned
+// (profiles/isa_before.json, isa_after.json).
+// Staging of one 8-half chunk u (chunk u = dword d = u % 4 of uint4 unit j = u / 4) whose unit sign / norm the caller has applied (q4_stage_sign_bits): the
+// permuted halves go to unit [(slot * 4 + d) * 64 + lane] of xs, the x-only term of the zero point -- the sum of the unit's 32 inputs, taken over the lane
+// quad that stages it -- to sx[j] as -(sum x) * 2^-20. Every lane of a quad calls it together (the quad sum is two DPP steps); chunks at or past `limit`
+// (the units the caller's LDS rows hold) are computed and not stored. (The bound is a parameter and not an `if` around the call: the compare in front of the
+// staging arithmetic changes the instruction count of 24 gemv_q4_kernel instantiations.)
+__device__ __forceinline__ void q4_stage_chunk(u32x4* xs, float* sx, const unsigned u, const u32x4 v, const unsigned limit = 0xFFFFFFFFu) {
+    const u32x4 pv = permute_x8(v);
+    const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
+    float cb = 0.f;
+#pragma unroll
+    for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
+    cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);   // quad sum
+    const unsigned j = u >> 2, d = u & 3u;
+    if (u < limit) {
+        xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
+        if (d == 0) sx[j] = cb * -9.5367431640625e-07f;   // -(sum x) * 2^-20
+    }
+}
+// one uint4 of weights unpacked AHEAD of its use into its sixteen nibble masks, left in place as fp16 denormal pairs -- per dword (n0,n4) * 2^-24, (n1,n5) * 2^-20,
+// (n2,n6) * 2^-24, (n3,n7) * 2^-20; the pin keeps the sixteen v_and_b32 where the caller wrote them
+__device__ __forceinline__ void q4_unpack_masks(const u32x4 w, unsigned (&m)[16]) {
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const unsigned ww = w[d], tt = ww >> 8;
+        m[4 * d + 0] = ww & 0x000F000Fu;
+        m[4 * d + 1] = ww & 0x00F000F0u;
+        m[4 * d + 2] = tt & 0x000F000Fu;
+        m[4 * d + 3] = tt & 0x00F000F0u;
+    }
+    asm volatile("" : "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3]), "+v"(m[4]), "+v"(m[5]), "+v"(m[6]), "+v"(m[7]),
+                 "+v"(m[8]), "+v"(m[9]), "+v"(m[10]), "+v"(m[11]), "+v"(m[12]), "+v"(m[13]), "+v"(m[14]), "+v"(m[15]));
+}
+// One uint4 of weights w against the unit's four staged u32x4 of inputs: 2^-20 * (sum q x - z * sum x) of the unit's 32 weights. zw: the zero word of the
+// unit's group, zsh: the nibble's shift in it, corr: sx of the unit. The masks are taken between the dot products, and the zero nibble is extracted BEHIND
+// them (a zf computed by the caller moves the v_bfe_u32 and the wait for zw in front of every piece's sixteen v_dot2c). What the caller does with the
+// result -- fma(scale, t, c), the half slot's product and sum, the live-lane select -- differs between sites and stays there.
+__device__ __forceinline__ float q4_dot_unit(const u32x4 w, const u32x4 (&X)[4], const unsigned zw, const unsigned zsh, const float corr) {
+    float acc_e = 0.f, acc_o = 0.f;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const unsigned ww = w[d];
+        const unsigned tt = ww >> 8;
+        acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[d][0]), acc_e, false);   // (n0,n4) * 2^-24
+        acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[d][1]), acc_o, false);   // (n1,n5) * 2^-20
+        acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[d][2]), acc_e, false);   // (n2,n6)
+        acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[d][3]), acc_o, false);   // (n3,n7)
+    }
+    const float zf = (float)((zw >> zsh) & 0xFu);
+    const float t = __builtin_fmaf(acc_e, 16.f, acc_o);   // 2^-20 * sum q x
+    return __builtin_fmaf(zf, corr, t);                   // - z * 2^-20 * sum x
+}
+
 // ABL (profiling-only ablation builds): 0 = product, 1 = loads kept but no dequant math, 2 = math on constants
 // without the weight loads.
 // register-heavy shapes (>= 24 uint4 in flight per lane, e.g. the 7B down projection) run 4 waves per block with
@@ -395,7 +451,6 @@ __device__ __forceinline__ void gemv_q4_body(const GemvArgs& a, const unsigned v
             if (ABL == 3) ts[2] = __builtin_readcyclecounter();
             ss = rms_scale_from_partials<NUNITS>(part, NUNITS, a.K);
         }
-        const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
         const unsigned sgn = q4_stage_sign_bits(tid);      // odd units are staged negated (q4_stage_sign_bits)
         if (NORM) ss = q4_signed_scale(ss, sgn);
 #pragma unroll
@@ -405,17 +460,7 @@ __device__ __forceinline__ void gemv_q4_body(const GemvArgs& a, const unsigned v
             if (NORM) v = rms_apply8(v, wraw[i], ss);     // (ss carries this thread's unit sign)
             else v = q4_signed_x(v, sgn);
             if (u >= nchunks) v = (u32x4){0u, 0u, 0u, 0u};
-            const u32x4 pv = permute_x8(v);
-            // x-only term of the zero point: sum of the 32 inputs of uint4 j (4 consecutive units = one lane quad)
-            float cb = 0.f;
-#pragma unroll
-            for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
-            cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);   // quad sum
-            const unsigned j = u >> 2, d = u & 3u;
-            if (u < NUNITS) {
-                xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
-                if (d == 0) sx[j] = cb * -9.5367431640625e-07f;   // -(sum x) * 2^-20
-            }
+            q4_stage_chunk(xs, sx, u, v, NUNITS);
         }
         __syncthreads();
         if (ABL == 3) ts[3] = __builtin_readcyclecounter();
@@ -480,20 +525,7 @@ __device__ __forceinline__ void gemv_q4_body(const GemvArgs& a, const unsigned v
                     const u32x4 w = W[m][s][c];
                     t = as_f(((w[0] ^ w[1] ^ w[2] ^ w[3]) & 0x007FFFFFu) | 0x3F000000u) + as_f(X[s & 3][c & 3] & 0x3FFFFFFFu);
                 } else {
-                    const u32x4 w = W[m][s][c];
-                    float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const unsigned ww = w[d];
-                        const unsigned tt = ww >> 8;
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[d][0]), acc_e, false);   // (n0,n4) * 2^-24
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[d][1]), acc_o, false);   // (n1,n5) * 2^-20
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[d][2]), acc_e, false);   // (n2,n6)
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[d][3]), acc_o, false);   // (n3,n7)
-                    }
-                    const float zf = (float)((ZW[m][s][c] >> zsh) & 0xFu);
-                    t = __builtin_fmaf(acc_e, 16.f, acc_o);          // 2^-20 * sum q x
-                    t = __builtin_fmaf(zf, corr, t);                 // - z * 2^-20 * sum x
+                    t = q4_dot_unit(W[m][s][c], X, ZW[m][s][c], zsh, corr);
                 }
                 // idle tail lanes (j >= pw4) multiply re-read weights by the zero padding of xs/sx: exactly 0
                 if (hs) {                                       // lanes 0-31 worked for column c, lanes 32-63 for column c + 1

@@ -2,7 +2,7 @@
 // for wide matrices (ffn_strip_covers below). NO loader wave: one 16-wave block per CU owns a contiguous range of columns;
 // every wave streams its OWN units -- unit u = wave + 16 i of the block's (column, matrix) pairs, 2 KiB each at K = 4096, 2.5 KiB at K = 5120 -- with
 // `buffer_load_dwordx4 ... nt lds` into a private ring of two 1 KiB pieces (lds_dma.h), waits for its oldest piece with vmcnt (a wave's loads return
-// in order), reads it back with ds_read_b128, re-issues and multiplies with the denormal-nibble v_dot2c body of gemv_q4.h. Four waves per SIMD, x staged
+// in order), reads it back with ds_read_b128, re-issues and multiplies with q4_dot_unit, the denormal-nibble v_dot2c body of gemv_q4.h. Four waves per SIMD, x staged
 // once per CU by waves 0..7 (0..9) and held in 32 (48) registers by every wave. Same arithmetic in the same order as gemv_q4_kernel<MODE_FFN>, bit for
 // bit (tests/prof_cases.py). Deeper rings, the paced issue and the stamped build live in exp/ffn_strip_variants.h (profiling library only).
 #pragma once
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_kernel(const u32x4
     for (int k = 0; k < D; k++)                        // the wave sends its whole ring at entry
         if (k < npieces) issue2(k / TS, k % TS);
 
-    // ---- x chain (gemv_q4_body's staging, one 8-half chunk per thread of waves 0..7)
+    // ---- x chain (q4_stage_chunk, one 8-half chunk per thread of waves 0..7)
     u32x4* xs = reinterpret_cast<u32x4*>(smem + L::XS);
     float* sx = reinterpret_cast<float*>(smem + L::SX);
     float* part = reinterpret_cast<float*>(smem + L::PART);
@@ -108,15 +108,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_kernel(const u32x4
         const unsigned sgn = q4_stage_sign_bits(tid);      // odd units are staged negated (gemv_q4.h, q4_stage_sign_bits)
         if (NORM) v = rms_apply8(v, wraw, q4_signed_scale(ss, sgn));
         else v = q4_signed_x(v, sgn);
-        const u32x4 pv = permute_x8(v);
-        const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
-        float cb = 0.f;
-#pragma unroll
-        for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
-        cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);   // quad sum: the 32 inputs of one uint4 unit
-        const unsigned j = tid >> 2, d = tid & 3u;
-        xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
-        if (d == 0) sx[j] = cb * -9.5367431640625e-07f;     // -(sum x) * 2^-20
+        q4_stage_chunk(xs, sx, tid, v);
     }
     block_barrier_lds();                               // x staged; side data landed (its issuers passed the vmcnt wait above)
     u32x4 X[TS][4];
@@ -155,19 +147,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_kernel(const u32x4
                     const unsigned zw = *reinterpret_cast<const unsigned*>(zbase + (unsigned)i * (8u * ZW * 4u) + (hs ? 16 - (int)(upper ? 4u : 0u) : ks * 8));
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads are done: the entry may be refilled
                     if (j + D < npieces) issue2(i + (ks + D) / TS, (ks + D) % TS);
-                    float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const unsigned ww = w[d];
-                        const unsigned tt = ww >> 8;
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[ks][d][0]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[ks][d][1]), acc_o, false);
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[ks][d][2]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[ks][d][3]), acc_o, false);
-                    }
-                    const float zf = (float)((zw >> zsh) & 0xFu);
-                    float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-                    t = __builtin_fmaf(zf, corr[ks], t);
+                    const float t = q4_dot_unit(w, X[ks], zw, zsh, corr[ks]);
                     if (hs) {       // gemv_q4.h's half slot: a product and a sum (not an fma), only on the half of the wave that serves this column
                         const float v = h2f(sc) * t;
                         c += (upper == odd) ? v : 0.f;
@@ -272,15 +252,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_pair_kernel(const 
         const unsigned sgn = q4_stage_sign_bits(tid);      // odd units are staged negated (gemv_q4.h, q4_stage_sign_bits)
         if (NORM) v = rms_apply8(v, wraw, q4_signed_scale(ss, sgn));
         else v = q4_signed_x(v, sgn);
-        const u32x4 pv = permute_x8(v);
-        const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
-        float cb = 0.f;
-#pragma unroll
-        for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
-        cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);
-        const unsigned j = tid >> 2, d = tid & 3u;
-        xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
-        if (d == 0) sx[j] = cb * -9.5367431640625e-07f;
+        q4_stage_chunk(xs, sx, tid, v);
     }
     block_barrier_lds();                               // x staged; side data landed
     u32x4 X[TS][4];
@@ -317,19 +289,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_strip_pair_kernel(const 
                     const unsigned zw = *reinterpret_cast<const unsigned*>(zbase + ((unsigned)i * 16u + colsel) * (ZW * 4u) + (k == 4 ? 16 - (int)(upper ? 4u : 0u) : ks * 8));
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads are done: the entry may be refilled
                     if (j + D < npieces) issue(i + (k + D) / PPU, (k + D) % PPU);
-                    float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const unsigned ww = w[d];
-                        const unsigned tt = ww >> 8;
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[ks][d][0]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[ks][d][1]), acc_o, false);
-                        acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[ks][d][2]), acc_e, false);
-                        acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[ks][d][3]), acc_o, false);
-                    }
-                    const float zf = (float)((zw >> zsh) & 0xFu);
-                    float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-                    t = __builtin_fmaf(zf, corr[ks], t);
+                    const float t = q4_dot_unit(w, X[ks], zw, zsh, corr[ks]);
                     if (k == 4) {        // gemv_q4.h's shared half slot: a product and a sum, each half of the wave for its own column
                         const float v = h2f(sc) * t;
                         cA += upper ? 0.f : v;

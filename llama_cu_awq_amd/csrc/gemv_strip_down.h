@@ -85,31 +85,19 @@ __global__ void __launch_bounds__(SD_WAVES * 64) down_strip_kernel(const u32x4* 
     for (int k = 0; k < 2; k++)
         if (k < npieces) issue2(0, k);
 
-    // ---- x staging: gemv_q4_body's, two chunks per thread; no norm on this path (llama2_q4.cu:331)
+    // ---- x staging: q4_stage_chunk, two chunks per thread; no norm on this path (llama2_q4.cu:331)
     u32x4* xs = reinterpret_cast<u32x4*>(smem + L::XS);
     float* sx = reinterpret_cast<float*>(smem + L::SX);
     float* tot = reinterpret_cast<float*>(smem + L::TOT);
     if (npieces >= 2) asm volatile("s_waitcnt vmcnt(2)" : "+v"(xraw[0]), "+v"(xraw[1]) : : "memory");   // all but the two weight pieces
     else asm volatile("s_waitcnt vmcnt(0)" : "+v"(xraw[0]), "+v"(xraw[1]) : : "memory");
-    {
-        const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
 #pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const unsigned u = tid + (unsigned)i * (SD_WAVES * 64u);
-            u32x4 v = xraw[i];
-            if (u >= nchunks) v = (u32x4){0u, 0u, 0u, 0u};
-            v = q4_signed_x(v, q4_stage_sign_bits(tid));      // odd units are staged negated (gemv_q4.h, q4_stage_sign_bits)
-            const u32x4 pv = permute_x8(v);
-            float cb = 0.f;
-#pragma unroll
-            for (int d4 = 0; d4 < 4; d4++) cb = __builtin_amdgcn_fdot2(as_h2(pv[d4]), ones, cb, false);
-            cb += dpp_mov<0xB1>(cb); cb += dpp_mov<0x4E>(cb);   // quad sum: the 32 inputs of one uint4 unit
-            const unsigned j = u >> 2, d = u & 3u;
-            if (u < (unsigned)(SD_ROWS * 256)) {
-                xs[(((j >> 6) * 4 + d) << 6) + (j & 63u)] = pv;
-                if (d == 0) sx[j] = cb * -9.5367431640625e-07f;     // -(sum x) * 2^-20
-            }
-        }
+    for (int i = 0; i < 2; i++) {
+        const unsigned u = tid + (unsigned)i * (SD_WAVES * 64u);
+        u32x4 v = xraw[i];
+        if (u >= nchunks) v = (u32x4){0u, 0u, 0u, 0u};
+        v = q4_signed_x(v, q4_stage_sign_bits(tid));      // odd units are staged negated (gemv_q4.h, q4_stage_sign_bits)
+        q4_stage_chunk(xs, sx, u, v, (unsigned)(SD_ROWS * 256));
     }
     block_barrier_lds();                               // x staged; side data landed (its issuers passed the vmcnt wait above)
     const unsigned char* wbase = smem + ring + lane * 16u;
@@ -141,20 +129,7 @@ __global__ void __launch_bounds__(SD_WAVES * 64) down_strip_kernel(const u32x4* 
                 const float corr = sx[uj];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the reads are done: the entry may be refilled
                 if (j + 2 < npieces) issue2(i + (ks + 2) / PPU, (ks + 2) % PPU);
-                float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    const unsigned ww = w[d];
-                    const unsigned tt = ww >> 8;
-                    acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[d][0]), acc_e, false);
-                    acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[d][1]), acc_o, false);
-                    acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[d][2]), acc_e, false);
-                    acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[d][3]), acc_o, false);
-                }
-                const unsigned zsh = ((uj >> 2) & 7u) * 4u;
-                const float zf = (float)((zw >> zsh) & 0xFu);
-                float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-                t = __builtin_fmaf(zf, corr, t);
+                const float t = q4_dot_unit(w, X, zw, ((uj >> 2) & 7u) * 4u, corr);
                 if (hs) {           // the shared slot: a product and a sum, only on the half of the wave (and the lanes) that hold this column's units
                     const float v = h2f(sc) * t;
                     c += live ? v : 0.f;

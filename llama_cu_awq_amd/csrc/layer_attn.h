@@ -206,6 +206,7 @@ __global__ void __launch_bounds__(LA16_WAVES * 64) attention_oproj16_kernel(unsi
             __builtin_amdgcn_s_sleep(2);
         }
         if (!ok && dead == 0u) __hip_atomic_store(error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // q4_stage_chunk's arithmetic (gemv_q4.h), kept as written: the call reorders the address arithmetic in front of the ds_write, and this kernel's ISA is pinned
         const unsigned sgn = q4_stage_sign_bits(tid);
         const u32x4 pv = permute_x8(q4_signed_x(xraw, sgn));
         const h2 ones = {(f16_t)1.0f, (f16_t)1.0f};
@@ -227,18 +228,7 @@ __global__ void __launch_bounds__(LA16_WAVES * 64) attention_oproj16_kernel(unsi
 #pragma unroll
         for (int d = 0; d < 4; d++) X[d] = xs[((s * 4 + d) << 6) + lu];
         const float corr = sx[s * 64 + lu];
-        float acc_e = 0.f, acc_o = 0.f;
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const unsigned ww = W[s][d], tt = ww >> 8;
-            acc_e = __builtin_amdgcn_fdot2(as_h2(ww & 0x000F000Fu), as_h2(X[d][0]), acc_e, false);
-            acc_o = __builtin_amdgcn_fdot2(as_h2(ww & 0x00F000F0u), as_h2(X[d][1]), acc_o, false);
-            acc_e = __builtin_amdgcn_fdot2(as_h2(tt & 0x000F000Fu), as_h2(X[d][2]), acc_e, false);
-            acc_o = __builtin_amdgcn_fdot2(as_h2(tt & 0x00F000F0u), as_h2(X[d][3]), acc_o, false);
-        }
-        const float zf = (float)((ZW[s] >> (((lu >> 2) & 7u) * 4u)) & 0xFu);
-        float t = __builtin_fmaf(acc_e, 16.f, acc_o);
-        t = __builtin_fmaf(zf, corr, t);
+        const float t = q4_dot_unit(W[s], X, ZW[s], ((lu >> 2) & 7u) * 4u, corr);
         if (hs) {                   // gemv_q4.h's shared half slot: lanes 0 .. 31 work for the pair's even column, lanes 32 .. 63 for the odd one
             const float v = h2f(SC[s]) * t;
             const bool mine = ((lane >> 5) & 1u) == (n & 1u);
