@@ -446,8 +446,7 @@ __device__ __forceinline__ void split_store_record(const SplitArgs& a, const Han
 // PUB: the merged output also leaves as data-tagged granules for the o-proj blocks of the same launch (layer_attn.hip)
 constexpr size_t att_split_lds_bytes(int nw, int head_size, int ring) { return (size_t)nw * ring * 1024 + (size_t)(32 + nw * head_size) * 4; }
 // How a live chunk block takes its K / V rows in: the product reads them into registers (every row requested at entry, one memory latency for the
-// chunk). A laboratory form that brought them in on per-wave LDS-DMA rings instead (same lanes, same bytes, same sums) measured the same speed and is gone
-// from the tree (EXPERIMENTS.md keeps the record); the policy parameter stays for the next such form.
+// chunk). The policy parameter is where another form plugs in (per-wave LDS-DMA rings measured the same speed: EXPERIMENTS.md).
 struct KvInRegisters { static constexpr unsigned ring_bytes(int) { return 0u; } };
 
 #ifdef Q4_PROFILING

@@ -852,7 +852,7 @@ __global__ void __launch_bounds__(STRIP_WAVES * 64) ffn_pair_kernel(const u32x4*
 
 // Shapes: gate/up K = dim = 4096 (two 1 KiB pieces per column), whole column pairs per CU, 8 .. 28 of them; down projection K = hidden in two k-parts of
 // three slots with an ordinary last one (Llama-2-7B: 172 = 64 + 64 + 44 units), at most 16 output columns per CU whose weights fit the 88 KiB the launch keeps
-// for them; every CU of the device takes one block, so the stream must not be masked. What decides whether the form RUNS is q4_runtime.hip (fusion level 4).
+// for them; every CU of the device takes one block, so the stream must not be masked. What decides whether the form RUNS is q4_network.hip (fusion level 4).
 static bool ffn_pair_shape(const GemvArgs& a, int hidden_k, int dim_n) {
     const int nb = cu_count();
     if (!(a.K == 4096 && a.pw4 == 128 && a.sh == 32 && a.pzh == 4) || a.N != hidden_k || (a.N & 1) || stream_cu_count() != nb || g_ablate != 0) return false;

@@ -21,7 +21,7 @@ size_t ffn_pair_sync_words(int dim, int hidden) { return (size_t)(hidden / 2) * 
 
 // fusion level 6: the launch begins with the layer's attention and output projection. Llama-2-7B's shape below the split-context bins: 128-wide heads (four
 // 64-byte V slices each), as many (head, slice) units as half the blocks -- the other half are the output projection, 32 columns of two k-slots each; the attention's arithmetic is
-// the V-slice role's of layer_attn.h (forms 5 / 6), which q4_runtime.hip checks is what fusion level 3 would run
+// the V-slice role's of layer_attn.h (forms 5 / 6), which q4_network.hip checks is what fusion level 3 would run
 bool layer_att_covers(int dim, int hidden, int kv_dim, int n_heads, int seq_len_bin) {
     if (!ffn_pair_covers(dim, hidden) || n_heads < 1 || dim % n_heads || kv_dim != dim) return false;
     const int nb = cu_count(), head_size = dim / n_heads;

@@ -8,8 +8,7 @@
 // more than that launch (EXPERIMENTS.md notebook §9), 256 blocks do not. Measured (7B, one call): the launch with the norm inside 42.7 / 42.1 / 40.7 us at ring
 // depth 2 / 4 / 8 against 40.2 + 4.7 us for gemv_f16_kernel behind rmsnorm_kernel -- a 262 MB stream sustains 6.2-6.5 TB/s on this chip whatever is in
 // flight --, 969.3 -> 973.0 / 971.8 tokens/s at depth 4 / 8: depth 4 ships.
-// An epilogue policy sees every logit a wave stores (the greedy sampler as this launch's epilogue was measured level, not shipped, and its header is gone
-// from the tree -- EXPERIMENTS.md #19; the product's policy is empty).
+// An epilogue policy sees every logit a wave stores (the product's policy is empty; the greedy sampler as this launch's epilogue measured level: EXPERIMENTS.md #19).
 #pragma once
 #include "gemv_strip.h"
 

@@ -182,7 +182,7 @@ static bool down_strip_covers(const GemvArgs& a, bool shared) {
     return a.nslots >= 5 && shape && a.ku * 2 >= a.pw4 && divUp(a.pw4, 64) <= SD_ROWS && a.loff == -1 && a.rms_w == nullptr &&
            a.N / nb >= 8 && divUp(a.N, nb) <= SD_NCMAX && g_ablate == 0 && stream_cu_count() == nb;
 }
-// 70 KiB of LDS: the opt-in is not a stream operation -- build_transformer makes it for the model (q4_runtime.hip), a stand-alone call at its first launch
+// 70 KiB of LDS: the opt-in is not a stream operation -- build_transformer makes it for the model (q4_model.hip), a stand-alone call at its first launch
 int down_strip_prepare() {
     const int rc = lds_opt_in((const void*)down_strip_kernel<4, true>, StripDownLds::BYTES);      // (once per device)
     return rc ? rc : lds_opt_in((const void*)down_strip_kernel<3, false>, StripDownLds::BYTES);

@@ -2,7 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <time.h>
 #include <vector>
-#include "q4_internal.h"
+#include "q4_model.h"
 using namespace q4;
 
 // launch `kernel_id` on the i-th weight set of the ring (a different layer's weights every launch: > 256 MB in flight, past the
@@ -14,12 +14,15 @@ static int launch_by_id(int kernel_id, int i, const Config* p, RunState* s, cons
     const int kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
     const PerLayerWeight* L = &w->layers[i % w->num_layers];   // ring: a different layer's weights every launch
     const long long loff = (long long)(i % w->num_layers) * p->seq_len * kv_dim;
+    const Model* m = model_of(s);
+    const float2* rope_table = m ? m->rope_table : nullptr;
+    unsigned* sync = m ? m->sync : nullptr;
     switch (kernel_id) {
         case 0: return launch_ffn_fused(s->hb, s->x, L->rms_ffn_weight, &L->wq_gate, &L->wq_up, dim, hidden);
         case 1: return q4_matmul_q4(s->hb, s->xb, &L->wq_gate, dim, hidden, 0, -1, nullptr);
         case 2: return q4_matmul_q4(s->xb, s->hb, &L->wq_down, hidden, dim, 1, -1, nullptr);
         case 3: return launch_qkv_fused(s->q, s->key_cache, s->value_cache, s->x, L->rms_att_weight, &L->wq_q, &L->wq_k,
-                                        &L->wq_v, dim, kv_dim, loff, s->pos, head_size, p->rope_theta, rope_table_of(s), nullptr);
+                                        &L->wq_v, dim, kv_dim, loff, s->pos, head_size, p->rope_theta, rope_table, nullptr);
         case 4: return q4_matmul_q4(s->q, s->xb, &L->wq_o, dim, dim, 1, -1, nullptr);
         case 5: return q4_matmul_f16(s->logits, s->x, w->wcls, p->dim, p->vocab_size, 1, 0, 0, 0, -1, 1.0f);
         case 6:
@@ -32,16 +35,14 @@ static int launch_by_id(int kernel_id, int i, const Config* p, RunState* s, cons
         case 8: return q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, 0);
         case 9: return q4_copy_embedding(s->x, w->token_embedding_table, dim, s->shared_data->tokens, s->pos);
         case 10: {   // the FFN half of a layer as one launch (gemv_ffn_pair.h); no QKV launch advances the epoch here: distinct tags by launch index
-            unsigned* sync = sync_words_of_state(s);
             if (!sync) return Q4_ERR_ARG;
             return launch_ffn_pair(s->x, s->hb, L->rms_ffn_weight, &L->wq_gate, &L->wq_up, &L->wq_down, dim, hidden, sync, ffn_pair_sync_offset(dim), 1u + (unsigned)i);
         }
         case 11: {   // ... with the next layer's QKV as its third phase (fusion level 5)
-            unsigned* sync = sync_words_of_state(s);
             if (!sync) return Q4_ERR_ARG;
             const PerLayerWeight* N = &w->layers[(i + 1) % w->num_layers];
             const long long noff = (long long)((i + 1) % w->num_layers) * p->seq_len * kv_dim;
-            const FfnQkvNext nx = {N->rms_att_weight, &N->wq_q, &N->wq_k, &N->wq_v, s->q, s->key_cache + noff, s->value_cache + noff, s->pos, rope_table_of(s), nullptr, kv_dim, head_size};
+            const FfnQkvNext nx = {N->rms_att_weight, &N->wq_q, &N->wq_k, &N->wq_v, s->q, s->key_cache + noff, s->value_cache + noff, s->pos, rope_table, nullptr, kv_dim, head_size};
             return launch_ffn_pair(s->x, s->hb, L->rms_ffn_weight, &L->wq_gate, &L->wq_up, &L->wq_down, dim, hidden, sync, ffn_pair_sync_offset(dim), 1u + (unsigned)i, &nx);
         }
     }
@@ -50,9 +51,9 @@ static int launch_by_id(int kernel_id, int i, const Config* p, RunState* s, cons
 
 // kernel 10 leaves granules tagged beyond the model's epoch behind: cleared, so that no later launch of the network can meet one of them as its own
 static void forget_bench_granules(int kernel_id, const Config* p, RunState* s) {
-    unsigned* sync = sync_words_of_state(s);
-    if ((kernel_id != 10 && kernel_id != 11) || !sync) return;
-    (void)hipMemsetAsync(sync + ffn_pair_sync_offset(p->dim), 0, ffn_pair_sync_words(p->dim, p->hidden_dim) * sizeof(unsigned), g_stream);
+    const Model* m = model_of(s);
+    if ((kernel_id != 10 && kernel_id != 11) || !m || !m->sync) return;
+    (void)hipMemsetAsync(m->sync + ffn_pair_sync_offset(p->dim), 0, ffn_pair_sync_words(p->dim, p->hidden_dim) * sizeof(unsigned), g_stream);
     (void)hipStreamSynchronize(g_stream);
 }
 

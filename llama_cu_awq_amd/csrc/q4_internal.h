@@ -75,7 +75,6 @@ struct GemvTune { int cols; int waves; int early; };   // columns per wave, wave
 int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, const q4_half* rms_w,
                      const QWeight* qw, const QWeight* kw, const QWeight* vw, int dim, int kv_dim, long long loff,
                      const int* pPos, int head_size, float rope_theta, const float2* rope_table, unsigned* bump);
-const float2* rope_table_of(const RunState* s);   // this model's table (q4_runtime.hip), null if none
 int rope_table_build(float2** out, int seq_len, int head_size, float theta);   // (cos,sin) table for the fused QKV epilogue
 int launch_attention(q4_half* output, const q4_half* q, const q4_half* key_cache, const q4_half* value_cache,
                      int num_heads, int head_size, int kv_mul, int max_seq_len, const int* pPos, float* scratch,
@@ -93,9 +92,8 @@ int attention_oproj_form(int dim, int kv_dim, int head_size, int n_heads, int se
                          int split_min, int split_chunk);   // >= 0: the fused attention + o-proj launch covers this case
 int launch_attention_oproj(q4_half* x, q4_half* xb, const q4_half* q, const q4_half* key_cache, const q4_half* value_cache,
                            const QWeight* wo, int dim, int kv_dim, int n_heads, const int* pPos, int seq_len_bin, unsigned* sync,
-                           float* scratch, size_t scratch_bytes, int split_min, int split_chunk);
-void attention_set_kv_price(const unsigned* sync, double ticks_per_pos);   // layer_attn.hip: what the split-context launch's hold-back is priced from
-double attention_get_kv_price(const unsigned* sync);
+                           float* scratch, size_t scratch_bytes, int split_min, int split_chunk,
+                           double kv_price);   // 10 ns ticks per context position of the model's K / V stream (what the split-context hold-back is priced from); 0.0: not measured
 extern int g_att_chunk;
 extern int g_att_split_min;
 extern int g_ao_guard;
@@ -158,7 +156,6 @@ bool layer_att_covers(int dim, int hidden, int kv_dim, int n_heads, int seq_len_
 int ffn_pair_prepare();     // gemv_ffn_pair.hip: LDS opt-in, outside any stream capture
 int launch_ffn_pair(q4_half* x, q4_half* hb, const q4_half* rms_w, const QWeight* gate, const QWeight* up, const QWeight* down, int dim, int hidden,
                     unsigned* sync, size_t gran_word, unsigned tag_add = 0, const FfnQkvNext* next = nullptr, const FfnLayerAtt* att = nullptr);
-unsigned* sync_words_of_state(const RunState* s);   // q4_runtime.hip: the model's hand-off words, or null
 extern int g_fp_pre, g_fp_mute, g_fp_nt;
 
 }  // namespace q4

@@ -213,7 +213,7 @@ __global__ void rope_table_kernel(float2* table, int seq_len, int head_size, flo
     table[idx] = make_float2(c, s);
 }
 
-// One table per Transformer (owned by its slabs in q4_runtime.hip, freed with it): seq_len rows of head_size/2 pairs.
+// One table per Transformer (owned by its record in q4_model.hip, freed with it): seq_len rows of head_size/2 pairs.
 int rope_table_build(float2** out, int seq_len, int head_size, float theta) {
     *out = nullptr;
     const size_t n = (size_t)seq_len * (head_size / 2);
@@ -496,7 +496,7 @@ int launch_argmax_feed(const q4_half* x, int size, int* result, volatile int* pP
 // final rmsnorm + classifier (llama2_q4.cu:336, 339) as ONE launch where the strips form covers the shape: the norm is computed once per CU inside it and x
 // itself is left un-normalised (nothing reads it afterwards: the next step's embedding overwrites it); elsewhere the two launches of the reference
 namespace q4 {
-// the LDS opt-in is not a stream operation: q4_set_device and build_transformer make it (q4_runtime.hip), outside any capture
+// the LDS opt-in is not a stream operation: q4_set_device and build_transformer make it (q4_model.hip), outside any capture
 int cls_strip_prepare() {
     // called in front of every launch of the kernel: one hipGetDevice and a comparison once the device's opt-ins are made (single host thread: q4_internal.h)
     static int prepared_device = -1;

@@ -1,0 +1,39 @@
+// q4_model.h -- what the library keeps beside a Transformer, and what q4_model.hip, q4_network.hip and q4_step.hip share (not part of the C ABI).
+#pragma once
+#include <map>
+#include "q4_internal.h"
+
+namespace q4 {
+
+// every Transformer owns two HBM slabs (weights, run state) instead of ~750 small allocations: layers sit
+// back to back in HBM in the order the token loop streams them. ONE record per model: q4_build_transformer registers it as soon as its
+// first allocation exists, q4_free_transformer is the only place that releases and forgets it.
+struct Model {
+    void* weights = nullptr;
+    void* state = nullptr;
+    void* shared = nullptr;
+    void* logits_array = nullptr;
+    float2* rope_table = nullptr;   // [seq_len][head_size/2] (cos, sin), lives exactly as long as the Transformer
+    unsigned* sync = nullptr;       // hand-off words of the attention -> o-proj launch (layout: q4_internal.h SYNC_*), null: the five-launch sequence
+    size_t sync_words = 0;          // word 0 is the sticky error flag
+    size_t att_bytes = 0;           // bytes of RunState::att (the split-context records live there)
+    double kv_price = 0.0;          // 10 ns ticks per context position of this model's K / V stream on this device (measure_kv_price), 0.0: not measured
+};
+// the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
+using Models = std::map<const RunState*, Model>;
+Models& models();
+// null for a RunState the library did not build (the public per-kernel API): no table, no hand-off words, the five-launch sequence
+static inline Model* model_of(const RunState* s) {
+    auto it = models().find(s);
+    return it == models().end() ? nullptr : &it->second;
+}
+
+#define Q4_TRY(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
+
+// q4_network.hip. have_embedding: the preceding launch of the stream (the greedy sampler of the previous step, inside one graph replay) has left
+// the token's embedding row in s->x already
+int run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding);
+// q4_step.hip
+void drop_graphs_of(const RunState* s);   // the model's captured graphs, after the launch stream has drained
+
+}  // namespace q4

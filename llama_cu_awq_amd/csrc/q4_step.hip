@@ -1,0 +1,483 @@
+// q4_step.hip -- one decode step and the loops over it: per-model graph sets and q4_run_transformer*, the sampler's host side, the hand-off
+// state between sequences, generate and perplexity on token ids.
+// Mirrors llama2_q4.cu:342-395 (run_transformer), :436-492 (generate), sampler.h, perplexity.h:57-97.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include "q4_model.h"
+
+namespace q4 {
+
+static int g_rearm_after = 0;          // > 0: sequences left at fusion level 1 before the level in force is tried again (after a timed-out hand-off)
+static int g_rearm_level = 5;          // the fusion level that comes back when the probation ends
+static int g_rearm_backoff = 16;       // sequences to sit out after the next time-out: doubles every time, so a box that keeps stalling settles at level 1
+static int g_handoff_timeouts = 0;     // timed-out in-launch waits seen by q4_handoff_status since the library was loaded
+
+// Hand-off state between sequences / launch-sequence changes / after a time-out. The EPOCH word is never rewound: the tag of a
+// launch is the epoch as it finds it, and the tagged words that outlive a launch -- the attention granules and the split-context
+// records in RunState::att -- validate themselves by tag alone, so a tag must never repeat during the life of the model (a second
+// sequence that reached the same (position, layer) used to re-create the first one's tag and could merge its stale records).
+// Cleared: arrival counters and granules, and the error word when asked. Past 2^31 launches (days of decoding) the epoch does
+// start over, together with every buffer that holds tags.
+static int clear_handoff_state(const RunState* s, const Model* m, bool error_too) {
+    if (!m || !m->sync || m->sync_words <= SYNC_EPOCH + 1) return Q4_OK;
+    unsigned* sync = m->sync;
+    if (error_too) Q4_HIP(hipMemsetAsync(sync + SYNC_ERROR, 0, sizeof(unsigned), g_stream));
+    Q4_HIP(hipMemsetAsync(sync + SYNC_EPOCH + 1, 0, (m->sync_words - SYNC_EPOCH - 1) * sizeof(unsigned), g_stream));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    unsigned epoch = 0;
+    Q4_HIP(hipMemcpy(&epoch, sync + SYNC_EPOCH, sizeof(epoch), hipMemcpyDeviceToHost));
+    if (epoch >= 0x80000000u) {
+        Q4_HIP(hipMemsetAsync(sync + SYNC_EPOCH, 0, sizeof(unsigned), g_stream));
+        if (s->att) Q4_HIP(hipMemsetAsync(s->att, 0, m->att_bytes, g_stream));
+        Q4_HIP(hipStreamSynchronize(g_stream));
+    }
+    return Q4_OK;
+}
+
+// graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
+// bit3 = Q4_MULTI_STEPS steps per graph. A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
+// recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
+// weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
+enum { GRAPH_OWNERS = 4 };
+struct GraphSet {
+    const RunState* owner;
+    const Config* config;
+    const TransformerWeights* weights;
+    unsigned long long used;
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][16];
+    bool captured[Q4_MAX_GRAPHS][16];
+    const Sampler* sampler;            // what the set's sampled graphs have baked in
+    float temperature, topp;
+    const float* coins;
+};
+static GraphSet g_sets[GRAPH_OWNERS];
+static unsigned long long g_set_clock = 0;
+static int g_graph_captures = 0;
+// a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
+static void drop_graphs(GraphSet& gs, bool sampled_only) {
+    bool drained = false;
+    for (int i = 0; i < Q4_MAX_GRAPHS; i++)
+        for (int v = 0; v < 16; v++)
+            if (gs.captured[i][v] && (!sampled_only || (v & 4))) {
+                if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
+                hipGraphExecDestroy(gs.exec[i][v]);
+                gs.captured[i][v] = false;
+            }
+    if (!sampled_only) gs.owner = nullptr;
+    gs.sampler = nullptr; gs.coins = nullptr;
+}
+void drop_graphs_of(const RunState* s) {
+    for (GraphSet& gs : g_sets)
+        if (gs.owner == s) drop_graphs(gs, false);
+}
+static GraphSet& graph_set_of(const RunState* owner, const Config* p, const TransformerWeights* w) {
+    GraphSet* pick = nullptr;
+    for (GraphSet& gs : g_sets)
+        if (gs.owner == owner) { pick = &gs; break; }
+    if (pick && (pick->config != p || pick->weights != w)) drop_graphs(*pick, false);   // the same RunState with another Config or other weights
+    if (!pick || !pick->owner) {
+        for (GraphSet& gs : g_sets)
+            if (!pick || (gs.owner == nullptr && pick->owner != nullptr) || (((gs.owner == nullptr) == (pick->owner == nullptr)) && gs.used < pick->used)) pick = &gs;
+        if (pick->owner) drop_graphs(*pick, false);
+        pick->owner = owner; pick->config = p; pick->weights = w;
+    }
+    pick->used = ++g_set_clock;
+    return *pick;
+}
+
+}  // namespace q4
+
+using namespace q4;
+
+extern "C" __attribute__((visibility("hidden"))) int q4_copy_logits_at_pos(float* logits_array, const q4_half* logits, int vocab_size, const int* pPos);
+
+extern "C" {
+
+// 0: the reference's 1:1 kernel sequence; 1: fused rmsnorm / RoPE / SiLU epilogues (five launches per layer); 3: attention ->
+// o-proj as one launch on top of that (default). Level 2 (QKV -> attention -> o-proj as one launch) was measured slower than
+// level 1 in round 2 and removed in round 3: the value selects level 1.
+void q4_set_fusion(int level) {
+    g_fusion = level <= 0 ? 0 : level >= 6 ? 6 : level == 5 ? 5 : level == 4 ? 4 : level == 3 ? 3 : 1;
+    g_rearm_after = 0;          // an explicit choice ends the probation after a time-out (and is the documented way to re-arm at once)
+    q4_reset_graphs();
+    if (g_stream)
+        for (auto& kv : models()) (void)clear_handoff_state(kv.first, &kv.second, false);   // no stale counters / granules across a change of launch sequence
+}
+int q4_get_fusion(void) { return g_fusion; }
+
+void q4_reset_graphs(void) {
+    for (GraphSet& gs : g_sets) drop_graphs(gs, false);
+}
+int q4_graph_captures(void) { return g_graph_captures; }
+
+// ---------------------------------------------------------------------------------------------------
+// sampler.h
+int build_sampler(Sampler* sampler, int vocab_size, float temperature, float topp, unsigned long long rng_seed) {
+    memset(sampler, 0, sizeof(*sampler));
+    sampler->vocab_size = vocab_size;
+    sampler->temperature = temperature;
+    sampler->topp = topp;
+    sampler->rng_state = rng_seed;
+    Q4_HIP(hipMalloc((void**)&sampler->indices, vocab_size * sizeof(int)));        // sampler.h:22
+    return Q4_OK;
+}
+// Coins of the sampled steps that run inside captured graphs: the xorshift stream stays on the host (sampler.h:31-40), the values
+// of the steps a replay covers are copied to a device ring indexed by position just before the replay (one small async copy per
+// replay), and topp_sample_kernel reads coins[position] -- so the launch needs no per-step argument and sampled steps go out
+// eight per replay like greedy ones. (The Sampler struct is the reference's: the ring lives beside it.)
+struct CoinRing { float* host; float* dev; int cap; };
+static std::map<const Sampler*, CoinRing> g_coin_rings;
+static int coin_ring_for(const Sampler* sampler, int positions, CoinRing** out) {
+    CoinRing& r = g_coin_rings[sampler];
+    if (r.cap < positions) {
+        if (r.host) hipHostFree(r.host);
+        if (r.dev) hipFree(r.dev);
+        r = CoinRing{nullptr, nullptr, 0};
+        Q4_HIP(hipHostMalloc((void**)&r.host, (size_t)positions * sizeof(float), hipHostMallocDefault));
+        Q4_HIP(hipMalloc((void**)&r.dev, (size_t)positions * sizeof(float)));
+        // zeroed on both sides: a caller whose `pos` runs behind the device position (q4_run_transformer_at / _steps with a stale `pos`: the
+        // sampled step reads coins[device position], the host fills ring[pos + i]) then samples with coin 0.0 -- the most probable token,
+        // deterministic -- instead of with uninitialised memory. INTEGRATION.md: `pos` must equal the device position for sampled steps.
+        memset(r.host, 0, (size_t)positions * sizeof(float));
+        Q4_HIP(hipMemsetAsync(r.dev, 0, (size_t)positions * sizeof(float), g_stream));
+        r.cap = positions;
+    }
+    *out = &r;
+    return Q4_OK;
+}
+void destroy_sampler(Sampler* sampler) {
+    auto cr = g_coin_rings.find(sampler);
+    if (cr != g_coin_rings.end()) {
+        for (GraphSet& gs : g_sets)
+            if (gs.sampler == sampler) drop_graphs(gs, true);
+        if (g_stream) hipStreamSynchronize(g_stream);
+        if (cr->second.host) hipHostFree(cr->second.host);
+        if (cr->second.dev) hipFree(cr->second.dev);
+        g_coin_rings.erase(cr);
+    }
+    if (sampler->indices) hipFree(sampler->indices);
+    if (sampler->tempStorage_sort) hipFree(sampler->tempStorage_sort);
+    if (sampler->tempStorage_scan) hipFree(sampler->tempStorage_scan);
+    memset(sampler, 0, sizeof(*sampler));
+}
+unsigned int random_u32(unsigned long long* state) {                               // sampler.h:31-37
+    *state ^= *state >> 12;
+    *state ^= *state << 25;
+    *state ^= *state >> 27;
+    return (unsigned int)((*state * 0x2545F4914F6CDD1Dull) >> 32);
+}
+float random_f32(unsigned long long* state) { return (random_u32(state) >> 8) / 16777216.0f; }   // :38-40
+
+Sampler* q4_sampler_new(int vocab_size, float temperature, float topp, unsigned long long rng_seed) {
+    Sampler* s = (Sampler*)calloc(1, sizeof(Sampler));
+    if (build_sampler(s, vocab_size, temperature, topp, rng_seed)) { free(s); return nullptr; }
+    return s;
+}
+void q4_sampler_delete(Sampler* s) {
+    if (!s) return;
+    destroy_sampler(s);
+    free(s);
+}
+
+__attribute__((visibility("hidden"))) int q4_sample_topp_device(Sampler* sampler, RunState* s, float coin, const float* coins, q4_half* x_next,
+                                                                const q4_half* table, int dim);   // q4_sampling.hip
+__attribute__((visibility("hidden"))) int q4_sample_topp_prepare(Sampler* sampler);
+
+static bool sampler_is_greedy(const Sampler* sampler, int gen_token) {
+    return sampler->temperature == 0.0f || !gen_token;                             // sampler.h:47
+}
+
+// sample(), sampler.h:43-82. `launch_argmax` false when the captured graph already contains it.
+static int sample_impl(Sampler* sampler, RunState* s, int gen_token, bool launch_argmax) {
+    float coin = random_f32(&sampler->rng_state);                                  // :45, drawn every step (P8)
+    if (sampler_is_greedy(sampler, gen_token)) {
+        if (launch_argmax)
+            return q4_argmax(s->logits, sampler->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, gen_token);
+        return Q4_OK;
+    }
+    return q4_sample_topp_device(sampler, s, coin, nullptr, nullptr, nullptr, 0);
+}
+int q4_sample(Sampler* sampler, RunState* s, int gen_token) { return sample_impl(sampler, s, gen_token, true); }
+
+// ---------------------------------------------------------------------------------------------------
+// run_transformer, llama2_q4.cu:346-395
+int q4_run_transformer(int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
+                       Sampler* pSampler) {
+    return q4_run_transformer_at(s->shared_data->pos, gen_token, p, s, w, copyLogits, pSampler);   // :354
+}
+
+// The same step with the position supplied by the caller instead of read back from SharedData::pos: the device keeps
+// its own position (`s->pos`) and reads its input token from the ring, so step pos+1 can be queued while step pos is
+// still running (generate() below); only the graph bin depends on the host's idea of the position.
+static int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out) {
+    int graphIndex;
+    int seq_len_bin = 128;
+    for (graphIndex = 0; graphIndex < Q4_MAX_GRAPHS - 1; seq_len_bin *= 2, graphIndex++)
+        if (seq_len <= seq_len_bin) break;                                         // :356-359
+    if ((seq_len > seq_len_bin) || (graphIndex == Q4_MAX_GRAPHS - 1)) seq_len_bin = p->seq_len;   // :360
+    *seq_len_bin_out = seq_len_bin;
+    return graphIndex;
+}
+
+int q4_run_transformer_at(int pos, int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
+                          Sampler* pSampler) {
+    return q4_run_transformer_steps(pos, 1, gen_token, p, s, w, copyLogits, pSampler);
+}
+
+// `nsteps` consecutive greedy steps (positions pos .. pos + nsteps - 1, same gen_token) as ONE graph replay: the device
+// advances its own position and feeds itself the tokens (argmax_kernel writes the ring, copy_embedding reads it), so a
+// replay needs nothing from the host between steps -- the per-replay launch cost is paid once per nsteps tokens. Only
+// nsteps == 1 or Q4_MULTI_STEPS are captured; the caller keeps a group inside one sequence-length bin (q4_steps_that_fit).
+int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
+                             int copyLogits, Sampler* pSampler) {
+    const int seq_len = pos + nsteps;                                              // :354 (of the group's last step)
+    const bool greedy = sampler_is_greedy(pSampler, gen_token);
+    int seq_len_bin;
+    const int graphIndex = graph_bin(seq_len, p, &seq_len_bin);
+    if (nsteps != 1 && (nsteps != g_multi_steps || g_use_graphs != 1)) return Q4_ERR_ARG;
+    if (pos < 0 || pos + nsteps > p->seq_len) return Q4_ERR_ARG;
+
+    if (g_use_graphs == 1) {
+        GraphSet& gs = graph_set_of(s, p, w);
+        // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
+        // graph (one launch per token instead of up to three); the variant index keeps them apart.
+        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0);
+        CoinRing* ring = nullptr;
+        if (!greedy) {     // the sampling kernel is part of the graph: its temperature, top-p, scratch and coin ring are baked in
+            Q4_TRY(coin_ring_for(pSampler, p->seq_len, &ring));
+            Q4_TRY(q4_sample_topp_prepare(pSampler));     // scratch + LDS opt-in: not capturable
+            if (gs.sampler != pSampler || gs.temperature != pSampler->temperature || gs.topp != pSampler->topp || gs.coins != ring->dev) {
+                drop_graphs(gs, true);
+                gs.sampler = pSampler; gs.temperature = pSampler->temperature; gs.topp = pSampler->topp; gs.coins = ring->dev;
+            }
+        }
+        if (!gs.captured[graphIndex][variant]) {                                   // :362-371
+            hipGraph_t graph = nullptr;
+            Q4_HIP(hipStreamBeginCapture(g_stream, hipStreamCaptureModeGlobal));
+            int rc = 0;
+            // generated tokens, several steps per replay: step i + 1 takes the token step i writes -- its sampler launch leaves the
+            // embedding row in s->x and the copy_embedding launch of step i + 1 is left out (the fused sequence only: level 0 is
+            // the reference's 1:1 launch list)
+            const bool feed = gen_token && nsteps > 1 && g_fusion >= 1;
+            for (int i = 0; i < nsteps && !rc; i++) {
+                rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0);
+                if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
+                if (!rc && greedy) {
+                    if (feed && i + 1 < nsteps)
+                        rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
+                                                s->x, w->token_embedding_table, p->dim);
+                    else
+                        rc = q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, gen_token);
+                } else if (!rc) {   // sampler.h:51-81 inside the graph: the coin comes from the ring, by position
+                    rc = q4_sample_topp_device(pSampler, s, 0.f, ring->dev, feed && i + 1 < nsteps ? s->x : nullptr, w->token_embedding_table, p->dim);
+                }
+            }
+            hipError_t e = hipStreamEndCapture(g_stream, &graph);
+            if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+            Q4_HIP(e);
+            Q4_HIP(hipGraphInstantiate(&gs.exec[graphIndex][variant], graph, nullptr, nullptr, 0));
+            Q4_HIP(hipGraphDestroy(graph));
+            gs.captured[graphIndex][variant] = true;
+            g_graph_captures++;
+        }
+        // one coin per step, drawn whether the step samples or not (sampler.h:45, P8); the sampled steps' coins go to the ring
+        for (int i = 0; i < nsteps; i++) {
+            const float coin = random_f32(&pSampler->rng_state);
+            if (ring) ring->host[pos + i] = coin;
+        }
+        if (ring) Q4_HIP(hipMemcpyAsync(ring->dev + pos, ring->host + pos, (size_t)nsteps * sizeof(float), hipMemcpyHostToDevice, g_stream));
+        Q4_HIP(hipGraphLaunch(gs.exec[graphIndex][variant], g_stream));          // :372 (:384: the sampler launch is in the graph)
+        return Q4_OK;
+    }
+    Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false));   // :374
+    if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
+    return sample_impl(pSampler, s, gen_token, true);
+}
+
+// ---------------------------------------------------------------------------------------------------
+int q4_reset_sequence(RunState* s, const int* prompt_tokens, int num_prompt_tokens) {
+    Q4_HIP(hipMemsetAsync(s->pos, 0, sizeof(int), g_stream));                     // llama2_q4.cu:461
+    if (g_rearm_after > 0 && --g_rearm_after == 0 && g_fusion == 1) { g_fusion = g_rearm_level; q4_reset_graphs(); }   // probation over
+    Q4_TRY(clear_handoff_state(s, model_of(s), false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    s->shared_data->pos = 0;                                                       // :462
+    if (prompt_tokens && num_prompt_tokens > 0)
+        memcpy((void*)s->shared_data->tokens, prompt_tokens, sizeof(int) * num_prompt_tokens);   // :463
+    return Q4_OK;
+}
+int q4_shared_pos(const RunState* s) { return s->shared_data->pos; }
+
+// How many steps a token loop may queue at once from `pos`: Q4_MULTI_STEPS when graphs are on, the sampler is greedy, the
+// whole group generates (or the whole group feeds prompt tokens), ends by `steps` and stays inside one sequence-length
+// bin; else 1.
+int q4_steps_that_fit(int pos, int num_prompt_tokens, int steps, const Config* p, const Sampler* sampler) {
+    const int k = g_multi_steps;
+    if (k <= 1 || g_use_graphs != 1 || pos + k > steps || pos + k > p->seq_len) return 1;
+    const bool gen0 = pos >= num_prompt_tokens - 1, gen1 = pos + k - 1 >= num_prompt_tokens - 1;
+    if (gen0 != gen1) return 1;
+    (void)sampler;     // sampled steps take their coins from a device ring by position: they go out k per replay too
+    int b0, b1;
+    if (graph_bin(pos + 1, p, &b0) != graph_bin(pos + k, p, &b1)) return 1;
+    return k;
+}
+// The in-launch hand-offs of fusion levels 3 and 4 (attention -> o-proj, layer_attn.h; the FFN pair launch, gemv_ffn_pair.h) spin for a bounded time; a spin that ran out
+// sets the model's error word: everything computed since is invalid. Synchronises the stream and reports it ONCE: the word,
+// the counters and the granules are cleared (the epoch keeps counting: tags never repeat), and the library drops to fusion
+// level 1 (no in-launch waits), so the caller can simply redo the sequence -- the token loops of this library do exactly that.
+// The level in force comes back by itself after 16 sequences (q4_reset_sequence counts them; 32, 64, ... after further time-outs) or at
+// once with q4_set_fusion(level).
+int q4_handoff_status(const RunState* s) {
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const Model* m = model_of(s);
+    if (!m || !m->sync) return Q4_OK;
+    unsigned flag = 0;
+    Q4_HIP(hipMemcpy(&flag, m->sync + SYNC_ERROR, sizeof(flag), hipMemcpyDeviceToHost));
+    if (flag) {
+        Q4_TRY(clear_handoff_state(s, m, true));
+        g_handoff_timeouts++;
+        if (g_fusion >= 3) {    // one transient stall (a profiler attaching, a co-tenant) must not cost every later sequence its 3 %
+            g_rearm_level = g_fusion;
+            g_fusion = 1;
+            g_rearm_after = g_rearm_backoff;
+            if (g_rearm_backoff < (1 << 20)) g_rearm_backoff *= 2;
+            q4_reset_graphs();
+        }
+        snprintf(g_last_error, sizeof(g_last_error), "an in-launch hand-off timed out (fusion level %d); state cleared, continuing at fusion level 1 for the next %d sequences", g_rearm_level, g_rearm_after);
+        if (!g_quiet) fprintf(stderr, "llama2_q4: %s\n", g_last_error);
+        return Q4_ERR_HIP;
+    }
+    return Q4_OK;
+}
+int q4_handoff_timeouts(void) { return g_handoff_timeouts; }
+// Wait until the device has published position >= pos (argmax_kernel / sample_scan_kernel write the token, fence, then
+// SharedData::pos -- "unblocks the CPU", gpu_kernels.h:490). Spins on the pinned word; falls back to the stream state
+// so that a failed launch cannot hang the host.
+int q4_wait_pos(const RunState* s, int pos) {
+    volatile int* p = &s->shared_data->pos;
+    for (unsigned spins = 1;; spins++) {
+        if (*p >= pos) return Q4_OK;
+        if ((spins & 0x3fff) == 0) {
+            hipError_t e = hipStreamQuery(g_stream);
+            if (e == hipSuccess) return *p >= pos ? Q4_OK : Q4_ERR_ARG;           // stream drained: pos is final
+            if (e != hipErrorNotReady) Q4_HIP(e);
+        }
+        __builtin_ia32_pause();
+    }
+}
+int q4_shared_token(const RunState* s, int index) { return s->shared_data->tokens[index]; }
+
+
+// generate() llama2_q4.cu:436-492 on token ids (no tokenizer, no printing): same loop order -- synchronise,
+// launch step `pos`, then look at the token produced by the PREVIOUS step; same throughput rule (pos-1)/elapsed.
+double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps,
+                       int* out_tokens, int* timed_tokens_out, double* seconds_out) {
+    if (num_prompt_tokens < 1) return -1.0;
+    if (steps <= 0 || steps > t->config.seq_len) steps = t->config.seq_len;        // :690
+    const unsigned long long rng0 = sampler->rng_state;
+    for (int attempt = 0;; attempt++) {
+        struct timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        int pos = 0, queued = 0, group_start = 0;
+        unsigned long long group_rng = sampler->rng_state;   // sampler state in front of the group of steps queued last
+        if (q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens)) return -1.0;
+        bool stopped = false;
+        while (pos < steps) {
+            // the reference synchronises and then launches step `pos` (:468-470); here the launch goes out first, queued
+            // behind step pos-1, and the host then waits for step pos-1's token -- same device order, no idle gap per token.
+            // Greedy steps inside one bin go out Q4_MULTI_STEPS at a time (one graph replay); a stop at EOS leaves at most
+            // Q4_MULTI_STEPS - 1 surplus steps behind, which the next q4_reset_sequence discards.
+            if (pos >= queued) {
+                const int k = q4_steps_that_fit(pos, num_prompt_tokens, steps, &t->config, sampler);
+                group_start = pos;
+                group_rng = sampler->rng_state;
+                if (q4_run_transformer_steps(pos, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler)) return -1.0;
+                queued = pos + k;
+            }
+            if (q4_wait_pos(&t->state, pos)) return -1.0;                              // :468
+            if (pos > 0) {
+                int next = t->state.shared_data->tokens[pos];                          // :473
+                if (next >= t->config.vocab_size) next = 0;                            // :474
+                if (next == 2) { stopped = true; break; }                              // eos_token, :477
+            }
+            pos++;
+        }
+        clock_gettime(CLOCK_MONOTONIC, &t1);                                           // :485, taken where the reference takes it
+        if (stopped) {
+            // the reference has drawn one coin per run_transformer call, steps 0..pos (sampler.h:45); a multi-step group drew
+            // for its surplus steps too: put the stream back to exactly pos + 1 draws so a reused Sampler continues like the reference's
+            sampler->rng_state = group_rng;
+            for (int i = group_start; i <= pos; i++) (void)random_f32(&sampler->rng_state);
+        }
+        const double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
+        const int timed_tokens = pos - 1;                                              // :488
+        if (q4_handoff_status(&t->state)) {     // a timed-out in-launch wait: the library is at fusion level 1 now, state cleared
+            if (attempt == 0) { sampler->rng_state = rng0; continue; }                 // redo the whole sequence once
+            return -1.0;
+        }
+        if (out_tokens) {
+            const int n = (pos < steps ? pos : steps) + 1;
+            for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = t->state.shared_data->tokens[i];
+        }
+        if (timed_tokens_out) *timed_tokens_out = timed_tokens;
+        if (seconds_out) *seconds_out = secs;
+        return secs > 0 ? timed_tokens / secs : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// perplexity.h:3-51 (host math)
+void q4_softmax_f32(float* x, int size) {
+    float max_val = x[0];
+    for (int i = 1; i < size; i++)
+        if (x[i] > max_val) max_val = x[i];
+    float sum = 0.0f;
+    for (int i = 0; i < size; i++) {
+        x[i] = expf(x[i] - max_val);
+        sum += x[i];
+    }
+    for (int i = 0; i < size; i++) x[i] /= sum;
+}
+float compute_perplexity(const int* tokens, float* logits, int num_tokens, int vocab_size) {
+    double sum = 0.0;
+    for (int i = 0; i < num_tokens; i++) {
+        int word_index = tokens[i];
+        q4_softmax_f32(&logits[(size_t)i * vocab_size], vocab_size);
+        double prob = logits[(size_t)i * vocab_size + word_index];
+        sum += log(prob);
+    }
+    double avg_log_prob = sum / num_tokens;
+    return float(exp(-avg_log_prob));
+}
+
+// get_dataset_perplexity perplexity.h:57-97 on token ids: tokens_with_bos[0] = BOS, targets follow.
+float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, int num_tokens) {
+    Config* config = &t->config;
+    RunState* state = &t->state;
+    if (!state->logits_array || num_tokens < 1) return -1.0f;
+    if (num_tokens >= config->seq_len) num_tokens = config->seq_len - 1;           // :68-72
+    const unsigned long long rng0 = sampler->rng_state;
+    for (int attempt = 0;; attempt++) {
+        if (q4_reset_sequence(state, tokens_with_bos, num_tokens + 1)) return -1.0f;   // :76-78
+        // the input tokens are all known: the steps are queued back to back (the device advances its own position) and the
+        // host synchronises once, where the reference calls cudaDeviceSynchronize after every step (:81)
+        for (int pos = 0; pos < num_tokens; pos++)
+            if (q4_run_transformer_at(pos, 0, config, state, &t->weights, 1, sampler)) return -1.0f;   // :80
+        if (hipDeviceSynchronize() != hipSuccess) return -1.0f;                        // :81
+        if (!q4_handoff_status(state)) break;
+        // a timed-out in-launch wait: the library has dropped to fusion level 1 and cleared its state; redo the pass once
+        if (attempt > 0) return -1.0f;
+        sampler->rng_state = rng0;
+    }
+    float* logits_arr = (float*)malloc((size_t)num_tokens * config->vocab_size * sizeof(float));
+    if (q4_get_logits_array(t, num_tokens, logits_arr)) { free(logits_arr); return -1.0f; }   // :88-89
+    float pplx = compute_perplexity(tokens_with_bos + 1, logits_arr, num_tokens, config->vocab_size);   // :91
+    free(logits_arr);
+    return pplx;
+}
+
+}  // extern "C"

@@ -380,7 +380,7 @@ def test_sampler_rng_after_an_early_stop_matches_one_draw_per_executed_step(q4, 
 
 
 def test_two_models_alternate_without_recapture(q4, models):
-    """Captured graphs are kept per model (csrc/q4_runtime.hip, GraphSet): a host that alternates two Transformers step by step replays each one's
+    """Captured graphs are kept per model (csrc/q4_step.hip, GraphSet): a host that alternates two Transformers step by step replays each one's
     graphs instead of capturing them again on every switch (q4_graph_captures counts), and every token equals the model's own stepwise run. A fifth
     live model evicts the least recently used set, which is captured again on its next turn."""
     L = q4.lib()
@@ -417,3 +417,86 @@ def test_two_models_alternate_without_recapture(q4, models):
     assert int(ts["tiny"].token(31)) == want["tiny"][31]
     for t in list(ts.values()) + extra:
         t.close()
+
+
+def test_a_model_built_where_a_freed_one_lived_starts_clean(q4, models):
+    """Everything the library keeps beside a Transformer is one record (csrc/q4_model.h), and q4_free_transformer is the only place that forgets it --
+    together with the model's captured graphs. The allocator hands a freed Transformer's address to the next one: a model built there must meet nothing
+    of its predecessor (rope table, hand-off words, K / V price, graphs). The models are freed WITHOUT q4_reset_graphs (Transformer.close calls it first),
+    so the clean-up is the library's own."""
+    L = q4.lib()
+    prompt = [1, 17, 300, 45, 9]
+    t = q4.Transformer(models["tiny_gqa"])
+    want = list(t.generate_ids(prompt, 34)[0])
+    t.close()
+    for _ in range(3):
+        t = q4.Transformer(models["tiny"])
+        t.reset(prompt)
+        for pos in range(6):
+            t.run_transformer(pos >= len(prompt) - 1)
+        q4.synchronize()
+        L.q4_sampler_delete(t.sampler)
+        L.q4_transformer_delete(t.h)
+        t.h = None
+        c0 = L.q4_graph_captures()
+        g = q4.Transformer(models["tiny_gqa"])
+        got = list(g.generate_ids(prompt, 34)[0])
+        assert got == want
+        assert L.q4_graph_captures() > c0          # its own captures: nothing was replayed from the freed model
+        g.close()
+
+
+def test_the_kv_price_belongs_to_its_model(q4, models):
+    """The K / V stream price q4_build_transformer measures lives in the model's record: building and freeing other models leaves it bit for bit what it
+    was, and a model below the measurable context (tiny: seq_len 64) has none. (No value is asserted for the price itself: it is a measurement of the
+    box, and the build may reject it.)"""
+    import struct
+    L = q4.lib()
+    a = q4.Transformer(models["head64_long"])        # seq_len 1300: measured
+    before = struct.pack("d", L.q4_kv_stream_price(a.state))
+    b = q4.Transformer(models["head128"])            # seq_len 1100: measured too
+    b.close()
+    c = q4.Transformer(models["tiny"])
+    assert L.q4_kv_stream_price(c.state) == 0.0
+    assert struct.pack("d", L.q4_kv_stream_price(a.state)) == before
+    c.close()
+    assert struct.pack("d", L.q4_kv_stream_price(a.state)) == before
+    a.close()
+
+
+def test_reusing_a_runstate_with_other_weights_captures_again(q4, tmp_path):
+    """A graph set remembers the Config and the TransformerWeights it was captured with: q4_run_transformer with model A's Config and RunState and model
+    B's weights (same geometry: legal) captures again -- once -- instead of replaying A's graphs, and its logits are those of the eager run of the same
+    combination, bit for bit."""
+    import ctypes as C
+    L = q4.lib()
+    paths = [str(tmp_path / ("tiny_%d.bin" % seed)) for seed in (7, 8)]
+    for path, seed in zip(paths, (7, 8)):
+        synth.write_model(path, "tiny", seed=seed)
+    a, b = q4.Transformer(paths[0]), q4.Transformer(paths[1])
+    prompt = [1, 17, 300]
+
+    def run(weights, steps):
+        a.reset(prompt)
+        for pos in range(steps):
+            q4.check(L.q4_run_transformer(int(pos >= len(prompt) - 1), C.byref(a.config), a.state, weights, 0, a.sampler))
+        q4.synchronize()
+        return a.logits().view(np.uint16).copy()
+
+    try:
+        own = run(a.weights, 1)
+        run(a.weights, 5)                            # A's graphs: prompt steps and generated steps
+        c0 = L.q4_graph_captures()
+        mixed = run(b.weights, 1)
+        used = L.q4_graph_captures() - c0
+        L.q4_set_use_graphs(0)
+        eager = run(b.weights, 1)
+        print("captures for the mixed step: %d; halves that differ from the eager run: %d, from A's own step: %d" % (
+            used, int((mixed != eager).sum()), int((mixed != own).sum())))
+        assert used == 1, used
+        assert (mixed == eager).all()
+        assert (mixed != own).any()                  # (the two checkpoints do differ: a replay of A's graph would have shown)
+    finally:
+        L.q4_set_use_graphs(1)
+        a.close()
+        b.close()

@@ -3,7 +3,7 @@
 (head, chunk) block of the attention role -- entry, position known, q landed, scores done (the K rows have arrived), block maximum
 known, P.V done (the V rows have arrived), record stored, head merged (chunk 0) -- and per block of the o-proj role (entry, wait
 passed, end), all relative to the launch's first entry. Profiling build; the last layer's launch of one eager token.
-tools/lab/timeline_split.py [context] [model] [ring: 0 registers, 1 LDS-DMA rings]"""
+tools/lab/timeline_split.py [context] [model]"""
 import ctypes as C
 import os
 import sys
@@ -16,7 +16,6 @@ from llama_cu_awq_amd import api, synth   # noqa: E402
 api.use_profiling_build()
 ctx = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
 model = sys.argv[2] if len(sys.argv) > 2 else "7b"
-ring = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 path = "/tmp/llama2_q4_synth_%s_seed20240229.bin" % model
 if not os.path.exists(path):
     synth.write_model(path, model)
@@ -26,7 +25,6 @@ s = C.c_void_p()
 api.check(L.q4_stream_create(C.byref(s)))
 L.q4_set_stream(s)
 L.q4_set_gemv_early(11, -1)     # wave-owned GEMVs: the strips kernels stamp into the same buffer
-L.q4_set_gemv_early(14, ring)
 tr = api.Transformer(path)
 tr.generate_ids([1, 2436, 385, 3686, 388, 1048, 22796, 118], ctx)
 L.q4_set_use_graphs(0)
@@ -51,8 +49,8 @@ for rep in range(3):
     nblk = len(att)
     w = w[: nblk * nw]
     live = w[:, 3] > 0
-    print("rep %d, position %d, ring %d: %d attention blocks (%d live waves), %d o-proj blocks; launch span %.2f us" % (
-        rep, tr.pos() - 1, ring, nblk, live.sum(), len(con), (blk[:, 2].max() - t0) / 100.0))
+    print("rep %d, position %d: %d attention blocks (%d live waves), %d o-proj blocks; launch span %.2f us" % (
+        rep, tr.pos() - 1, nblk, live.sum(), len(con), (blk[:, 2].max() - t0) / 100.0))
     print("   (min / median / p90 / max, us since the launch's first entry)")
     for k in range(7):
         v = w[live][:, k]
