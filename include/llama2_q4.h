@@ -185,6 +185,15 @@ int q4_rope_rotation(q4_half* q, q4_half* k, int num_heads, int num_kv_heads, in
 int q4_multi_head_attention(q4_half* output, const q4_half* q, const q4_half* key_cache,
                             const q4_half* value_cache, q4_half* att, int num_heads, int head_size, int kv_mul,
                             int max_seq_len, const int* pPos);
+/* The same over FP8 (OCP e4m3fn) caches, the layout of Q4_KV_FP8 models: k8 / v8 [max_seq_len][kv_dim] bytes, k_exp / v_exp
+ * [n_kv_heads][max_seq_len] signed row exponents (a row of one position and kv head is head_size bytes times 2^e, e the smallest integer
+ * in [-15, 7] with amax <= 448 * 2^e). k_row / v_row [kv_dim] halves hold position *pPos (K already rotated): the launch quantises them,
+ * attends over their round trip and APPENDS bytes and exponents at *pPos; it reads no cache row at or past *pPos. Head sizes 64, 128, 256.
+ * att: null (one block per head at any context), or a scratch of at least 8 * num_heads * max_seq_len BYTES: bins from 512 positions then run one block per
+ * (head, chunk) with flash-decode records in it, merged by a second launch. */
+int q4_multi_head_attention_kv8(q4_half* output, const q4_half* q, uint8_t* k8, uint8_t* v8, int8_t* k_exp, int8_t* v_exp,
+                                const q4_half* k_row, const q4_half* v_row, q4_half* att, int num_heads, int head_size, int kv_mul,
+                                int max_seq_len, const int* pPos);
 
 /* copy_embedding_kernel gpu_kernels.h:61-69, launch llama2_q4.cu:294. tokens: device-visible int array */
 int q4_copy_embedding(q4_half* x, const q4_half* table, int size, const int* tokens, const int* pPos);
@@ -246,6 +255,15 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
  * projection; the whole layer behind its q / k / v is ONE launch, 1 launch/layer; bit-identical to levels 3 / 4 / 5. */
 void q4_set_fusion(int level);
 int q4_get_fusion(void);
+/* The K / V cache format of the models q4_build_transformer builds from now on (a model's format is fixed at build time): Q4_KV_FP16 (default:
+ * every launch and every bit as without this call) or Q4_KV_FP8 -- e4m3 bytes with one exponent byte per (position, kv head), half the cache's
+ * bytes; attention then is the fp16 attention over rows replaced by their FP8 round trip. Head sizes 64, 128 and 256; a build
+ * with another fails with Q4_ERR_UNSUPPORTED_SIZE and a q4_last_error text. Returns Q4_ERR_ARG for any other value. */
+enum { Q4_KV_FP16 = 0, Q4_KV_FP8 = 1 };
+int q4_set_kv_format(int format);
+int q4_get_kv_format(void);
+/* the format of the model that owns this RunState; Q4_KV_FP16 for a RunState the library did not build */
+int q4_kv_format_of(const RunState* s);
 /* 1: at fusion levels 4 / 5 a layer's FFN half of these sizes runs as one launch on the current device and stream (csrc/gemv_ffn_pair.h) */
 int q4_ffn_pair_covers(int dim, int hidden_dim);
 /* 1 (default): hipGraph capture/replay as USE_CUDA_GRAPHS llama2_q4.cu:33; 0: eager launches with the exact context length (the
@@ -295,7 +313,7 @@ double q4_kv_stream_price(const RunState* s);
 int q4_shared_token(const RunState* s, int index);
 /* parity dumps: synchronise, then copy fp16 logits / a KV row / the residual to the host */
 int q4_get_logits(const Transformer* t, q4_half* host_out);
-int q4_get_kv_row(const Transformer* t, int layer, int pos, q4_half* host_k, q4_half* host_v);
+int q4_get_kv_row(const Transformer* t, int layer, int pos, q4_half* host_k, q4_half* host_v);   /* Q4_KV_FP8 models: the dequantised halves */
 int q4_get_logits_array(const Transformer* t, int num_pos, float* host_out);
 
 /* ---- host drivers (llama2_q4.cu:436-601, perplexity.h) ---------------------------------------- */

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libllama2_q4.so")
 PROF_LIB_PATH = os.path.join(_HERE, "libllama2_q4_prof.so")
 
 MAX_SEQ_LEN = 128 * 1024
+KV_FP16, KV_FP8 = 0, 1          # q4_set_kv_format
+KV_FORMATS = {"fp16": KV_FP16, "fp8": KV_FP8}
 
 
 class Config(C.Structure):
@@ -53,8 +55,8 @@ SYMBOLS = [
     "q4_status_string", "q4_last_error", "q4_set_device", "q4_stream_create", "q4_stream_create_masked", "q4_stream_destroy", "q4_set_stream",
     "q4_get_stream", "q4_stream_synchronize", "q4_device_synchronize", "q4_malloc", "q4_free", "q4_memcpy_h2d",
     "q4_memcpy_d2h", "q4_memset", "q4_rmsnorm", "q4_matmul_f16", "q4_matmul_q4", "q4_qkv_matvec", "q4_ffn_matvec_silu",
-    "q4_rope_rotation", "q4_multi_head_attention", "q4_copy_embedding", "q4_convert_fp16_to_fp32", "q4_argmax",
-    "q4_run_llama_network", "q4_run_transformer", "q4_run_transformer_at", "q4_wait_pos", "q4_steps_that_fit", "q4_run_transformer_steps", "q4_set_fusion", "q4_get_fusion", "q4_ffn_pair_covers", "q4_set_use_graphs", "q4_reset_graphs", "q4_graph_captures",
+    "q4_rope_rotation", "q4_multi_head_attention", "q4_multi_head_attention_kv8", "q4_copy_embedding", "q4_convert_fp16_to_fp32", "q4_argmax",
+    "q4_run_llama_network", "q4_run_transformer", "q4_run_transformer_at", "q4_wait_pos", "q4_steps_that_fit", "q4_run_transformer_steps", "q4_set_fusion", "q4_get_fusion", "q4_set_kv_format", "q4_get_kv_format", "q4_kv_format_of", "q4_ffn_pair_covers", "q4_set_use_graphs", "q4_reset_graphs", "q4_graph_captures",
     "build_sampler", "destroy_sampler", "random_u32", "random_f32", "q4_sample", "q4_build_transformer",
     "q4_free_transformer", "q4_set_quiet", "q4_transformer_new", "q4_transformer_delete", "q4_transformer_config",
     "q4_transformer_state", "q4_transformer_weights", "q4_sampler_new", "q4_sampler_delete", "q4_reset_sequence",
@@ -117,6 +119,10 @@ def lib():
     L.q4_run_transformer.argtypes = [i, C.POINTER(Config), C.POINTER(RunState), C.POINTER(TransformerWeights), i, vp]
     L.q4_set_fusion.argtypes = [i]
     L.q4_set_fusion.restype = None
+    if hasattr(L, "q4_set_kv_format"):             # (older builds under tools/ab.py do not have it)
+        L.q4_set_kv_format.argtypes = [i]
+        L.q4_kv_format_of.argtypes = [C.POINTER(RunState)]
+        L.q4_multi_head_attention_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
     if hasattr(L, "q4_kv_stream_price"):
         L.q4_kv_stream_price.restype = C.c_double
         L.q4_kv_stream_price.argtypes = [vp]
@@ -302,11 +308,25 @@ def device_info():
 class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
-    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True):
+    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16"):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
-        self.h = L.q4_transformer_new(path.encode(), int(perplexity), C.byref(st))
+        if kv not in KV_FORMATS:
+            raise ValueError("kv: 'fp16' or 'fp8', not %r" % (kv,))
+        # the format is a process-wide setting read by the build: set around it and restored, whatever the build does
+        has = hasattr(L, "q4_set_kv_format")           # (older builds under tools/ab.py do not have it: fp16 only)
+        if not has and kv != "fp16":
+            raise Q4Error("this build of the library has no FP8 K / V cache")
+        before = L.q4_get_kv_format() if has else KV_FP16
+        if has:
+            check(L.q4_set_kv_format(KV_FORMATS[kv]))
+        try:
+            self.h = L.q4_transformer_new(path.encode(), int(perplexity), C.byref(st))
+        finally:
+            if has:
+                L.q4_set_kv_format(before)
+        self.kv_format = kv
         if not self.h:
             raise Q4Error("build_transformer failed: %s %s" % (L.q4_status_string(st.value).decode(), L.q4_last_error().decode()))
         # a COPY of the header: the C struct lives inside the Transformer and dies with close(); readers of

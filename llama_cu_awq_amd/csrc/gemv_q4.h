@@ -67,6 +67,7 @@ struct GemvArgs {
     const float2* rope_table;  // [seq_len][head_size/2] (cos, sin) built with the reference's formula; null: compute
     int early;                 // waves in the first `early` slots of a SIMD issue their weight loads before the staging ends
     unsigned* bump;            // QKV: epoch word of the FOLLOWING attention + o-proj launch, advanced once by block (0, 0)
+    int kv_stage;              // QKV: out[1] / out[2] are ROWS (the FP8 cache's fp16 staging rows, attention_kv8.h), not caches: no loff + pos * N
 };
 
 // In-launch hand-off (layer_attn.hip: attention -> o-proj as ONE launch) with data-tagged granules: a vector
@@ -600,7 +601,7 @@ __device__ __forceinline__ void gemv_q4_body(const GemvArgs& a, const unsigned v
     } else {   // MODE_QKV, COLS == 4: rows = pair0 first, pair1 first, pair0 second, pair1 second
         q4_half* out = a.out[mat0];
         const int pos = pos_now;
-        if (mat0 != 0) out += (size_t)a.loff + (size_t)pos * N;                     // gpu_kernels.h:251,253
+        if (mat0 != 0 && !a.kv_stage) out += (size_t)a.loff + (size_t)pos * N;      // gpu_kernels.h:251,253
         const float mine = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
         const int hp = a.head_size >> 1;
         const int p = wg * 2 + (row & 1);                // pair index of this row

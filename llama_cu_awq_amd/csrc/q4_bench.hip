@@ -17,6 +17,14 @@ static int launch_by_id(int kernel_id, int i, const Config* p, RunState* s, cons
     const Model* m = model_of(s);
     const float2* rope_table = m ? m->rope_table : nullptr;
     unsigned* sync = m ? m->sync : nullptr;
+    if (m && m->kv_format == Q4_KV_FP8) {      // an FP8 model's K / V launches: staging rows, attention over the byte caches
+        const size_t eoff = (size_t)(i % w->num_layers) * p->n_kv_heads * p->seq_len;
+        if (kernel_id == 3) return launch_qkv_fused(s->q, m->k_row, m->v_row, s->x, L->rms_att_weight, &L->wq_q, &L->wq_k, &L->wq_v, dim, kv_dim, 0, s->pos,
+                                                    head_size, p->rope_theta, rope_table, nullptr, true);
+        if (kernel_id == 6) return launch_attention_kv8(s->xb, s->q, (uint8_t*)s->key_cache + loff, (uint8_t*)s->value_cache + loff, m->k_exp + eoff, m->v_exp + eoff, m->k_row, m->v_row,
+                                                        p->n_heads, head_size, p->n_heads / p->n_kv_heads, p->seq_len, p->seq_len, s->pos, (float*)s->att, att_buffer_bytes(p), nullptr);
+        if (kernel_id == 11) return Q4_ERR_ARG;   // (the next layer's QKV never rides in the pair launch of an FP8 model)
+    }
     switch (kernel_id) {
         case 0: return launch_ffn_fused(s->hb, s->x, L->rms_ffn_weight, &L->wq_gate, &L->wq_up, dim, hidden);
         case 1: return q4_matmul_q4(s->hb, s->xb, &L->wq_gate, dim, hidden, 0, -1, nullptr);

@@ -435,6 +435,11 @@ int q4_main(int argc, char** argv) {
     if (q4_parse_args(argc, argv, &a)) { error_usage_text(argv[0]); exit(EXIT_FAILURE); }
     if (!a.perplexity && a.dataset_path) printf("Warning: dataset path is ignored in non-perplexity mode\n");
 
+    // the K / V cache format comes from the environment: the flags, CliArgs and the usage text stay the reference's
+    const char* kv = getenv("Q4_KV_CACHE");
+    if (kv && strcmp(kv, "fp8") == 0) q4_set_kv_format(Q4_KV_FP8);
+    else if (kv && *kv && strcmp(kv, "fp16") != 0) { fprintf(stderr, "Q4_KV_CACHE: unknown format '%s' (fp16 or fp8)\n", kv); exit(EXIT_FAILURE); }
+
     Transformer transformer;
     int rc = q4_build_transformer(&transformer, a.checkpoint_path, a.perplexity);
     if (rc) exit(rc == Q4_ERR_IO ? 1 : EXIT_FAILURE);

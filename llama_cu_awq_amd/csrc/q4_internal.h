@@ -74,11 +74,18 @@ struct GemvTune { int cols; int waves; int early; };   // columns per wave, wave
 // bump: epoch word of the attention -> o-proj launch that follows in the stream (advanced once by this launch), or null
 int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, const q4_half* rms_w,
                      const QWeight* qw, const QWeight* kw, const QWeight* vw, int dim, int kv_dim, long long loff,
-                     const int* pPos, int head_size, float rope_theta, const float2* rope_table, unsigned* bump);
+                     const int* pPos, int head_size, float rope_theta, const float2* rope_table, unsigned* bump,
+                     bool kv_stage = false);   // kv_stage: kc / vc are the FP8 cache's fp16 staging rows [kv_dim], written without loff + pos * kv_dim
 int rope_table_build(float2** out, int seq_len, int head_size, float theta);   // (cos,sin) table for the fused QKV epilogue
 int launch_attention(q4_half* output, const q4_half* q, const q4_half* key_cache, const q4_half* value_cache,
                      int num_heads, int head_size, int kv_mul, int max_seq_len, const int* pPos, float* scratch,
                      size_t scratch_bytes, unsigned* arrive);   // arrive: n_heads zeroed counters (split-context merge by the last block) or null
+// attention over the FP8 (e4m3) K / V cache, appending the staging rows (attention_kv8.h); exp_stride: positions per kv head in the exponent arrays
+bool kv8_head_size_ok(int head_size);
+int launch_attention_kv8(q4_half* output, const q4_half* q, uint8_t* k8, uint8_t* v8, int8_t* k_exp, int8_t* v_exp, const q4_half* k_row,
+                         const q4_half* v_row, int num_heads, int head_size, int kv_mul, int max_seq_len, int exp_stride, const int* pPos,
+                         float* scratch, size_t scratch_bytes, unsigned* arrive);
+extern int g_kv_format;    // the format q4_build_transformer gives the next model (q4_set_kv_format)
 // attention -> o-proj as one launch (layer_attn.h). Hand-off words of a model (unsigned), zeroed at build and by
 // q4_reset_sequence: [SYNC_ERROR] flag of a timed-out wait and [SYNC_EPOCH] launch epoch (advanced by the fused QKV launch) in
 // ONE aligned 8-byte word, [SYNC_ARRIVE .. +n_heads) arrival counters of the split-context merge, [SYNC_GRANULES ..) dim/2

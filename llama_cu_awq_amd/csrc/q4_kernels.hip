@@ -239,7 +239,7 @@ static int fill_geom(GemvArgs& a, int K, int N) {
 
 int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, const q4_half* rms_w, const QWeight* qw,
                      const QWeight* kw, const QWeight* vw, int dim, int kv_dim, long long loff, const int* pPos,
-                     int head_size, float rope_theta, const float2* rope_table, unsigned* bump) {
+                     int head_size, float rope_theta, const float2* rope_table, unsigned* bump, bool kv_stage) {
     if (kv_dim > dim || (kv_dim & 7)) return Q4_ERR_ARG;
     GemvArgs a = {};
     int rc = fill_geom(a, dim, dim);
@@ -252,6 +252,7 @@ int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, con
     a.rope_table = head_size > 0 ? rope_table : nullptr;   // [seq_len][head_size/2] for THIS model, or null: compute
     a.early = g_tune[TUNE_QKV].early;
     a.bump = bump;
+    a.kv_stage = kv_stage ? 1 : 0;
     return launch_gemv_qkv(a, g_tune[TUNE_QKV].cols, g_tune[TUNE_QKV].waves);
 }
 

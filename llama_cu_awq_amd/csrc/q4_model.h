@@ -17,6 +17,11 @@ struct Model {
     unsigned* sync = nullptr;       // hand-off words of the attention -> o-proj launch (layout: q4_internal.h SYNC_*), null: the five-launch sequence
     size_t sync_words = 0;          // word 0 is the sticky error flag
     size_t att_bytes = 0;           // bytes of RunState::att (the split-context records live there)
+    int kv_format = Q4_KV_FP16;     // fixed at build time (q4_set_kv_format). Q4_KV_FP8: RunState::key_cache / value_cache point at [layer][seq_len][kv_dim] e4m3 BYTES, and
+    int8_t* k_exp = nullptr;        // [layer][n_kv_heads][seq_len] row exponents (contiguous per head: a chunk reads a run of bytes),
+    int8_t* v_exp = nullptr;
+    q4_half* k_row = nullptr;       // [kv_dim] fp16 staging rows: the current position's K (rotated) and V between the QKV launch and the attention launch that appends them
+    q4_half* v_row = nullptr;       // (all four live in the state slab, behind RunState's buffers -- RunState's layout is ABI -- and are zeroed with it)
     double kv_price = 0.0;          // 10 ns ticks per context position of this model's K / V stream on this device (measure_kv_price), 0.0: not measured
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)

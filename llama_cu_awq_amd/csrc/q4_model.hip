@@ -4,13 +4,16 @@
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 #include <type_traits>
+#include <vector>
 #include "q4_model.h"
 
 namespace q4 {
 
 hipStream_t g_stream = nullptr;
 int g_fusion = 5;
+int g_kv_format = Q4_KV_FP16;
 int g_multi_steps = Q4_MULTI_STEPS;   // greedy steps per graph replay in the token loops (profiling build: q4_set_gemv_early(7, n))
 int g_use_graphs = 1;
 int g_quiet = 0;
@@ -108,7 +111,7 @@ static void carve_weights(SlabCursor& c, TransformerWeights* w, const Config* p,
 
 // malloc_run_state :38-67. att holds n_heads*max(seq_len, dim) halves (the reference's n_heads*dim overflows
 // for seq_len > dim); this build's attention does not use it at all.
-static void carve_state(SlabCursor& c, RunState* s, const Config* p) {
+static void carve_state(SlabCursor& c, RunState* s, const Config* p, Model& m) {
     const int kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
     s->x = (q4_half*)c.take((size_t)p->dim * sizeof(q4_half));
     s->xb = (q4_half*)c.take((size_t)p->dim * sizeof(q4_half));
@@ -116,9 +119,16 @@ static void carve_state(SlabCursor& c, RunState* s, const Config* p) {
     s->q = (q4_half*)c.take((size_t)p->dim * sizeof(q4_half));
     s->att = (q4_half*)c.take(att_buffer_bytes(p));
     s->logits = (q4_half*)c.take((size_t)p->vocab_size * sizeof(q4_half));
-    s->key_cache = (q4_half*)c.take(sizeof(q4_half) * p->n_layers * p->seq_len * kv_dim);
-    s->value_cache = (q4_half*)c.take(sizeof(q4_half) * p->n_layers * p->seq_len * kv_dim);
+    const size_t kv_elem = m.kv_format == Q4_KV_FP8 ? 1 : sizeof(q4_half);     // FP8: one byte per element, half the fp16 caches
+    s->key_cache = (q4_half*)c.take(kv_elem * p->n_layers * p->seq_len * kv_dim);
+    s->value_cache = (q4_half*)c.take(kv_elem * p->n_layers * p->seq_len * kv_dim);
     s->pos = (int*)c.take(sizeof(int));
+    if (m.kv_format == Q4_KV_FP8) {
+        m.k_exp = (int8_t*)c.take((size_t)p->n_layers * p->n_kv_heads * p->seq_len);
+        m.v_exp = (int8_t*)c.take((size_t)p->n_layers * p->n_kv_heads * p->seq_len);
+        m.k_row = (q4_half*)c.take((size_t)kv_dim * sizeof(q4_half));
+        m.v_row = (q4_half*)c.take((size_t)kv_dim * sizeof(q4_half));
+    }
 }
 
 // zeroed on the launch stream and waited for: a null-stream hipMemset returns before the device has finished, and nothing orders it
@@ -206,11 +216,11 @@ static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
 
     RunState* s = &t->state;
     SlabCursor sd = {nullptr, 0};
-    carve_state(sd, s, p);
+    carve_state(sd, s, p, m);
     if (hipMalloc(&m.state, sd.off) != hipSuccess) { printf("malloc failed for allocaing run state!\n"); return Q4_ERR_ALLOC; }
     zero_on_stream(m.state, sd.off);
     cur = {(char*)m.state, 0};
-    carve_state(cur, s, p);
+    carve_state(cur, s, p, m);
     m.att_bytes = att_buffer_bytes(p);
     if (hipHostMalloc(&m.shared, sizeof(SharedData), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {   // cudaMallocHost :50
         printf("malloc failed for allocaing run state!\n");
@@ -232,7 +242,7 @@ static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
     if (hipMalloc((void**)&m.sync, sync_words * sizeof(unsigned)) == hipSuccess) {
         zero_on_stream(m.sync, sync_words * sizeof(unsigned));
         m.sync_words = sync_words;
-        m.kv_price = measure_kv_price(p, s, m.sync);
+        if (m.kv_format == Q4_KV_FP16) m.kv_price = measure_kv_price(p, s, m.sync);   // (prices the fp16 split-context attention -> o-proj launch, which an FP8 model never runs)
     } else {
         (void)hipGetLastError();    // no hand-off words: the network runs its five-launch sequence
         m.sync = nullptr;
@@ -356,6 +366,14 @@ int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perple
     if (!t->weights.layers) { printf("malloc failed!\n"); fclose(file); return Q4_ERR_ALLOC; }
     // the first allocation exists: the record is registered, and from here every failure leaves through q4_free_transformer
     Model& m = models()[&t->state] = Model{};
+    m.kv_format = g_kv_format;
+    if (m.kv_format == Q4_KV_FP8 && !kv8_head_size_ok(p->dim / p->n_heads)) {
+        snprintf(g_last_error, sizeof(g_last_error), "FP8 KV cache: head size %d is not supported (64, 128 or 256)", p->dim / p->n_heads);
+        printf("%s\n", g_last_error);
+        fclose(file);
+        q4_free_transformer(t);
+        return Q4_ERR_UNSUPPORTED_SIZE;
+    }
     const int rc = load_model(t, m, file, perplexity);
     fclose(file);
     if (rc) q4_free_transformer(t);
@@ -377,6 +395,14 @@ void q4_free_transformer(Transformer* t) {                                      
     free(t->weights.layers);
     memset(t, 0, sizeof(*t));
 }
+
+int q4_set_kv_format(int format) {
+    if (format != Q4_KV_FP16 && format != Q4_KV_FP8) return Q4_ERR_ARG;
+    g_kv_format = format;
+    return Q4_OK;
+}
+int q4_get_kv_format(void) { return g_kv_format; }
+int q4_kv_format_of(const RunState* s) { const Model* m = model_of(s); return m ? m->kv_format : Q4_KV_FP16; }
 
 double q4_kv_stream_price(const RunState* s) { const Model* m = model_of(s); return m ? m->kv_price : 0.0; }
 
@@ -406,6 +432,26 @@ int q4_get_kv_row(const Transformer* t, int layer, int pos, q4_half* host_k, q4_
     const int kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
     const size_t off = (size_t)layer * p->seq_len * kv_dim + (size_t)pos * kv_dim;
     Q4_HIP(hipStreamSynchronize(g_stream));
+    const Model* m = model_of(&t->state);
+    if (m && m->kv_format == Q4_KV_FP8) {      // bytes * 2^e, exactly an fp16 number each
+        const int head_size = p->dim / p->n_heads;
+        std::vector<uint8_t> b(kv_dim);
+        std::vector<int8_t> e(p->n_kv_heads);
+        for (int which = 0; which < 2; which++) {
+            const uint8_t* bytes = (const uint8_t*)(which ? t->state.value_cache : t->state.key_cache) + off;
+            const int8_t* exps = (which ? m->v_exp : m->k_exp) + (size_t)layer * p->n_kv_heads * p->seq_len + pos;
+            Q4_HIP(hipMemcpy(b.data(), bytes, (size_t)kv_dim, hipMemcpyDeviceToHost));
+            Q4_HIP(hipMemcpy2D(e.data(), 1, exps, (size_t)p->seq_len, 1, (size_t)p->n_kv_heads, hipMemcpyDeviceToHost));
+            q4_half* out = which ? host_v : host_k;
+            for (int i = 0; i < kv_dim; i++) {
+                const int E = (b[i] >> 3) & 15, M = b[i] & 7;
+                const float mag = E ? ldexpf(1.0f + M / 8.0f, E - 7) : ldexpf(M / 8.0f, -6);      // OCP e4m3fn (the quantiser never writes a NaN byte)
+                const _Float16 v = (_Float16)ldexpf((b[i] & 0x80) ? -mag : mag, e[i / head_size]);
+                memcpy(&out[i], &v, sizeof(v));
+            }
+        }
+        return Q4_OK;
+    }
     Q4_HIP(hipMemcpy(host_k, t->state.key_cache + off, (size_t)kv_dim * sizeof(q4_half), hipMemcpyDeviceToHost));
     Q4_HIP(hipMemcpy(host_v, t->state.value_cache + off, (size_t)kv_dim * sizeof(q4_half), hipMemcpyDeviceToHost));
     return Q4_OK;

@@ -56,10 +56,11 @@ static NetForms net_forms(const Config* p, const RunState* s, const Model* m, in
     const int dim = p->dim, hidden_dim = p->hidden_dim, head_size = dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
     const bool sync = m && m->sync;
     NetForms f;
-    f.ao_form = g_fusion >= 3 && sync ? attention_oproj_form(dim, kv_dim, head_size, p->n_heads, seq_len_bin, s->att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk) : -1;
+    const bool kv8 = m && m->kv_format == Q4_KV_FP8;   // FP8 cache: QKV into the staging rows, launch_attention_kv8, o-proj; the FFN half as the level chooses, without fq / fa
+    f.ao_form = g_fusion >= 3 && sync && !kv8 ? attention_oproj_form(dim, kv_dim, head_size, p->n_heads, seq_len_bin, s->att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk) : -1;
     f.ao = f.ao_form >= 0;
     f.fp = g_fusion >= 4 && sync && ffn_pair_covers(dim, hidden_dim);
-    f.fq = f.fp && g_fusion >= 5 && ffn_qkv_covers(dim, hidden_dim, kv_dim, head_size, m->rope_table != nullptr);
+    f.fq = f.fp && !kv8 && g_fusion >= 5 && ffn_qkv_covers(dim, hidden_dim, kv_dim, head_size, m->rope_table != nullptr);
     f.fa = f.fq && g_fusion >= 6 && (f.ao_form == 5 || f.ao_form == 6) && layer_att_covers(dim, hidden_dim, kv_dim, p->n_heads, seq_len_bin) && !(g_skip & 15);
     return f;
 }
@@ -77,6 +78,9 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
     const Model* m = model_of(s);
     const float2* rope_table = m ? m->rope_table : nullptr;
     unsigned* sync = m ? m->sync : nullptr;
+    const bool kv8 = m && m->kv_format == Q4_KV_FP8;
+    uint8_t* const k8 = (uint8_t*)s->key_cache;     // (FP8 models: the caches are bytes)
+    uint8_t* const v8 = (uint8_t*)s->value_cache;
 
     if (!have_embedding)
         Q4_UNLESS(64, q4_copy_embedding(x, w->token_embedding_table, dim, s->shared_data->tokens, pPos));   // :294
@@ -92,6 +96,10 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
         const long long loff = (long long)l * p->seq_len * kv_dim;
         if (qkv_done) {
             qkv_done = false;
+        } else if (kv8) {
+            // ... at EVERY fusion level (the same bits as the 1:1 chain), this position's K / V left in the fp16 staging rows: the attention launch appends them
+            Q4_UNLESS(1, launch_qkv_fused(s->q, m->k_row, m->v_row, x, L->rms_att_weight, &L->wq_q, &L->wq_k, &L->wq_v,
+                                          dim, kv_dim, 0, pPos, head_size, p->rope_theta, rope_table, f.fp ? sync + SYNC_EPOCH : nullptr, true));
         } else if (g_fusion) {
             // rmsnorm (:300) + qkv (:307, or the three GEMVs of the GQA branch :310-312) + RoPE (:317) in one launch
             Q4_UNLESS(1, launch_qkv_fused(s->q, s->key_cache, s->value_cache, x, L->rms_att_weight, &L->wq_q, &L->wq_k, &L->wq_v,
@@ -107,7 +115,12 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
             }
             Q4_TRY(q4_rope_rotation(s->q, s->key_cache + loff, p->n_heads, p->n_kv_heads, head_size, pPos, 0, p->rope_theta));   // :317
         }
-        if (f.fa) {
+        if (kv8) {
+            const size_t eoff = (size_t)l * p->n_kv_heads * p->seq_len;
+            Q4_UNLESS(2, launch_attention_kv8(s->xb, s->q, k8 + loff, v8 + loff, m->k_exp + eoff, m->v_exp + eoff, m->k_row, m->v_row, p->n_heads, head_size, kv_mul,
+                                              seq_len_bin, p->seq_len, pPos, (float*)s->att, att_bytes, sync && p->n_heads <= SYNC_MAX_HEADS ? sync + SYNC_ARRIVE : nullptr));
+            Q4_UNLESS(4, q4_matmul_q4(s->x, s->xb, &L->wq_o, dim, dim, 1, -1, nullptr));
+        } else if (f.fa) {
             // (phases A and O of the launch below)
         } else if (f.ao) {
             Q4_UNLESS(6, launch_attention_oproj(x, s->xb, s->q, s->key_cache + loff, s->value_cache + loff, &L->wq_o, dim, kv_dim, p->n_heads,

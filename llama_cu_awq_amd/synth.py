@@ -28,6 +28,7 @@ GROUP_SIZE = 128
 GEOMETRIES = {
     # name: (dim, hidden, layers, heads, kv_heads, vocab, seq_len, rope_theta)
     "7b": (4096, 11008, 32, 32, 32, 32000, 2048, 10000.0),
+    "7b_16k": (4096, 11008, 32, 32, 32, 32000, 16384, 10000.0),      # 7B with a 16 K context: the K / V stream measurement (tools/bench_kv8.py)
     "13b": (5120, 13824, 40, 40, 40, 32000, 2048, 10000.0),
     "mistral7b": (4096, 14336, 32, 32, 8, 32000, 2048, 1000000.0),   # GQA 4:1, the shape of Mistral-7B / CodeLlama-style models
     "tiny": (256, 352, 2, 4, 4, 512, 64, 10000.0),
