@@ -205,6 +205,18 @@ int q4_convert_fp16_to_fp32(float* out, const q4_half* in, int elements);
  * pPos: host-visible position (SharedData::pos), pPosGpu: device position. Ties -> lowest index. */
 int q4_argmax(const q4_half* x, int size, int* result, volatile int* pPos, int* pPosGpu, int write_token);
 
+/* Not in the reference: log-probabilities under the model's OWN distribution -- temperature 1, no nucleus; NOT the tempered / truncated distribution
+ * the sampler draws from. logits: n >= 1 fp16 values (16-byte aligned). lse[0] = m + log(sum_i exp(l_i - m)), m the maximum, in fp32 (expf / logf, a
+ * fixed summation order: the same input gives the same bits on every launch). top_ids / top_logprobs [top_k]: the top_k entries of highest logit,
+ * ordered by (logit descending, index ascending) -- argmax_kernel's tie rule, entry 0 is the greedy token -- with their log-probabilities l - lse;
+ * the order is exact on the halves (-0 equals +0; -inf contributes 0 and ranks last; a NaN ranks behind everything and makes lse NaN, never a
+ * fault). target: null, or a device-visible int; *target in [0, n) writes target_logprob[0] = l_target - lse, else NaN. All pointers are device
+ * pointers; enqueues on the q4 stream. top_k in [0, Q4_MAX_TOP_LOGPROBS], top_k > n is Q4_ERR_ARG; a vocabulary beyond about 300,000 entries at
+ * top_k 20 (more at a smaller top_k) is Q4_ERR_UNSUPPORTED_SIZE. */
+enum { Q4_MAX_TOP_LOGPROBS = 20 };
+int q4_logprob_topk(const q4_half* logits, int n, int top_k, const int* target, float* lse, float* target_logprob, int* top_ids,
+                    float* top_logprobs);
+
 /* ---- network + per-token step ------------------------------------------------------------- */
 
 /* run_llama_network(int* pPos, Config*, RunState*, TransformerWeights*, int seq_len_bin) llama2_q4.cu:286-340 */
@@ -276,6 +288,23 @@ void q4_reset_graphs(void);   /* drop captured graphs (main() cleanup llama2_q4.
  * this counter is how a host sees that happen. */
 int q4_graph_captures(void);
 
+/* Per-token log-probability records inside the decode step (opt-in, per model; off by default, and then every launch list, every captured graph and
+ * every bit is what it is without this call). top_k = -1: off; 0: the chosen / target token's log-probability only; 1 .. Q4_MAX_TOP_LOGPROBS: also
+ * that many top alternatives. Anything else, a top_k above the vocabulary, or a Transformer the library did not build: Q4_ERR_ARG. Allocates a device
+ * ring of seq_len records {lse, token_logprob, top_ids[K], top_logprobs[K]} (freed by q4_free_transformer or by top_k = -1) and drops the model's
+ * captured graphs that contain the launch; the next steps capture again. The records are those of q4_logprob_topk: the model's own distribution,
+ * temperature 1, no nucleus.
+ * Record p describes step p's logits and the token at ring index p + 1: on a prompt step (gen_token = 0) token_logprob is that of the prompt token
+ * tokens[p + 1]; on a greedy generated step it is entry 0 of the top order (the greedy token, same bits as top_logprobs[0]); on a sampled step it is
+ * that of the token the sampler chose, inside the top k or not. One extra launch per step in front of the sampler (two on sampled steps: a one-wave
+ * launch behind the sampler looks the chosen token up), in every graph variant and in the eager modes. Steps queued past an EOS write records nobody
+ * reads; that is harmless. */
+int q4_set_logprobs(Transformer* t, int top_k);
+int q4_get_logprobs_k(const Transformer* t);      /* -1: off, or a Transformer the library did not build */
+/* Synchronises the stream (like the parity dumps), then copies records first_pos .. first_pos + n - 1 to the host: token_logprob [n], top_ids and
+ * top_logprobs [n x K] (K = q4_get_logprobs_k). Any of the three may be NULL. Records off, or positions outside [0, seq_len]: Q4_ERR_ARG. */
+int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_logprob, int* top_ids, float* top_logprobs);
+
 /* build_sampler / destroy_sampler sampler.h:15-29; random_u32 / random_f32 :31-40; sample :43-82 */
 int build_sampler(Sampler* sampler, int vocab_size, float temperature, float topp, unsigned long long rng_seed);
 void destroy_sampler(Sampler* sampler);
@@ -339,6 +368,12 @@ double q4_parse_dataset_and_compute_perplexity(const char* textFileName, struct 
 /* teacher-forced logits for given token ids (perplexity path without a tokenizer): runs num_tokens steps with
  * copyLogits, returns perplexity of targets[i] under step i's logits */
 float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, int num_tokens);
+/* Teacher-forced scoring without the (seq_len, vocab) fp32 array -- works on a model built with perplexity = 0: logprobs_out[i] is the log-probability of
+ * tokens_with_bos[i + 1] under step i's logits, i < num_tokens <= seq_len - 1 (more: Q4_ERR_ARG). The steps are queued like generate()'s prompt steps
+ * (q4_steps_that_fit / q4_run_transformer_steps), one synchronise at the end, one retry after a timed-out hand-off. Records are switched on with
+ * top_k = 0 for the call if they were off, and the setting is put back -- the ring and the graphs with the record launch then live for one call (each
+ * such call captures them again, q4_graph_captures counts it): a host that scores repeatedly calls q4_set_logprobs(t, 0) once beforehand. */
+int q4_score_ids(Transformer* t, Sampler* s, const int* tokens_with_bos, int num_tokens, float* logprobs_out);
 
 /* ---- tokenizer.h:1-223 ------------------------------------------------------------------------ */
 struct Tokenizer* q4_tokenizer_new(const char* tokenizer_path, int vocab_size);   /* build_tokenizer :35-59 */

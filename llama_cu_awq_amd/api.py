@@ -17,6 +17,7 @@ PROF_LIB_PATH = os.path.join(_HERE, "libllama2_q4_prof.so")
 MAX_SEQ_LEN = 128 * 1024
 KV_FP16, KV_FP8 = 0, 1          # q4_set_kv_format
 KV_FORMATS = {"fp16": KV_FP16, "fp8": KV_FP8}
+MAX_TOP_LOGPROBS = 20           # Q4_MAX_TOP_LOGPROBS
 
 
 class Config(C.Structure):
@@ -65,6 +66,7 @@ SYMBOLS = [
     "q4_parse_dataset_and_compute_perplexity", "q4_perplexity_ids", "q4_tokenizer_new", "q4_tokenizer_delete",
     "q4_tokenizer_encode", "q4_tokenizer_decode", "q4_tokenizer_max_token_length", "q4_main", "q4_parse_args",
     "q4_bench_kernel", "q4_bench_kernel_graph", "q4_bench_in_network", "q4_device_info",
+    "q4_logprob_topk", "q4_set_logprobs", "q4_get_logprobs_k", "q4_get_logprobs", "q4_score_ids",
 ]
 
 _lib = None
@@ -117,6 +119,7 @@ def lib():
     L.q4_argmax.argtypes = [vp, i, vp, vp, vp, i]
     L.q4_run_llama_network.argtypes = [vp, C.POINTER(Config), C.POINTER(RunState), C.POINTER(TransformerWeights), i]
     L.q4_run_transformer.argtypes = [i, C.POINTER(Config), C.POINTER(RunState), C.POINTER(TransformerWeights), i, vp]
+    L.q4_run_transformer_at.argtypes = [i, i, C.POINTER(Config), C.POINTER(RunState), C.POINTER(TransformerWeights), i, vp]
     L.q4_set_fusion.argtypes = [i]
     L.q4_set_fusion.restype = None
     if hasattr(L, "q4_set_kv_format"):             # (older builds under tools/ab.py do not have it)
@@ -188,6 +191,12 @@ def lib():
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i)]
     L.q4_bench_in_network.restype = C.c_double
     L.q4_device_info.argtypes = [C.c_char_p, i, C.POINTER(i), C.POINTER(C.c_size_t)]
+    if hasattr(L, "q4_set_logprobs"):              # (older builds under tools/ab.py do not have it)
+        L.q4_logprob_topk.argtypes = [vp, i, i, vp, vp, vp, vp, vp]
+        L.q4_set_logprobs.argtypes = [vp, i]
+        L.q4_get_logprobs_k.argtypes = [vp]
+        L.q4_get_logprobs.argtypes = [vp, i, i, vp, vp, vp]
+        L.q4_score_ids.argtypes = [vp, vp, vp, i, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -293,6 +302,12 @@ def MultiHeadAttention(output, q, key_cache, value_cache, att, num_heads, head_s
                                         att.ptr if att else None, num_heads, head_size, kv_mul, max_seq_len, pPos.ptr))
 
 
+def logprob_topk(logits, n, top_k, target, lse, target_logprob, top_ids=None, top_logprobs=None):
+    """q4_logprob_topk over DevBufs: the model's own distribution (temperature 1, no nucleus). target: a DevBuf holding one int32, or None."""
+    check(lib().q4_logprob_topk(logits.ptr, n, top_k, target.ptr if target else None, lse.ptr, target_logprob.ptr,
+                                top_ids.ptr if top_ids else None, top_logprobs.ptr if top_logprobs else None))
+
+
 def synchronize():
     check(lib().q4_stream_synchronize())
 
@@ -308,7 +323,7 @@ def device_info():
 class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
-    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16"):
+    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -337,6 +352,12 @@ class Transformer:
         self.sampler = L.q4_sampler_new(self.config.vocab_size, temperature, topp, seed)
         if not self.sampler:
             raise Q4Error("build_sampler failed")
+        if logprobs is not None:
+            try:
+                self.set_logprobs(logprobs)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         L = lib()
@@ -360,6 +381,11 @@ class Transformer:
     def run_transformer(self, gen_token, copy_logits=False):
         check(lib().q4_run_transformer(int(gen_token), C.byref(self.config), self.state, self.weights, int(copy_logits),
                                        self.sampler))
+
+    def run_transformer_at(self, pos, gen_token, copy_logits=False):
+        """the step with the position supplied by the caller: queued behind the previous one, nothing is read back (q4_run_transformer_at)"""
+        check(lib().q4_run_transformer_at(int(pos), int(gen_token), C.byref(self.config), self.state, self.weights, int(copy_logits),
+                                          self.sampler))
 
     def logits(self):
         out = np.empty(self.config.vocab_size, dtype=np.float16)
@@ -397,6 +423,30 @@ class Transformer:
         if tps < 0:
             raise Q4Error("generate failed: " + lib().q4_last_error().decode())
         return out[: timed.value + 2], tps, timed.value, secs.value
+
+    def set_logprobs(self, top_k):
+        """Per-token log-probability records inside the decode step: None / -1 off, 0 the chosen or target token only, K <= 20 also the top K."""
+        check(lib().q4_set_logprobs(self.h, -1 if top_k is None else int(top_k)))
+
+    def logprobs_k(self):
+        return lib().q4_get_logprobs_k(self.h)
+
+    def logprobs(self, first_pos, n):
+        """(token_logprob [n], top_ids [n, K], top_logprobs [n, K]) of records first_pos .. first_pos + n - 1; synchronises. Record p describes step p's
+        logits and the token at ring index p + 1, under the model's own distribution (temperature 1, no nucleus)."""
+        k = max(self.logprobs_k(), 0)
+        tok = np.empty(n, dtype=np.float32)
+        ids = np.empty((n, k), dtype=np.int32)
+        top = np.empty((n, k), dtype=np.float32)
+        check(lib().q4_get_logprobs(self.h, first_pos, n, tok.ctypes.data, ids.ctypes.data if k else None, top.ctypes.data if k else None))
+        return tok, ids, top
+
+    def score_ids(self, tokens_with_bos):
+        """Teacher-forced log-probabilities of tokens_with_bos[1:] (no logits_array needed: works on a perplexity=False build)."""
+        t = np.ascontiguousarray(tokens_with_bos, dtype=np.int32)
+        out = np.empty(t.shape[0] - 1, dtype=np.float32)
+        check(lib().q4_score_ids(self.h, self.sampler, t.ctypes.data, t.shape[0] - 1, out.ctypes.data))
+        return out
 
     def perplexity_ids(self, tokens_with_bos):
         t = np.ascontiguousarray(tokens_with_bos, dtype=np.int32)

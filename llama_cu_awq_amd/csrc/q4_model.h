@@ -23,6 +23,13 @@ struct Model {
     q4_half* k_row = nullptr;       // [kv_dim] fp16 staging rows: the current position's K (rotated) and V between the QKV launch and the attention launch that appends them
     q4_half* v_row = nullptr;       // (all four live in the state slab, behind RunState's buffers -- RunState's layout is ABI -- and are zeroed with it)
     double kv_price = 0.0;          // 10 ns ticks per context position of this model's K / V stream on this device (measure_kv_price), 0.0: not measured
+    int logprobs_k = -1;            // q4_set_logprobs: -1 off, else the K of the record ring below (one allocation, lp_ring, carved into arrays by position)
+    void* lp_ring = nullptr;
+    float* lp_lse = nullptr;        // [seq_len]
+    float* lp_token = nullptr;      // [seq_len] token_logprob
+    int* lp_ids = nullptr;          // [seq_len][K]
+    float* lp_top = nullptr;        // [seq_len][K]
+    q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
 using Models = std::map<const RunState*, Model>;
@@ -40,5 +47,11 @@ static inline Model* model_of(const RunState* s) {
 int run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding);
 // q4_step.hip
 void drop_graphs_of(const RunState* s);   // the model's captured graphs, after the launch stream has drained
+void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the log-probability launch only
+// q4_logprobs.hip. The record launch of a step (in front of the sampler: reads the position before it advances) and the chosen token's look-up behind
+// the sampler of a sampled step
+bool logprobs_size_ok(int n, int top_k);
+int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_token, bool greedy);
+int launch_logprobs_pick(const Model* m, const Config* p, RunState* s);
 
 }  // namespace q4

@@ -387,7 +387,7 @@ void q4_free_transformer(Transformer* t) {                                      
     if (it != models().end()) {
         const Model& m = it->second;
         hipDeviceSynchronize();
-        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync})
+        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync, m.lp_ring})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);
         models().erase(it);

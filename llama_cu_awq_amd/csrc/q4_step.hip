@@ -39,7 +39,7 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
 }
 
 // graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
-// bit3 = Q4_MULTI_STEPS steps per graph. A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -49,8 +49,8 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][16];
-    bool captured[Q4_MAX_GRAPHS][16];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][32];
+    bool captured[Q4_MAX_GRAPHS][32];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
@@ -59,31 +59,36 @@ static GraphSet g_sets[GRAPH_OWNERS];
 static unsigned long long g_set_clock = 0;
 static int g_graph_captures = 0;
 // a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
-static void drop_graphs(GraphSet& gs, bool sampled_only) {
+// mask: 0 drops every variant and gives the set up; 4 the sampled variants (what they have baked in is forgotten); 16 those with the record launch
+static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 16; v++)
-            if (gs.captured[i][v] && (!sampled_only || (v & 4))) {
+        for (int v = 0; v < 32; v++)
+            if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
                 gs.captured[i][v] = false;
             }
-    if (!sampled_only) gs.owner = nullptr;
-    gs.sampler = nullptr; gs.coins = nullptr;
+    if (!mask) gs.owner = nullptr;
+    if (!mask || (mask & 4)) { gs.sampler = nullptr; gs.coins = nullptr; }
 }
 void drop_graphs_of(const RunState* s) {
     for (GraphSet& gs : g_sets)
-        if (gs.owner == s) drop_graphs(gs, false);
+        if (gs.owner == s) drop_graphs(gs, 0);
+}
+void drop_logprob_graphs_of(const RunState* s) {
+    for (GraphSet& gs : g_sets)
+        if (gs.owner == s) drop_graphs(gs, 16);
 }
 static GraphSet& graph_set_of(const RunState* owner, const Config* p, const TransformerWeights* w) {
     GraphSet* pick = nullptr;
     for (GraphSet& gs : g_sets)
         if (gs.owner == owner) { pick = &gs; break; }
-    if (pick && (pick->config != p || pick->weights != w)) drop_graphs(*pick, false);   // the same RunState with another Config or other weights
+    if (pick && (pick->config != p || pick->weights != w)) drop_graphs(*pick, 0);   // the same RunState with another Config or other weights
     if (!pick || !pick->owner) {
         for (GraphSet& gs : g_sets)
             if (!pick || (gs.owner == nullptr && pick->owner != nullptr) || (((gs.owner == nullptr) == (pick->owner == nullptr)) && gs.used < pick->used)) pick = &gs;
-        if (pick->owner) drop_graphs(*pick, false);
+        if (pick->owner) drop_graphs(*pick, 0);
         pick->owner = owner; pick->config = p; pick->weights = w;
     }
     pick->used = ++g_set_clock;
@@ -111,7 +116,7 @@ void q4_set_fusion(int level) {
 int q4_get_fusion(void) { return g_fusion; }
 
 void q4_reset_graphs(void) {
-    for (GraphSet& gs : g_sets) drop_graphs(gs, false);
+    for (GraphSet& gs : g_sets) drop_graphs(gs, 0);
 }
 int q4_graph_captures(void) { return g_graph_captures; }
 
@@ -154,7 +159,7 @@ void destroy_sampler(Sampler* sampler) {
     auto cr = g_coin_rings.find(sampler);
     if (cr != g_coin_rings.end()) {
         for (GraphSet& gs : g_sets)
-            if (gs.sampler == sampler) drop_graphs(gs, true);
+            if (gs.sampler == sampler) drop_graphs(gs, 4);
         if (g_stream) hipStreamSynchronize(g_stream);
         if (cr->second.host) hipHostFree(cr->second.host);
         if (cr->second.dev) hipFree(cr->second.dev);
@@ -241,18 +246,20 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
     const int graphIndex = graph_bin(seq_len, p, &seq_len_bin);
     if (nsteps != 1 && (nsteps != g_multi_steps || g_use_graphs != 1)) return Q4_ERR_ARG;
     if (pos < 0 || pos + nsteps > p->seq_len) return Q4_ERR_ARG;
+    const Model* lpm = model_of(s);                                                // q4_set_logprobs: a record launch between the classifier and the sampler
+    if (lpm && lpm->logprobs_k < 0) lpm = nullptr;
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
-        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0);
+        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0);
         CoinRing* ring = nullptr;
         if (!greedy) {     // the sampling kernel is part of the graph: its temperature, top-p, scratch and coin ring are baked in
             Q4_TRY(coin_ring_for(pSampler, p->seq_len, &ring));
             Q4_TRY(q4_sample_topp_prepare(pSampler));     // scratch + LDS opt-in: not capturable
             if (gs.sampler != pSampler || gs.temperature != pSampler->temperature || gs.topp != pSampler->topp || gs.coins != ring->dev) {
-                drop_graphs(gs, true);
+                drop_graphs(gs, 4);
                 gs.sampler = pSampler; gs.temperature = pSampler->temperature; gs.topp = pSampler->topp; gs.coins = ring->dev;
             }
         }
@@ -267,6 +274,7 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
             for (int i = 0; i < nsteps && !rc; i++) {
                 rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0);
                 if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
+                if (!rc && lpm) rc = launch_logprobs_step(lpm, p, s, gen_token, greedy);   // (before the sampler: it advances the position and overwrites the logits)
                 if (!rc && greedy) {
                     if (feed && i + 1 < nsteps)
                         rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
@@ -275,6 +283,7 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
                         rc = q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, gen_token);
                 } else if (!rc) {   // sampler.h:51-81 inside the graph: the coin comes from the ring, by position
                     rc = q4_sample_topp_device(pSampler, s, 0.f, ring->dev, feed && i + 1 < nsteps ? s->x : nullptr, w->token_embedding_table, p->dim);
+                    if (!rc && lpm) rc = launch_logprobs_pick(lpm, p, s);
                 }
             }
             hipError_t e = hipStreamEndCapture(g_stream, &graph);
@@ -296,7 +305,9 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
     }
     Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false));   // :374
     if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
-    return sample_impl(pSampler, s, gen_token, true);
+    if (lpm) Q4_TRY(launch_logprobs_step(lpm, p, s, gen_token, greedy));
+    Q4_TRY(sample_impl(pSampler, s, gen_token, true));
+    return lpm && !greedy ? launch_logprobs_pick(lpm, p, s) : Q4_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -478,6 +489,81 @@ float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with
     float pplx = compute_perplexity(tokens_with_bos + 1, logits_arr, num_tokens, config->vocab_size);   // :91
     free(logits_arr);
     return pplx;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// log-probability records (q4_logprobs.hip): the per-model switch, the read-out, teacher-forced scoring. Not in the reference.
+int q4_set_logprobs(Transformer* t, int top_k) {
+    if (!t || top_k < -1 || top_k > Q4_MAX_TOP_LOGPROBS) return Q4_ERR_ARG;
+    Model* m = model_of(&t->state);
+    if (!m || top_k > t->config.vocab_size) return Q4_ERR_ARG;
+    if (top_k == m->logprobs_k) return Q4_OK;
+    if (top_k >= 0 && !logprobs_size_ok(t->config.vocab_size, top_k)) return Q4_ERR_UNSUPPORTED_SIZE;
+    const size_t S = (size_t)t->config.seq_len, K = (size_t)(top_k < 0 ? 0 : top_k);
+    const size_t side = ((size_t)t->config.vocab_size * sizeof(q4_half) + 255) / 256 * 256;
+    const size_t bytes = side + S * sizeof(float) * 2 + S * K * (sizeof(int) + sizeof(float));
+    void* ring = nullptr;                                                          // the new ring first: a failed allocation leaves the setting as it was
+    if (top_k >= 0 && hipMalloc(&ring, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+    drop_logprob_graphs_of(&t->state);
+    (void)hipStreamSynchronize(g_stream);                                         // an eager launch may still be writing the old ring
+    if (m->lp_ring) (void)hipFree(m->lp_ring);
+    m->lp_ring = nullptr; m->lp_lse = m->lp_token = m->lp_top = nullptr; m->lp_ids = nullptr; m->lp_side = nullptr;
+    m->logprobs_k = -1;
+    if (top_k < 0) return Q4_OK;
+    m->lp_ring = ring;
+    Q4_HIP(hipMemsetAsync(m->lp_ring, 0, bytes, g_stream));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    char* c = (char*)m->lp_ring;
+    m->lp_side = (q4_half*)c; c += side;
+    m->lp_lse = (float*)c; c += S * sizeof(float);
+    m->lp_token = (float*)c; c += S * sizeof(float);
+    m->lp_ids = (int*)c; c += S * K * sizeof(int);
+    m->lp_top = (float*)c;
+    m->logprobs_k = top_k;
+    return Q4_OK;
+}
+int q4_get_logprobs_k(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m ? m->logprobs_k : -1;
+}
+int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_logprob, int* top_ids, float* top_logprobs) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || m->logprobs_k < 0 || first_pos < 0 || n < 0 || (long long)first_pos + n > t->config.seq_len) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const size_t K = (size_t)m->logprobs_k, f = (size_t)first_pos;
+    if (n == 0) return Q4_OK;
+    if (token_logprob) Q4_HIP(hipMemcpy(token_logprob, m->lp_token + f, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (top_ids && K) Q4_HIP(hipMemcpy(top_ids, m->lp_ids + f * K, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost));
+    if (top_logprobs && K) Q4_HIP(hipMemcpy(top_logprobs, m->lp_top + f * K, (size_t)n * K * sizeof(float), hipMemcpyDeviceToHost));
+    return Q4_OK;
+}
+int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, int num_tokens, float* logprobs_out) {
+    if (!t || !sampler || !tokens_with_bos || !logprobs_out || num_tokens < 1) return Q4_ERR_ARG;
+    Config* config = &t->config;
+    RunState* state = &t->state;
+    const Model* m = model_of(state);
+    if (!m || num_tokens > config->seq_len - 1) return Q4_ERR_ARG;
+    const int before = m->logprobs_k;
+    if (before < 0) Q4_TRY(q4_set_logprobs(t, 0));
+    const unsigned long long rng0 = sampler->rng_state;
+    int rc = Q4_OK;
+    for (int attempt = 0; !rc; attempt++) {
+        rc = q4_reset_sequence(state, tokens_with_bos, num_tokens + 1);
+        // every input token is known: the steps go out like generate()'s prompt steps (a target is the NEXT ring entry), up to Q4_MULTI_STEPS per replay
+        for (int pos = 0; pos < num_tokens && !rc;) {
+            const int k = q4_steps_that_fit(pos, num_tokens + 1, num_tokens, config, sampler);
+            rc = q4_run_transformer_steps(pos, k, 0, config, state, &t->weights, 0, sampler);
+            pos += k;
+        }
+        if (!rc && hipStreamSynchronize(g_stream) != hipSuccess) rc = Q4_ERR_HIP;
+        if (rc || !q4_handoff_status(state)) break;
+        // a timed-out in-launch wait: the library has dropped to fusion level 1 and cleared its state; redo the pass once
+        if (attempt > 0) rc = Q4_ERR_HIP;
+        sampler->rng_state = rng0;
+    }
+    if (!rc) rc = q4_get_logprobs(t, 0, num_tokens, logprobs_out, nullptr, nullptr);
+    if (before < 0) { const int rc2 = q4_set_logprobs(t, -1); if (!rc) rc = rc2; }
+    return rc;
 }
 
 }  // extern "C"
