@@ -305,6 +305,27 @@ int q4_get_logprobs_k(const Transformer* t);      /* -1: off, or a Transformer t
  * top_logprobs [n x K] (K = q4_get_logprobs_k). Any of the three may be NULL. Records off, or positions outside [0, seq_len]: Q4_ERR_ARG. */
 int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_logprob, int* top_ids, float* top_logprobs);
 
+/* The classifier of a greedy step without streaming every fp16 row of wcls (csrc/cls_screen.h): where the classifier runs as strips (dim 4096 or
+ * 5120, at least 64 vocabulary rows per CU, an unmasked stream) q4_build_transformer derives a per-row-scaled int8 copy of wcls (vocab x dim bytes: 131 MB
+ * at 7B, 164 MB at 13B; a failed allocation leaves the model without it, which is not an error). A screened step streams that copy, bounds every logit,
+ * computes the exact fp16 logit of the rows that can still be the largest and takes the argmax of those: the token is the one the full classifier gives, bit
+ * for bit and tie for tie. RunState::logits then holds the exact logits of the candidate rows and -inf elsewhere, so only steps whose logits nobody reads are
+ * screened: greedy generating steps (temperature 0) queued by the library's own token loops (q4_generate, q4_generate_ids, q4_chat) with copyLogits off,
+ * log-probability records off and fusion level >= 1 -- and never the last step a generation queues: after q4_generate* returns, RunState::logits holds the
+ * final position's full logits as before (a generation that stops at EOS ends on whatever step was queued last). q4_run_transformer, _at, _steps and
+ * q4_run_llama_network never screen. q4_set_greedy_screen: 1 (default) on, 0 off; drops captured graphs like q4_set_fusion. */
+void q4_set_greedy_screen(int on);
+int q4_get_greedy_screen(void);
+/* Candidate rows of the model's screened steps so far (synchronises the stream): of the last one, the largest, their sum, and the number of screened steps.
+ * Any pointer may be NULL. All zero for a model without a screening copy; Q4_ERR_ARG for a Transformer the library did not build. */
+int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* total, long long* steps);
+/* Op-level form of a screened step for tests and tools: x [n], w [d][n] and rms_w [n] (may be NULL: x is taken as it is) are device pointers to halves; a
+ * screening copy of w is built and freed inside the call. Host outputs, any may be NULL: the greedy token, A and B [d] floats (approximate logit and radius,
+ * B = +inf where no claim is made), the refined logits [d] halves (exact on candidate rows, -inf elsewhere), the number of candidate rows. Shapes the
+ * classifier's strips do not cover: Q4_ERR_UNSUPPORTED_SIZE. */
+int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const q4_half* rms_w, int* token, float* A, float* B, q4_half* refined,
+                        int* candidates);
+
 /* build_sampler / destroy_sampler sampler.h:15-29; random_u32 / random_f32 :31-40; sample :43-82 */
 int build_sampler(Sampler* sampler, int vocab_size, float temperature, float topp, unsigned long long rng_seed);
 void destroy_sampler(Sampler* sampler);

@@ -67,6 +67,7 @@ SYMBOLS = [
     "q4_tokenizer_encode", "q4_tokenizer_decode", "q4_tokenizer_max_token_length", "q4_main", "q4_parse_args",
     "q4_bench_kernel", "q4_bench_kernel_graph", "q4_bench_in_network", "q4_device_info",
     "q4_logprob_topk", "q4_set_logprobs", "q4_get_logprobs_k", "q4_get_logprobs", "q4_score_ids",
+    "q4_set_greedy_screen", "q4_get_greedy_screen", "q4_screen_candidates", "q4_greedy_screen_op",
 ]
 
 _lib = None
@@ -197,6 +198,11 @@ def lib():
         L.q4_get_logprobs_k.argtypes = [vp]
         L.q4_get_logprobs.argtypes = [vp, i, i, vp, vp, vp]
         L.q4_score_ids.argtypes = [vp, vp, vp, i, vp]
+    if hasattr(L, "q4_set_greedy_screen"):         # (older builds under tools/ab.py do not have it)
+        L.q4_set_greedy_screen.argtypes = [i]
+        L.q4_set_greedy_screen.restype = None
+        L.q4_screen_candidates.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.q4_greedy_screen_op.argtypes = [vp, vp, i, i, vp, C.POINTER(i), vp, vp, vp, C.POINTER(i)]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -306,6 +312,21 @@ def logprob_topk(logits, n, top_k, target, lse, target_logprob, top_ids=None, to
     """q4_logprob_topk over DevBufs: the model's own distribution (temperature 1, no nucleus). target: a DevBuf holding one int32, or None."""
     check(lib().q4_logprob_topk(logits.ptr, n, top_k, target.ptr if target else None, lse.ptr, target_logprob.ptr,
                                 top_ids.ptr if top_ids else None, top_logprobs.ptr if top_logprobs else None))
+
+
+def greedy_screen_op(x, w, n, d, rms_w=None):
+    """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
+    tok, cand = C.c_int(), C.c_int()
+    A = np.empty(d, dtype=np.float32)
+    B = np.empty(d, dtype=np.float32)
+    refined = np.empty(d, dtype=np.float16)
+    check(lib().q4_greedy_screen_op(x.ptr, w.ptr, n, d, rms_w.ptr if rms_w else None, C.byref(tok), A.ctypes.data, B.ctypes.data, refined.ctypes.data,
+                                    C.byref(cand)))
+    return tok.value, A, B, refined, cand.value
+
+
+def set_greedy_screen(on):
+    lib().q4_set_greedy_screen(int(on))
 
 
 def synchronize():
@@ -423,6 +444,13 @@ class Transformer:
         if tps < 0:
             raise Q4Error("generate failed: " + lib().q4_last_error().decode())
         return out[: timed.value + 2], tps, timed.value, secs.value
+
+    def screen_candidates(self):
+        """(last, max, total, steps) of the model's screened greedy steps (q4_screen_candidates); synchronises."""
+        last, mx = C.c_int(), C.c_int()
+        total, steps = C.c_longlong(), C.c_longlong()
+        check(lib().q4_screen_candidates(self.h, C.byref(last), C.byref(mx), C.byref(total), C.byref(steps)))
+        return last.value, mx.value, total.value, steps.value
 
     def set_logprobs(self, top_k):
         """Per-token log-probability records inside the decode step: None / -1 off, 0 the chosen or target token only, K <= 20 also the top K."""

@@ -153,6 +153,10 @@ static void die_on(int rc) {
     if (rc) { printf("\n%s\n", q4_status_string(rc)); exit(EXIT_FAILURE); }        // the reference's printf + exit
 }
 
+// q4_step.hip, not exported: q4_run_transformer_steps for a token loop that does not read the group's logits (the greedy screen, cls_screen.h)
+extern "C" __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
+                                                                                    int copyLogits, Sampler* pSampler, int may_screen);
+
 // generate(), llama2_q4.cu:436-492
 double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sampler, const char* prompt, int steps,
                    int* timed_tokens_out, double* seconds_out) {
@@ -187,7 +191,8 @@ double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sample
                 const int k = q4_steps_that_fit(pos, num_prompt_tokens, steps, &transformer->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                die_on(q4_run_transformer_steps(pos, k, pos >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler));
+                // (every group but the one with the generation's last step may screen its classifier: nobody reads those logits)
+                die_on(run_transformer_steps_screenable(pos, k, pos >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + k < steps));
                 queued = pos + k;
             }
             die_on(q4_wait_pos(state, pos));                                           // :468
@@ -272,7 +277,8 @@ void q4_chat(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sam
                 transformer->state.shared_data->tokens[pos + i] = prompt_tokens[i];   // :573
         }
         die_on(q4_stream_synchronize());                                           // :578
-        die_on(q4_run_transformer(user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler));
+        // (q4_run_transformer's step; a greedy generating step may screen its classifier: only its token is read. Not the last one.)
+        die_on(run_transformer_steps_screenable(q4_shared_pos(state), 1, user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + 1 < steps));
         user_idx++;
         if (user_idx > 0) {
             next = q4_shared_token(state, pos);                                    // :584

@@ -137,6 +137,7 @@ int classifier_with_final_norm(q4_half* logits, q4_half* x, const q4_half* rms_w
 // Opt `kernel` in to `bytes` of dynamic LDS (more than 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize), once per (kernel, device):
 // a process-wide flag would leave a second device's kernels at 64 KiB after q4_set_device. Not a stream operation: outside any capture.
 int lds_opt_in(const void* kernel, size_t bytes);
+bool classifier_runs_as_strips(int dim, int vocab);   // q4_kernels.hip: classifier_with_final_norm is ONE strips launch for this shape on the current device and stream
 int cls_strip_prepare();    // q4_kernels.hip (gemv_strip_cls.h): the same for the classifier's strips kernel
 int down_strip_prepare();   // gemv_plain.hip (gemv_strip_down.h): LDS opt-in of the 13B down projection's strips kernel, outside any stream capture
 extern unsigned long long* g_dbg;   // profiling build: device buffer for time stamps (q4_set_debug_buffer)

@@ -511,6 +511,7 @@ int cls_strip_prepare() {
     if (!rc) prepared_device = dev;
     return rc;
 }
+bool classifier_runs_as_strips(int dim, int vocab) { return cls_strip_covers(dim, vocab, 1, dim, 1.0f); }
 // (the greedy sampler as this launch's epilogue was built and measured level in round 4: EXPERIMENTS.md #19)
 int classifier_with_final_norm(q4_half* logits, q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab) {
     if (cls_strip_covers(dim, vocab, 1, dim, 1.0f)) return launch_cls_strip(logits, x, rms_w, wcls, dim, vocab);

@@ -2,6 +2,7 @@
 #pragma once
 #include <map>
 #include "q4_internal.h"
+#include "cls_screen.h"
 
 namespace q4 {
 
@@ -30,6 +31,7 @@ struct Model {
     int* lp_ids = nullptr;          // [seq_len][K]
     float* lp_top = nullptr;        // [seq_len][K]
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
+    ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
 using Models = std::map<const RunState*, Model>;
@@ -44,7 +46,8 @@ static inline Model* model_of(const RunState* s) {
 
 // q4_network.hip. have_embedding: the preceding launch of the stream (the greedy sampler of the previous step, inside one graph replay) has left
 // the token's embedding row in s->x already
-int run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding);
+// screened: the classifier as screen + refine (cls_screen.h): RunState::logits then holds the exact logits of the rows that can be the largest and -inf elsewhere
+int run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding, bool screened = false);
 // q4_step.hip
 void drop_graphs_of(const RunState* s);   // the model's captured graphs, after the launch stream has drained
 void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the log-probability launch only

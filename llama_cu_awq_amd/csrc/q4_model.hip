@@ -247,6 +247,8 @@ static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
         (void)hipGetLastError();    // no hand-off words: the network runs its five-launch sequence
         m.sync = nullptr;
     }
+    // the greedy steps' screening copy of wcls, where the classifier runs as strips; without it (another shape, no memory left) the model decodes as before
+    if (cls_screen_shape(p->dim, p->vocab_size) && cls_screen_build(&m.screen, w->wcls, p->dim, p->vocab_size) != Q4_OK) m.screen = ClsScreen{};
     return Q4_OK;
 }
 
@@ -272,8 +274,9 @@ const char* q4_last_error(void) { return g_last_error; }
 int q4_set_device(int device) {
     Q4_HIP(hipSetDevice(device));
     // LDS opt-ins of kernels the public matmuls may launch: attribute calls, made before any stream capture can begin
-    const int rc = down_strip_prepare();
-    return rc ? rc : cls_strip_prepare();
+    int rc = down_strip_prepare();
+    if (!rc) rc = cls_strip_prepare();
+    return rc ? rc : cls_screen_prepare();
 }
 int q4_stream_create(q4_stream_t* out) {
     hipStream_t s;
@@ -387,7 +390,7 @@ void q4_free_transformer(Transformer* t) {                                      
     if (it != models().end()) {
         const Model& m = it->second;
         hipDeviceSynchronize();
-        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync, m.lp_ring})
+        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);
         models().erase(it);

@@ -68,7 +68,7 @@ static NetForms net_forms(const Config* p, const RunState* s, const Model* m, in
 extern "C" int q4_run_llama_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin) {
     return run_network(pPos, p, s, w, seq_len_bin, false);
 }
-int q4::run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding) {
+int q4::run_network(const int* pPos, const Config* p, RunState* s, const TransformerWeights* w, int seq_len_bin, bool have_embedding, bool screened) {
     q4_half* x = s->x;
     const int dim = p->dim;
     const int hidden_dim = p->hidden_dim;
@@ -157,7 +157,10 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
         Q4_UNLESS(16, q4_matmul_q4(s->x, s->hb, &L->wq_down, hidden_dim, dim, 1, -1, nullptr));        // :332
         Q4_LAYER_DUMP(1);
     }
-    if (g_fusion >= 1) {      // one launch where the classifier runs as strips (gemv_strip_cls.h): the final norm inside its x staging
+    if (screened) {           // a greedy generating step whose logits nobody reads (q4_step.hip decides): int8 screen + exact refinement of the candidate rows
+        if (!m || !m->screen.base) return Q4_ERR_ARG;
+        Q4_UNLESS(32, launch_cls_screen(m->screen, s->logits, x, w->rms_final_weight, w->wcls));
+    } else if (g_fusion >= 1) {      // one launch where the classifier runs as strips (gemv_strip_cls.h): the final norm inside its x staging
         Q4_UNLESS(32, classifier_with_final_norm(s->logits, x, w->rms_final_weight, w->wcls, p->dim, p->vocab_size));
     } else {
         Q4_UNLESS(32, q4_rmsnorm(x, x, w->rms_final_weight, dim));                                         // :336

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <stddef.h>
 #include "q4_model.h"
 
 namespace q4 {
@@ -39,7 +40,7 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
 }
 
 // graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
-// bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in), bit5 = the classifier as screen + refine (cls_screen.h). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -49,8 +50,8 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][32];
-    bool captured[Q4_MAX_GRAPHS][32];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][64];
+    bool captured[Q4_MAX_GRAPHS][64];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
@@ -63,7 +64,7 @@ static int g_graph_captures = 0;
 static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 32; v++)
+        for (int v = 0; v < 64; v++)
             if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
@@ -95,6 +96,14 @@ static GraphSet& graph_set_of(const RunState* owner, const Config* p, const Tran
     return *pick;
 }
 
+// A step runs its classifier as screen + refine only when nothing but the greedy token is taken from its logits: a greedy generating step of a token
+// loop (may_screen: the public per-step entry points never pass it -- their callers read RunState::logits), no fp32 copy, no log-probability records, a
+// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on.
+static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits) {
+    return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
+           cls_screen_shape(m->screen.n, m->screen.d);
+}
+
 }  // namespace q4
 
 using namespace q4;
@@ -114,6 +123,34 @@ void q4_set_fusion(int level) {
         for (auto& kv : models()) (void)clear_handoff_state(kv.first, &kv.second, false);   // no stale counters / granules across a change of launch sequence
 }
 int q4_get_fusion(void) { return g_fusion; }
+
+// The greedy steps' classifier as an int8 screen + exact refinement (cls_screen.h). 1 (default): on, for models that have a screening copy; 0: off.
+void q4_set_greedy_screen(int on) {
+    g_greedy_screen = on ? 1 : 0;
+    q4_reset_graphs();
+}
+int q4_get_greedy_screen(void) { return g_greedy_screen; }
+int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* total, long long* steps) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    unsigned c[SCREEN_WORDS] = {};
+    if (m->screen.base) {
+        Q4_HIP(hipStreamSynchronize(g_stream));
+        Q4_HIP(hipMemcpy(c, m->screen.count, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    unsigned long long wide[SCREEN_WORDS / 2];
+    memcpy(wide, c, sizeof(c));
+    if (c[SCREEN_OPEN]) {     // the last screened step's tally is closed by the next one's screen launch: close it here
+        c[SCREEN_LAST] = c[SCREEN_CUR];
+        if (c[SCREEN_CUR] > c[SCREEN_MAX]) c[SCREEN_MAX] = c[SCREEN_CUR];
+        wide[SCREEN_TOTAL / 2] += c[SCREEN_CUR];
+    }
+    if (last) *last = (int)c[SCREEN_LAST];
+    if (max) *max = (int)c[SCREEN_MAX];
+    if (total) *total = (long long)wide[SCREEN_TOTAL / 2];
+    if (steps) *steps = (long long)wide[SCREEN_STEPS / 2];
+    return Q4_OK;
+}
 
 void q4_reset_graphs(void) {
     for (GraphSet& gs : g_sets) drop_graphs(gs, 0);
@@ -211,6 +248,8 @@ int q4_sample(Sampler* sampler, RunState* s, int gen_token) { return sample_impl
 
 // ---------------------------------------------------------------------------------------------------
 // run_transformer, llama2_q4.cu:346-395
+__attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
+                                                                         int copyLogits, Sampler* pSampler, int may_screen);
 int q4_run_transformer(int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
                        Sampler* pSampler) {
     return q4_run_transformer_at(s->shared_data->pos, gen_token, p, s, w, copyLogits, pSampler);   // :354
@@ -240,6 +279,11 @@ int q4_run_transformer_at(int pos, int gen_token, const Config* p, RunState* s, 
 // nsteps == 1 or Q4_MULTI_STEPS are captured; the caller keeps a group inside one sequence-length bin (q4_steps_that_fit).
 int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
                              int copyLogits, Sampler* pSampler) {
+    return run_transformer_steps_screenable(pos, nsteps, gen_token, p, s, w, copyLogits, pSampler, 0);
+}
+// ... for the token loops of this library (here and in q4_host.cpp; not exported): may_screen says that nobody reads the group's logits
+__attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
+                                                                         int copyLogits, Sampler* pSampler, int may_screen) {
     const int seq_len = pos + nsteps;                                              // :354 (of the group's last step)
     const bool greedy = sampler_is_greedy(pSampler, gen_token);
     int seq_len_bin;
@@ -247,13 +291,14 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
     if (nsteps != 1 && (nsteps != g_multi_steps || g_use_graphs != 1)) return Q4_ERR_ARG;
     if (pos < 0 || pos + nsteps > p->seq_len) return Q4_ERR_ARG;
     const Model* lpm = model_of(s);                                                // q4_set_logprobs: a record launch between the classifier and the sampler
+    const bool screened = step_screens(lpm, may_screen != 0, gen_token, greedy, copyLogits);
     if (lpm && lpm->logprobs_k < 0) lpm = nullptr;
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
-        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0);
+        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0) | (screened ? 32 : 0);
         CoinRing* ring = nullptr;
         if (!greedy) {     // the sampling kernel is part of the graph: its temperature, top-p, scratch and coin ring are baked in
             Q4_TRY(coin_ring_for(pSampler, p->seq_len, &ring));
@@ -272,7 +317,7 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
             // the reference's 1:1 launch list)
             const bool feed = gen_token && nsteps > 1 && g_fusion >= 1;
             for (int i = 0; i < nsteps && !rc; i++) {
-                rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0);
+                rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0, screened);
                 if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
                 if (!rc && lpm) rc = launch_logprobs_step(lpm, p, s, gen_token, greedy);   // (before the sampler: it advances the position and overwrites the logits)
                 if (!rc && greedy) {
@@ -303,7 +348,7 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
         Q4_HIP(hipGraphLaunch(gs.exec[graphIndex][variant], g_stream));          // :372 (:384: the sampler launch is in the graph)
         return Q4_OK;
     }
-    Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false));   // :374
+    Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false, screened));   // :374
     if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
     if (lpm) Q4_TRY(launch_logprobs_step(lpm, p, s, gen_token, greedy));
     Q4_TRY(sample_impl(pSampler, s, gen_token, true));
@@ -334,8 +379,16 @@ int q4_steps_that_fit(int pos, int num_prompt_tokens, int steps, const Config* p
     (void)sampler;     // sampled steps take their coins from a device ring by position: they go out k per replay too
     int b0, b1;
     if (graph_bin(pos + 1, p, &b0) != graph_bin(pos + k, p, &b1)) return 1;
+    // A model that screens its greedy steps: the last step a generation queues goes out alone, so that it can run the full classifier and leave
+    // RunState::logits whole (group_may_screen below). The Config of a Transformer leads to its record; any other Config finds none and changes nothing.
+    if (pos + k == steps && gen0 && sampler && sampler->temperature == 0.0f) {
+        const RunState* rs = reinterpret_cast<const RunState*>(reinterpret_cast<const char*>(p) - offsetof(Transformer, config) + offsetof(Transformer, state));
+        if (step_screens(model_of(rs), true, 1, true, 0)) return 1;
+    }
     return k;
 }
+// what a token loop passes as may_screen for the group of k steps it queues at pos: every step but the generation's last
+static int group_may_screen(int pos, int k, int steps) { return pos + k < steps ? 1 : 0; }
 // The in-launch hand-offs of fusion levels 3 and 4 (attention -> o-proj, layer_attn.h; the FFN pair launch, gemv_ffn_pair.h) spin for a bounded time; a spin that ran out
 // sets the model's error word: everything computed since is invalid. Synchronises the stream and reports it ONCE: the word,
 // the counters and the granules are cleared (the epoch keeps counting: tags never repeat), and the library drops to fusion
@@ -406,7 +459,7 @@ double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_token
                 const int k = q4_steps_that_fit(pos, num_prompt_tokens, steps, &t->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                if (q4_run_transformer_steps(pos, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler)) return -1.0;
+                if (run_transformer_steps_screenable(pos, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos, k, steps))) return -1.0;
                 queued = pos + k;
             }
             if (q4_wait_pos(&t->state, pos)) return -1.0;                              // :468
