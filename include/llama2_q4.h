@@ -333,6 +333,59 @@ unsigned int random_u32(unsigned long long* state);
 float random_f32(unsigned long long* state);
 int q4_sample(Sampler* sampler, RunState* s, int gen_token);
 
+/* Not in the reference: the sampling controls of a completion API beside temperature and top-p -- top-k, min-p, repetition / presence / frequency
+ * penalties, a logit bias -- applied on the device inside the decode step (csrc/q4_logit_process.hip), so that a host which wants them keeps the
+ * multi-step graphs and the queued-ahead step. The Sampler struct keeps the reference's layout: the controls live beside it, keyed by its address;
+ * destroy_sampler / q4_sampler_delete free them. Off by default, and then every launch list, every captured graph and every bit is what it is without
+ * these calls.
+ * With controls on, every GENERATING step (gen_token != 0) that uses the sampler -- greedy or sampled, eager or in any graph variant, one or
+ * Q4_MULTI_STEPS per replay -- runs one one-block launch behind the log-probability record launch and in front of the argmax / sampler. It rewrites
+ * RunState::logits in place; for token i with half logit l, v = float(l), every operation one IEEE fp32 operation:
+ *   1. bias: i in the bias list: v = v + b_i.
+ *   2. penalties: W = the ring entries tokens[max(0, pos + 1 - penalty_last_n) .. pos], pos the step's position (prompt tokens count; entries outside
+ *      the vocabulary do not), read only while a penalty is not neutral; c_i = occurrences of i in W. c_i > 0: v = v > 0 ? v / repeat_penalty :
+ *      v * repeat_penalty, then v = v - (float(c_i) * frequency_penalty + presence_penalty). The window is read from the ring by position in every step:
+ *      q4_reset_sequence, rewinds and q4_run_transformer_at need no bookkeeping.
+ *   3. a finite v is clamped to +-65504 and rounded to half (nearest even); an infinity stays; a NaN result is the quiet NaN 0x7E00. Only the entries
+ *      touched by 1 and 2 are rewritten.
+ *   4. top_k (0: off): in the order (value descending, index ascending) -- -0 equals +0, a NaN ranks last, ties across rank k are resolved by index --
+ *      the first top_k entries stay, every other becomes -inf.
+ *   5. min_p (0: off): with m the largest processed logit, entry i stays iff float(l_i) - float(m) >= logf(min_p), else it becomes -inf. This is min-p
+ *      on the PROCESSED logits AT TEMPERATURE 1: it does not depend on the sampler's temperature.
+ * Log-probability records and copyLogits are taken in front of the launch: they keep describing the model's own raw distribution (the token_logprob
+ * of a greedy step is then that of the token the step chose, which need not be entry 0 of the raw order: it is looked up behind the argmax, as on a
+ * sampled step). After a greedy
+ * generating step RunState::logits holds the PROCESSED logits (after a sampled one the sampler's probabilities, as always). Prompt steps launch nothing.
+ * Greedy steps are not screened (q4_set_greedy_screen) while controls are on. q4_sample itself is unchanged: a host with its own per-step loop calls
+ * q4_process_logits in front of it.
+ * The values may change between steps: the next step sees them, no captured graph is replayed with stale ones (graphs are captured again only when the
+ * controls go from off to on or back). */
+enum { Q4_MAX_PENALTY_WINDOW = 1024, Q4_MAX_LOGIT_BIAS = 256 };
+typedef struct {
+    int top_k;                 /* 0: off */
+    float min_p;               /* [0, 1), 0: off */
+    float repeat_penalty;      /* > 0, 1: off */
+    float presence_penalty;    /* 0: off */
+    float frequency_penalty;   /* 0: off */
+    int penalty_last_n;        /* [0, Q4_MAX_PENALTY_WINDOW] */
+} q4_sampling_controls;
+/* NULL or all-neutral {0, 0, 1, 0, 0, any}: off. Q4_ERR_ARG (nothing changes, the GPU is not touched): top_k < 0, min_p outside [0, 1), repeat_penalty
+ * <= 0 or not finite, a presence or frequency penalty that is not finite, penalty_last_n outside [0, Q4_MAX_PENALTY_WINDOW]. A top_k or a bias id beyond
+ * the vocabulary is found by the first step that uses the sampler with a model: that step returns Q4_ERR_ARG. */
+int q4_sampler_set_controls(Sampler* sampler, const q4_sampling_controls* controls);
+int q4_sampler_get_controls(const Sampler* sampler, q4_sampling_controls* out);
+/* ids / bias: host arrays of n <= Q4_MAX_LOGIT_BIAS entries, copied; n = 0 clears. Q4_ERR_ARG: an id that is negative or listed twice, a bias that is NaN,
+ * +inf or above 65504 in magnitude (-inf is allowed: it bans the token). */
+int q4_sampler_set_logit_bias(Sampler* sampler, const int* ids, const float* bias, int n);
+/* "top_k=40,min_p=0.05,repeat_penalty=1.1,last_n=64,presence=0,frequency=0": any subset of the keys in any order; a key left out keeps its neutral
+ * value (last_n: 64). Q4_ERR_ARG and *out untouched: an unknown key, a malformed number, a value q4_sampler_set_controls refuses. */
+int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out);
+/* Op-level form of the launch: logits [n] halves (16-byte aligned), tokens (the ring) and pPos (one int: the position) device-visible -- both may be
+ * NULL: no window --, bias_ids / bias host arrays. Rewrites logits in place on the q4 stream. top_k > n, a bias id >= n or anything the setters refuse:
+ * Q4_ERR_ARG without touching the GPU. */
+int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias,
+                      const int* tokens, const int* pPos);
+
 /* build_transformer(Transformer*, char* checkpoint_path, bool perplexity) llama2_q4.cu:408-426 (prints the
  * same "Model params" / "Loading Weights... done!" lines unless quiet), free_transformer :428-432 */
 int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perplexity);

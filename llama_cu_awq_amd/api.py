@@ -18,6 +18,8 @@ MAX_SEQ_LEN = 128 * 1024
 KV_FP16, KV_FP8 = 0, 1          # q4_set_kv_format
 KV_FORMATS = {"fp16": KV_FP16, "fp8": KV_FP8}
 MAX_TOP_LOGPROBS = 20           # Q4_MAX_TOP_LOGPROBS
+MAX_PENALTY_WINDOW = 1024       # Q4_MAX_PENALTY_WINDOW
+MAX_LOGIT_BIAS = 256            # Q4_MAX_LOGIT_BIAS
 
 
 class Config(C.Structure):
@@ -51,6 +53,18 @@ class CliArgs(C.Structure):
                 ("seed_from_time", C.c_int)]
 
 
+class SamplingControls(C.Structure):
+    """q4_sampling_controls; the defaults are the neutral values (everything off)"""
+    _fields_ = [("top_k", C.c_int), ("min_p", C.c_float), ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("penalty_last_n", C.c_int)]
+
+    def __init__(self, top_k=0, min_p=0.0, repeat_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, penalty_last_n=64):
+        super().__init__(int(top_k), float(min_p), float(repeat_penalty), float(presence_penalty), float(frequency_penalty), int(penalty_last_n))
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/llama2_q4.h declares (tests/test_abi.py checks the .so exports all of them)
 SYMBOLS = [
     "q4_status_string", "q4_last_error", "q4_set_device", "q4_stream_create", "q4_stream_create_masked", "q4_stream_destroy", "q4_set_stream",
@@ -68,6 +82,7 @@ SYMBOLS = [
     "q4_bench_kernel", "q4_bench_kernel_graph", "q4_bench_in_network", "q4_device_info",
     "q4_logprob_topk", "q4_set_logprobs", "q4_get_logprobs_k", "q4_get_logprobs", "q4_score_ids",
     "q4_set_greedy_screen", "q4_get_greedy_screen", "q4_screen_candidates", "q4_greedy_screen_op",
+    "q4_sampler_set_controls", "q4_sampler_get_controls", "q4_sampler_set_logit_bias", "q4_parse_sampling_controls", "q4_process_logits",
 ]
 
 _lib = None
@@ -203,6 +218,12 @@ def lib():
         L.q4_set_greedy_screen.restype = None
         L.q4_screen_candidates.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         L.q4_greedy_screen_op.argtypes = [vp, vp, i, i, vp, C.POINTER(i), vp, vp, vp, C.POINTER(i)]
+    if hasattr(L, "q4_sampler_set_controls"):      # (older builds under tools/ab.py do not have it)
+        L.q4_sampler_set_controls.argtypes = [vp, C.POINTER(SamplingControls)]
+        L.q4_sampler_get_controls.argtypes = [vp, C.POINTER(SamplingControls)]
+        L.q4_sampler_set_logit_bias.argtypes = [vp, vp, vp, i]
+        L.q4_parse_sampling_controls.argtypes = [C.c_char_p, C.POINTER(SamplingControls)]
+        L.q4_process_logits.argtypes = [vp, i, C.POINTER(SamplingControls), vp, vp, i, vp, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -314,6 +335,28 @@ def logprob_topk(logits, n, top_k, target, lse, target_logprob, top_ids=None, to
                                 top_ids.ptr if top_ids else None, top_logprobs.ptr if top_logprobs else None))
 
 
+def _bias_arrays(logit_bias):
+    """{id: bias} (or None) -> (ids int32, bias float32)"""
+    items = sorted((logit_bias or {}).items())
+    return np.array([k for k, _ in items], dtype=np.int32), np.array([v for _, v in items], dtype=np.float32)
+
+
+def parse_sampling_controls(text):
+    """q4_parse_sampling_controls: "top_k=40,min_p=0.05,repeat_penalty=1.1,last_n=64,presence=0,frequency=0" -> SamplingControls"""
+    c = SamplingControls()
+    check(lib().q4_parse_sampling_controls(text.encode(), C.byref(c)))
+    return c
+
+
+def process_logits(logits, n, controls=None, logit_bias=None, tokens=None, pos=None, **kw):
+    """q4_process_logits over DevBufs: rewrites `logits` (n halves) in place -- bias, penalties over the window of the ring `tokens` (int32) that ends
+    at the position in `pos` (one int32), top-k, min-p. controls: a SamplingControls, or its fields as keywords; logit_bias: {id: bias}."""
+    c = controls if controls is not None else SamplingControls(**kw)
+    ids, bias = _bias_arrays(logit_bias)
+    check(lib().q4_process_logits(logits.ptr, n, C.byref(c), ids.ctypes.data, bias.ctypes.data, ids.shape[0], tokens.ptr if tokens else None,
+                                  pos.ptr if pos else None))
+
+
 def greedy_screen_op(x, w, n, d, rms_w=None):
     """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
     tok, cand = C.c_int(), C.c_int()
@@ -344,7 +387,8 @@ def device_info():
 class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
-    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None):
+    def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
+                 logit_bias=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -373,12 +417,16 @@ class Transformer:
         self.sampler = L.q4_sampler_new(self.config.vocab_size, temperature, topp, seed)
         if not self.sampler:
             raise Q4Error("build_sampler failed")
-        if logprobs is not None:
-            try:
+        try:
+            if logprobs is not None:
                 self.set_logprobs(logprobs)
-            except Exception:
-                self.close()
-                raise
+            if sampling is not None:
+                self.set_sampling(**sampling)
+            if logit_bias is not None:
+                self.set_logit_bias(logit_bias)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         L = lib()
@@ -451,6 +499,21 @@ class Transformer:
         total, steps = C.c_longlong(), C.c_longlong()
         check(lib().q4_screen_candidates(self.h, C.byref(last), C.byref(mx), C.byref(total), C.byref(steps)))
         return last.value, mx.value, total.value, steps.value
+
+    def set_sampling(self, **kw):
+        """Sampling controls inside the decode step (q4_sampler_set_controls): top_k, min_p, repeat_penalty, presence_penalty, frequency_penalty,
+        penalty_last_n; no keyword: off. They rewrite the logits of every generating step in front of the argmax / sampler."""
+        check(lib().q4_sampler_set_controls(self.sampler, C.byref(SamplingControls(**kw)) if kw else None))
+
+    def sampling(self):
+        c = SamplingControls()
+        check(lib().q4_sampler_get_controls(self.sampler, C.byref(c)))
+        return c.as_dict()
+
+    def set_logit_bias(self, logit_bias):
+        """{token id: bias} added to the logits of every generating step (-inf bans a token); None or {}: cleared"""
+        ids, bias = _bias_arrays(logit_bias)
+        check(lib().q4_sampler_set_logit_bias(self.sampler, ids.ctypes.data, bias.ctypes.data, ids.shape[0]))
 
     def set_logprobs(self, top_k):
         """Per-token log-probability records inside the decode step: None / -1 off, 0 the chosen or target token only, K <= 20 also the top K."""

@@ -445,6 +445,13 @@ int q4_main(int argc, char** argv) {
     const char* kv = getenv("Q4_KV_CACHE");
     if (kv && strcmp(kv, "fp8") == 0) q4_set_kv_format(Q4_KV_FP8);
     else if (kv && *kv && strcmp(kv, "fp16") != 0) { fprintf(stderr, "Q4_KV_CACHE: unknown format '%s' (fp16 or fp8)\n", kv); exit(EXIT_FAILURE); }
+    // ... and so do the sampling controls (q4_parse_sampling_controls): Q4_SAMPLING="top_k=40,min_p=0.05,repeat_penalty=1.1,last_n=64"
+    const char* sampling = getenv("Q4_SAMPLING");
+    q4_sampling_controls controls;
+    if (sampling && *sampling && q4_parse_sampling_controls(sampling, &controls)) {
+        fprintf(stderr, "Q4_SAMPLING: cannot use '%s' (keys: top_k, min_p, repeat_penalty, last_n, presence, frequency; e.g. top_k=40,repeat_penalty=1.1)\n", sampling);
+        exit(EXIT_FAILURE);
+    }
 
     Transformer transformer;
     int rc = q4_build_transformer(&transformer, a.checkpoint_path, a.perplexity);
@@ -456,6 +463,7 @@ int q4_main(int argc, char** argv) {
     if (!tokenizer) exit(EXIT_FAILURE);
     Sampler sampler;
     die_on(build_sampler(&sampler, transformer.config.vocab_size, a.temperature, a.topp, a.rng_seed));
+    if (sampling && *sampling) die_on(q4_sampler_set_controls(&sampler, &controls));
 
     q4_stream_t stream;
     die_on(q4_stream_create(&stream));                                             // :700

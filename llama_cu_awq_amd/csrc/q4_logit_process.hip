@@ -1,0 +1,472 @@
+// q4_logit_process.hip -- the sampling controls of a completion API beside temperature and top-p: logit bias, repetition / presence / frequency penalties,
+// top-k and min-p, as ONE launch that rewrites the step's fp16 logits in place in front of the argmax or the sampler. Not in the reference.
+// ONE 1024-thread block, the partition of q4_logprobs.hip: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last whole chunk, one tail
+// element; up to 32 x 1024 logits stay in registers, larger vocabularies are read again from L2 in every pass.
+//   1. bias, 2. penalties, 3. clamp and round -- on the TOUCHED entries only (at most 256 bias ids and 1024 window tokens):
+//      v = float(l); v += b_i; with c_i > 0 occurrences of i in the window: v = v > 0 ? v / r : v * r, v -= (float(c_i) * frequency + presence);
+//      a finite v is clamped to +-65504 and rounded to half (RNE), an infinity stays, a NaN result is the quiet NaN 0x7E00. Every operation is one IEEE
+//      fp32 operation (no contraction: numpy float32 reproduces the bits).
+//      The window is the ring entries tokens[max(0, pos + 1 - last_n) .. pos], pos = *pPos before the sampler advances it: prompt tokens count, entries
+//      outside [0, n) do not. It is read from the ring by position in every launch -- no state, nothing to reset or rewind -- and only when a penalty is
+//      not neutral. The ring is pinned host memory: thread t requests entry t first; the bias list is staged while the request is in flight. The
+//      occurrences are counted in LDS: every thread compares its entry with all the others (last_n / 4 broadcast reads of 16 bytes), the first occurrence
+//      of a token rewrites its logit, a bias id that is also in the window hands its bias to that thread through LDS.
+//   4. top-k on the 16-bit monotone key of q4_logprobs.hip (-0 equals +0, NaN ranks last), order (key descending, index ascending): T, the k-th largest
+//      key, by 16 steps of a binary search whose count is one block-wide sum each; with ties that straddle rank k the entries equal to T keep their place
+//      by index (one block-wide prefix sum per row of 8192 logits, until the k are full). Everything behind rank k becomes -inf.
+//   5. min-p on the PROCESSED logits at temperature 1 (independent of the sampler's temperature): with m the largest of them, entry i stays iff
+//      float(l_i) - float(m) >= logf(min_p) (the host's logf, a kernel argument); else -inf.
+// No atomics, no arrival order: the same input gives the same bytes on every launch. A NaN or an out-of-range token never faults: the window and the
+// bias ids are checked against [0, n) before they index anything.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include <map>
+#include "q4_device.h"
+#include "q4_model.h"
+#pragma clang fp contract(off)
+using namespace q4;
+
+namespace {
+
+constexpr int PL_T = 1024, PL_W = 16, PL_Q = 4;        // threads, waves, register-resident 16-byte chunks per thread
+constexpr unsigned PL_NO_BIAS = 0xFFFFFFFFu;           // (a NaN pattern: the setters refuse a NaN bias)
+
+// what the kernel reads: one small device block per Sampler (or the op-level launcher's), rewritten in stream order when the host changes the controls,
+// so a captured graph never holds a value of them -- only the block's address
+struct LogitParams {
+    int top_k;
+    int min_p_on;
+    float log_min_p;
+    float repeat, presence, frequency;
+    int last_n;              // 0: no penalty is on
+    int n_bias;
+    int bias_ids[Q4_MAX_LOGIT_BIAS];
+    float bias[Q4_MAX_LOGIT_BIAS];
+};
+
+__device__ __forceinline__ unsigned half_key(unsigned h) {      // q4_logprobs.hip: larger value <=> larger key, -0 -> +0, NaN -> 0
+    if (h == 0x8000u) h = 0u;
+    if ((h & 0x7FFFu) > 0x7C00u) return 0u;
+    return (h & 0x8000u) ? (~h & 0xFFFFu) : (h | 0x8000u);
+}
+__device__ __forceinline__ unsigned key_half(unsigned key) { return (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu); }   // (key 0 -> a NaN)
+__device__ __forceinline__ unsigned half_of(const u32x4& q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu; }
+__device__ __forceinline__ u32x4 chunk_keys(const u32x4& q) {
+    u32x4 k;
+#pragma unroll
+    for (int d = 0; d < 4; d++) k[d] = half_key(q[d] & 0xFFFFu) | (half_key(q[d] >> 16) << 16);
+    return k;
+}
+__device__ __forceinline__ int count_ge(const u32x4& k, unsigned mid) {
+    int c = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) c += half_of(k, e) >= mid ? 1 : 0;
+    return c;
+}
+__device__ __forceinline__ int count_eq(const u32x4& k, unsigned T) {
+    int c = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) c += half_of(k, e) == T ? 1 : 0;
+    return c;
+}
+
+// step 3: a finite value clamped to the half range and rounded (RNE); an infinity stays; a NaN is 0x7E00
+__device__ __forceinline__ q4_half finish(float v) {
+    if (v != v) return (q4_half)0x7E00u;
+    if (fabsf(v) != INFINITY) v = fminf(fmaxf(v, -65504.0f), 65504.0f);
+    return (q4_half)f2h(v);
+}
+
+// Block-wide sum / maximum / exclusive prefix sum of one int per thread. `use` counts the calls: two LDS rows take turns, so ONE barrier per call is
+// enough (a row is written again only two calls later, behind the barrier of the call in between, which every thread passes after its reads).
+__device__ __forceinline__ int block_sum(int v, int (*red)[PL_W], int& use) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    int* row = red[use++ & 1];
+    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < PL_W; w++) s += row[w];
+    return s;
+}
+__device__ __forceinline__ int block_max(int v, int (*red)[PL_W], int& use) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
+    int* row = red[use++ & 1];
+    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = row[0];
+#pragma unroll
+    for (int w = 1; w < PL_W; w++) s = max(s, row[w]);
+    return s;
+}
+__device__ __forceinline__ int block_scan(int v, int (*red)[PL_W], int& use, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(x, off);
+        if (lane >= off) x += o;
+    }
+    int* row = red[use++ & 1];
+    if (lane == 63) row[wave] = x;
+    __syncthreads();
+    int before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < PL_W; w++) {
+        const int r = row[w];
+        tot += r;
+        before += w < wave ? r : 0;
+    }
+    total = tot;
+    return before + x - v;
+}
+
+// REG: n <= 32 x 1024, the thread's chunks and their keys stay in registers. tokens / pPos null: no window.
+template <bool REG>
+__global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, int n, const LogitParams* __restrict__ prm, const int* tokens,
+                                                             const int* pPos) {
+    __shared__ __attribute__((aligned(16))) int s_win[PL_T];
+    __shared__ unsigned s_wbias[PL_T];
+    __shared__ int red[2][PL_W];
+    const int tid = threadIdx.x;
+    const int top_k = prm->top_k, min_p_on = prm->min_p_on, n_bias = min(max(prm->n_bias, 0), (int)Q4_MAX_LOGIT_BIAS);
+    const int last_n = min(max(prm->last_n, 0), (int)Q4_MAX_PENALTY_WINDOW);
+    const float repeat = prm->repeat, presence = prm->presence, frequency = prm->frequency, log_min_p = prm->log_min_p;
+
+    // ---- steps 1 - 3. The window entry of this thread is requested first (pinned host memory) and used last
+    int L = 0, w = -1;
+    if (last_n > 0 && tokens != nullptr && pPos != nullptr) {
+        const int pos = *pPos;
+        if (pos >= 0 && pos < Q4_MAX_SEQ_LEN) {
+            const int start = max(0, pos + 1 - last_n);
+            L = pos + 1 - start;                               // (block-uniform, <= 1024)
+            if (tid < L) w = tokens[start + tid];
+        }
+    }
+    if (L > 0 || n_bias > 0) {                                 // (block-uniform)
+        int bid = -1;
+        float bval = 0.f;
+        if (tid < n_bias) {
+            bid = prm->bias_ids[tid];
+            bval = prm->bias[tid];
+            if ((unsigned)bid >= (unsigned)n) bid = -1;
+        }
+        s_wbias[tid] = PL_NO_BIAS;
+        if ((unsigned)w >= (unsigned)n) w = -1;
+        s_win[tid] = w;                                        // (-1 from L on: it matches no token)
+        __syncthreads();
+        int cnt = 0, first = -1;
+        bool dup = false;
+        for (int s = 0; s < L; s += 4) {
+            const int4 x = *reinterpret_cast<const int4*>(&s_win[s]);
+            const int xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                cnt += xs[j] == w ? 1 : 0;
+                dup = dup || (xs[j] == w && s + j < tid);
+                if (xs[j] == bid && first < 0) first = s + j;
+            }
+        }
+        if (bid >= 0 && first >= 0) s_wbias[first] = __float_as_uint(bval);      // (ids are distinct: one writer per slot)
+        __syncthreads();
+        if (w >= 0 && !dup) {                                  // the first occurrence of a token in the window
+            float v = h2f(logits[w]);
+            const unsigned b = s_wbias[tid];
+            if (b != PL_NO_BIAS) v = v + __uint_as_float(b);
+            v = v > 0.f ? v / repeat : v * repeat;
+            const float pen = (float)cnt * frequency;
+            v = v - (pen + presence);
+            logits[w] = finish(v);
+        }
+        if (bid >= 0 && first < 0) logits[bid] = finish(h2f(logits[bid]) + bval);   // a bias id outside the window
+        __syncthreads();                                       // the block's own writes are visible to its loads below
+    }
+    if (top_k <= 0 && !min_p_on) return;                      // (block-uniform)
+
+    // ---- steps 4 and 5
+    const int n8 = n >> 3, nq = REG ? PL_Q : (n8 + PL_T - 1) / PL_T;
+    const int tail = n8 * 8 + tid;
+    u32x4* lv = reinterpret_cast<u32x4*>(logits);
+    u32x4 pq[PL_Q], kk[PL_Q];
+    if (REG) {
+#pragma unroll
+        for (int kq = 0; kq < PL_Q; kq++) {
+            const int u = tid + kq * PL_T;
+            pq[kq] = u < n8 ? lv[u] : (u32x4){0u, 0u, 0u, 0u};
+            kk[kq] = u < n8 ? chunk_keys(pq[kq]) : (u32x4){0u, 0u, 0u, 0u};      // (key 0 is below every threshold the search tries)
+        }
+    }
+    const unsigned th = tail < n ? (unsigned)logits[tail] : 0u;
+    const unsigned tkey = tail < n ? half_key(th) : 0u;
+    int use = 0;
+
+    // T = the k-th largest key: the largest T with count(key >= T) >= k. lo always has such a count (c_lo), hi never (c_hi)
+    const int keff = top_k > 0 ? min(top_k, n) : n;
+    int lo = 0, hi = 65536, c_lo = n, c_hi = 0;
+    if (keff < n) {
+        for (int it = 0; it < 16; it++) {
+            const unsigned mid = (unsigned)(lo + hi) >> 1;
+            int c = tkey >= mid ? 1 : 0;
+#pragma unroll 4
+            for (int kq = 0; kq < (REG ? PL_Q : nq); kq++) {
+                const int u = tid + kq * PL_T;
+                if constexpr (REG) c += count_ge(kk[kq], mid);
+                else if (u < n8) c += count_ge(chunk_keys(lv[u]), mid);
+            }
+            c = block_sum(c, red, use);
+            if (c >= keff) { lo = (int)mid; c_lo = c; } else { hi = (int)mid; c_hi = c; }
+        }
+    }
+    const bool all = keff >= n;                                // every entry stays in step 4
+    const unsigned T = (unsigned)lo;
+    const int need = keff - c_hi;                              // entries equal to T that stay: the first `need` by index
+    const bool straddle = !all && c_lo - c_hi > need;
+
+    float m = 0.f;
+    if (min_p_on) {
+        int mk = (int)tkey;
+#pragma unroll 4
+        for (int kq = 0; kq < (REG ? PL_Q : nq); kq++) {
+            const int u = tid + kq * PL_T;
+            u32x4 k;
+            if constexpr (REG) k = kk[kq]; else k = u < n8 ? chunk_keys(lv[u]) : (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 8; e++) mk = max(mk, (int)half_of(k, e));
+        }
+        mk = block_max(mk, red, use);
+        m = h2f((uint16_t)key_half((unsigned)mk));
+    }
+
+    // the rewrite, row by row in index order (a row: one chunk per thread, 8192 logits; the tail elements last)
+    int kept_eq = 0;                                           // entries equal to T in the rows so far (block-uniform; counted only while ties straddle)
+    for (int kq = 0; kq <= nq; kq++) {
+        const bool is_tail = kq == nq;
+        const int u = tid + kq * PL_T;
+        const bool have = is_tail ? tail < n : u < n8;
+        u32x4 q = {0u, 0u, 0u, 0u}, k = {0u, 0u, 0u, 0u};
+        if (is_tail) { q[0] = th; k[0] = tkey; }
+        else if (REG) {
+#pragma unroll
+            for (int j = 0; j < PL_Q; j++) if (j == kq) { q = pq[j]; k = kk[j]; }
+        } else if (have) { q = lv[u]; k = chunk_keys(q); }
+        const int ne = is_tail ? 1 : 8;
+        int base = need;                                       // ties no longer straddle, or the k are full: the rest of the equal entries go
+        if (straddle && kept_eq < need) {                      // (block-uniform)
+            int mine = 0;
+            if (have) mine = is_tail ? (tkey == T ? 1 : 0) : count_eq(k, T);
+            int total;
+            base = kept_eq + block_scan(mine, red, use, total);
+            kept_eq += total;
+        }
+        if (!have) continue;
+        u32x4 o = q;
+        bool changed = false;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            if (e < ne) {
+                const unsigned h = half_of(q, e), key = half_of(k, e);
+                bool keep = all || key > T || (key == T && (!straddle || base++ < need));
+                if (keep && min_p_on) keep = h2f((uint16_t)h) - m >= log_min_p;
+                if (!keep && h != 0xFC00u) {
+                    o[e >> 1] = (o[e >> 1] & ~(0xFFFFu << ((e & 1) * 16))) | (0xFC00u << ((e & 1) * 16));
+                    changed = true;
+                }
+            }
+        }
+        if (changed) {
+            if (is_tail) logits[tail] = (q4_half)(o[0] & 0xFFFFu);
+            else lv[u] = o;
+        }
+    }
+}
+
+// ---- host side: validation, the per-Sampler records, the launchers ---------------------------------------------------------------------------------
+bool finite_f(float v) { return v == v && fabsf(v) != INFINITY; }
+
+bool controls_valid(const q4_sampling_controls* c) {
+    return c->top_k >= 0 && c->min_p >= 0.f && c->min_p < 1.f && finite_f(c->repeat_penalty) && c->repeat_penalty > 0.f && finite_f(c->presence_penalty) &&
+           finite_f(c->frequency_penalty) && c->penalty_last_n >= 0 && c->penalty_last_n <= Q4_MAX_PENALTY_WINDOW;
+}
+bool controls_neutral(const q4_sampling_controls* c) {
+    return c->top_k == 0 && c->min_p == 0.f && c->repeat_penalty == 1.f && c->presence_penalty == 0.f && c->frequency_penalty == 0.f;
+}
+// ids distinct and >= 0 (below `limit` where limit > 0); no NaN, no +inf, nothing above 65504 in magnitude except -inf (a ban)
+bool bias_valid(const int* ids, const float* bias, int n, int limit) {
+    if (n < 0 || n > Q4_MAX_LOGIT_BIAS || (n > 0 && (!ids || !bias))) return false;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || (limit > 0 && ids[i] >= limit)) return false;
+        if (bias[i] != bias[i] || bias[i] == INFINITY || (bias[i] != -INFINITY && fabsf(bias[i]) > 65504.0f)) return false;
+        for (int j = 0; j < i; j++)
+            if (ids[j] == ids[i]) return false;
+    }
+    return true;
+}
+void fill_params(LogitParams* P, const q4_sampling_controls* c, const int* ids, const float* bias, int n_bias) {
+    memset(P, 0, sizeof(*P));
+    P->top_k = c->top_k;
+    P->min_p_on = c->min_p > 0.f ? 1 : 0;
+    P->log_min_p = c->min_p > 0.f ? logf(c->min_p) : -INFINITY;
+    P->repeat = c->repeat_penalty; P->presence = c->presence_penalty; P->frequency = c->frequency_penalty;
+    const bool pen = c->repeat_penalty != 1.f || c->presence_penalty != 0.f || c->frequency_penalty != 0.f;
+    P->last_n = pen ? c->penalty_last_n : 0;
+    P->n_bias = n_bias;
+    for (int i = 0; i < n_bias; i++) { P->bias_ids[i] = ids[i]; P->bias[i] = bias[i]; }
+}
+
+const q4_sampling_controls NEUTRAL = {0, 0.f, 1.f, 0.f, 0.f, 0};
+
+// The Sampler struct is the reference's: the controls live beside it, keyed by its address (like the coin rings of q4_step.hip)
+struct Controls {
+    q4_sampling_controls c = NEUTRAL;
+    int n_bias = 0;
+    int ids[Q4_MAX_LOGIT_BIAS];
+    float bias[Q4_MAX_LOGIT_BIAS];
+    LogitParams host;                  // what the next upload sends (pageable: the copy call returns when it has been staged)
+    LogitParams* dev = nullptr;
+    bool dirty = true;                 // the device block is behind the host's values
+    int checked_vocab = -1;            // the vocabulary top_k and the bias ids were last checked against
+    bool on() const { return !controls_neutral(&c) || n_bias > 0; }
+};
+std::map<const Sampler*, Controls>& registry() {
+    static std::map<const Sampler*, Controls> r;
+    return r;
+}
+LogitParams* g_op_block = nullptr;     // q4_process_logits' own block
+
+int launch(q4_half* logits, int n, const LogitParams* dev, const int* tokens, const int* pPos) {
+    if (n <= PL_T * PL_Q * 8) Q4_LAUNCH(logit_process_kernel<true>, dim3(1), dim3(PL_T), 0, logits, n, dev, tokens, pPos);
+    else Q4_LAUNCH(logit_process_kernel<false>, dim3(1), dim3(PL_T), 0, logits, n, dev, tokens, pPos);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+
+}  // namespace
+
+namespace q4 {
+
+bool sampling_controls_on(const Sampler* sampler) {
+    if (!sampler || registry().empty()) return false;
+    auto it = registry().find(sampler);
+    return it != registry().end() && it->second.on();
+}
+const void* sampling_controls_block(const Sampler* sampler) {
+    auto it = registry().find(sampler);
+    return it == registry().end() ? nullptr : it->second.dev;
+}
+// in front of a step (outside any capture): the values against this model's vocabulary, the device block, the pending upload in stream order
+int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block) {
+    Controls& ctl = registry()[sampler];
+    if (ctl.checked_vocab != vocab) {
+        if (ctl.c.top_k > vocab || !bias_valid(ctl.ids, ctl.bias, ctl.n_bias, vocab)) {
+            snprintf(g_last_error, sizeof(g_last_error), "sampling controls: top_k or a logit bias id exceeds the vocabulary (%d)", vocab);
+            return Q4_ERR_ARG;
+        }
+        ctl.checked_vocab = vocab;
+    }
+    if (!ctl.dev) {
+        Q4_HIP(hipMalloc((void**)&ctl.dev, sizeof(LogitParams)));
+        ctl.dirty = true;
+    }
+    if (ctl.dirty) {
+        fill_params(&ctl.host, &ctl.c, ctl.ids, ctl.bias, ctl.n_bias);
+        Q4_HIP(hipMemcpyAsync(ctl.dev, &ctl.host, sizeof(LogitParams), hipMemcpyHostToDevice, g_stream));
+        ctl.dirty = false;
+    }
+    *block = ctl.dev;
+    return Q4_OK;
+}
+int launch_logit_process_step(const void* block, const Config* p, RunState* s) {
+    return launch(s->logits, p->vocab_size, (const LogitParams*)block, &(s->shared_data->tokens[0]), s->pos);
+}
+// destroy_sampler: the caller has dropped the graphs that hold the block and drained the stream
+void sampling_controls_forget(const Sampler* sampler) {
+    auto it = registry().find(sampler);
+    if (it == registry().end()) return;
+    if (it->second.dev) (void)hipFree(it->second.dev);
+    registry().erase(it);
+}
+
+}  // namespace q4
+
+extern "C" {
+
+int q4_sampler_set_controls(Sampler* sampler, const q4_sampling_controls* controls) {
+    if (!sampler || (controls && !controls_valid(controls))) return Q4_ERR_ARG;
+    if (!controls && registry().find(sampler) == registry().end()) return Q4_OK;       // off, and never on
+    Controls& ctl = registry()[sampler];
+    const int keep_n = ctl.c.penalty_last_n;
+    ctl.c = controls ? *controls : NEUTRAL;
+    if (!controls) ctl.c.penalty_last_n = keep_n;
+    ctl.dirty = true;
+    ctl.checked_vocab = -1;
+    return Q4_OK;
+}
+int q4_sampler_get_controls(const Sampler* sampler, q4_sampling_controls* out) {
+    if (!sampler || !out) return Q4_ERR_ARG;
+    auto it = registry().find(sampler);
+    *out = it == registry().end() ? NEUTRAL : it->second.c;
+    return Q4_OK;
+}
+int q4_sampler_set_logit_bias(Sampler* sampler, const int* ids, const float* bias, int n) {
+    if (!sampler || !bias_valid(ids, bias, n, 0)) return Q4_ERR_ARG;
+    if (n == 0 && registry().find(sampler) == registry().end()) return Q4_OK;
+    Controls& ctl = registry()[sampler];
+    ctl.n_bias = n;
+    for (int i = 0; i < n; i++) { ctl.ids[i] = ids[i]; ctl.bias[i] = bias[i]; }
+    ctl.dirty = true;
+    ctl.checked_vocab = -1;
+    return Q4_OK;
+}
+
+// "top_k=40,min_p=0.05,repeat_penalty=1.1,last_n=64,presence=0,frequency=0": any subset, any order; a key that is left out keeps its neutral value
+// (last_n: 64). An unknown key, a key without a value, a number with trailing text or a value the setter would refuse: Q4_ERR_ARG, *out untouched.
+int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out) {
+    if (!text || !out) return Q4_ERR_ARG;
+    q4_sampling_controls c = NEUTRAL;
+    c.penalty_last_n = 64;
+    const char* p = text;
+    while (*p) {
+        const char* eq = strchr(p, '=');
+        const char* end = strchr(p, ',');
+        if (!end) end = p + strlen(p);
+        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
+        char key[32], val[64];
+        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
+        memcpy(key, p, eq - p); key[eq - p] = 0;
+        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char* rest = nullptr;
+        if (!strcmp(key, "top_k") || !strcmp(key, "last_n")) {
+            const long v = strtol(val, &rest, 10);
+            if (*rest || v < -1000000 || v > 1000000) return Q4_ERR_ARG;
+            (!strcmp(key, "top_k") ? c.top_k : c.penalty_last_n) = (int)v;
+        } else {
+            float* f = !strcmp(key, "min_p") ? &c.min_p : !strcmp(key, "repeat_penalty") ? &c.repeat_penalty : !strcmp(key, "presence") ? &c.presence_penalty :
+                       !strcmp(key, "frequency") ? &c.frequency_penalty : nullptr;
+            if (!f) return Q4_ERR_ARG;
+            *f = strtof(val, &rest);
+            if (*rest || rest == val) return Q4_ERR_ARG;
+        }
+        p = *end ? end + 1 : end;
+        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
+    }
+    if (!controls_valid(&c)) return Q4_ERR_ARG;
+    *out = c;
+    return Q4_OK;
+}
+
+int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias, const int* tokens,
+                      const int* pPos) {
+    if (!logits || n < 1 || !controls || !controls_valid(controls) || controls->top_k > n || !bias_valid(bias_ids, bias, n_bias, n)) return Q4_ERR_ARG;
+    if (controls_neutral(controls) && n_bias == 0) return Q4_OK;
+    if (!g_op_block) Q4_HIP(hipMalloc((void**)&g_op_block, sizeof(LogitParams)));
+    LogitParams P;
+    fill_params(&P, controls, bias_ids, bias, n_bias);
+    Q4_HIP(hipMemcpyAsync(g_op_block, &P, sizeof(P), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
+    return launch(logits, n, g_op_block, tokens, pPos);
+}
+
+}  // extern "C"

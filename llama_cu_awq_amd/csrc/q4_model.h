@@ -56,5 +56,13 @@ void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the 
 bool logprobs_size_ok(int n, int top_k);
 int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_token, bool greedy);
 int launch_logprobs_pick(const Model* m, const Config* p, RunState* s);
+// q4_logit_process.hip. The sampling controls kept beside a Sampler (q4_sampler_set_controls / _set_logit_bias): whether any is on; before a step and
+// outside any capture, the check against the vocabulary and the device block the launch reads (allocated once, rewritten in stream order when the host
+// changed a value); the launch itself, between the record launch and the argmax / sampler of a generating step
+bool sampling_controls_on(const Sampler* sampler);
+const void* sampling_controls_block(const Sampler* sampler);
+int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block);
+int launch_logit_process_step(const void* block, const Config* p, RunState* s);
+void sampling_controls_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
 
 }  // namespace q4
