@@ -386,6 +386,39 @@ int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out);
 int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias,
                       const int* tokens, const int* pPos);
 
+/* ---- guided decoding (q4_guide.hip; not in the reference) --------------------------------------
+ * A constraint over tokens as a finite automaton: S states (state 0 starts), a dense table next[s][i] of uint16_t, each entry a state in [0, S) or
+ * Q4_GUIDE_DEAD (state s forbids token i). A guide is immutable and lives on the device: S rows of the vocabulary rounded up to 8 entries, 2 * S * V
+ * bytes (64 KB per state at 32000 tokens). A model with a guide attached keeps the automaton's state on the device, by position, in a ring
+ * state[seq_len] of int: Q4_GUIDE_NONE where no guided step ran, Q4_GUIDE_OFFTRACK (sticky) once a token the guide forbids was consumed. Every
+ * GENERATING step of such a model carries one one-block launch between the record launch and the sampling controls' launch (or the argmax / sampler):
+ * with p the step's position,
+ *   prev = p > 0 ? state[p - 1] : NONE;
+ *   s = 0 if prev == NONE; OFFTRACK if prev == OFFTRACK or prev is outside [0, S); else with t = tokens[p] (the pinned ring):
+ *       next[prev][t] if 0 <= t < V and that entry is not DEAD, else OFFTRACK;
+ *   state[p] = s; unless s == OFFTRACK, every logit i with next[s][i] == DEAD becomes -inf (0xFC00); every other logit keeps its 16 bits.
+ * A position outside [0, seq_len) does nothing. Nothing returns to the host between steps: the multi-step replays, the queued-ahead step and the in-graph
+ * sampler stay. A prompt step writes NONE at its position, q4_reset_sequence and q4_set_guide write NONE everywhere: a guided span begins at the first
+ * generating step behind a prompt step (or at position 0), a rewind with q4_run_transformer_at inside a span continues from state[p - 1], a chat's next
+ * turn starts at state 0 again. Log-probability records and copyLogits are taken in front of the launch and describe the raw distribution (a greedy
+ * step's token_logprob is then looked up behind the argmax); after a greedy generating step RunState::logits holds the masked logits; greedy steps are
+ * not screened while a guide is attached. Without a guide: the same launches, graphs and bits as before, nothing allocated. */
+enum { Q4_GUIDE_MAX_STATES = 4096, Q4_GUIDE_DEAD = 0xFFFF, Q4_GUIDE_NONE = -1, Q4_GUIDE_OFFTRACK = -2 };
+typedef struct q4_guide q4_guide;                       /* opaque, device-resident, immutable; may be attached to several models of the same vocabulary */
+/* next: host, [n_states][vocab_size]. Q4_ERR_ARG without touching the GPU: n_states outside [1, Q4_GUIDE_MAX_STATES], vocab_size < 1, an entry that is
+ * neither a state nor DEAD, a state without a live entry (the generated sequence could never leave it). Q4_ERR_ALLOC: no device memory for the table. */
+int q4_guide_new(q4_guide** out, int n_states, int vocab_size, const uint16_t* next);
+int q4_guide_delete(q4_guide* g);                       /* Q4_ERR_ARG while attached to a live model */
+/* NULL: off. Q4_ERR_ARG: vocabulary != the model's, or a Transformer the library did not build. Sets the whole state ring to NONE. Graphs are captured
+ * again only when the guide goes from off to on or back (another guide rewrites a small device block in stream order). */
+int q4_set_guide(Transformer* t, const q4_guide* g);
+const q4_guide* q4_get_guide(const Transformer* t);
+int q4_get_guide_states(const Transformer* t, int first_pos, int n, int* out);   /* synchronises, like q4_get_logprobs; Q4_ERR_ARG without a guide */
+/* Op-level form of the launch: logits [n] halves (16-byte aligned), n == the guide's vocabulary; state_ring, tokens and pPos (one int) device-visible;
+ * a position outside [0, Q4_MAX_SEQ_LEN) does nothing. For one device and one stream: the op keeps one small parameter block for the life of the
+ * process, on the device that was current at its first call, and (like q4_guide_delete) orders itself against the current q4 stream only. */
+int q4_guide_mask(q4_half* logits, int n, const q4_guide* g, int* state_ring, const int* tokens, const int* pPos);
+
 /* build_transformer(Transformer*, char* checkpoint_path, bool perplexity) llama2_q4.cu:408-426 (prints the
  * same "Model params" / "Loading Weights... done!" lines unless quiet), free_transformer :428-432 */
 int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perplexity);
@@ -456,6 +489,8 @@ void q4_tokenizer_delete(struct Tokenizer* t);                                  
 int q4_tokenizer_encode(struct Tokenizer* t, const char* text, int bos, int eos, int* tokens, int* n_tokens);
 const char* q4_tokenizer_decode(struct Tokenizer* t, int prev_token, int token);   /* decode :68-79 */
 int q4_tokenizer_max_token_length(const struct Tokenizer* t);
+/* raw bytes of a vocabulary entry as the file holds them (may contain NUL; not terminated): what a guide compiler lifts a byte automaton over */
+int q4_tokenizer_piece(const struct Tokenizer* t, int id, const char** bytes, int* len);
 
 /* ---- CLI: main() llama2_q4.cu:622-720 behind a callable (the llama2_q4 executable calls this) --- */
 int q4_main(int argc, char** argv);

@@ -20,6 +20,7 @@ KV_FORMATS = {"fp16": KV_FP16, "fp8": KV_FP8}
 MAX_TOP_LOGPROBS = 20           # Q4_MAX_TOP_LOGPROBS
 MAX_PENALTY_WINDOW = 1024       # Q4_MAX_PENALTY_WINDOW
 MAX_LOGIT_BIAS = 256            # Q4_MAX_LOGIT_BIAS
+GUIDE_MAX_STATES, GUIDE_DEAD, GUIDE_NONE, GUIDE_OFFTRACK = 4096, 0xFFFF, -1, -2   # Q4_GUIDE_*
 
 
 class Config(C.Structure):
@@ -83,6 +84,7 @@ SYMBOLS = [
     "q4_logprob_topk", "q4_set_logprobs", "q4_get_logprobs_k", "q4_get_logprobs", "q4_score_ids",
     "q4_set_greedy_screen", "q4_get_greedy_screen", "q4_screen_candidates", "q4_greedy_screen_op",
     "q4_sampler_set_controls", "q4_sampler_get_controls", "q4_sampler_set_logit_bias", "q4_parse_sampling_controls", "q4_process_logits",
+    "q4_guide_new", "q4_guide_delete", "q4_set_guide", "q4_get_guide", "q4_get_guide_states", "q4_guide_mask", "q4_tokenizer_piece",
 ]
 
 _lib = None
@@ -224,6 +226,15 @@ def lib():
         L.q4_sampler_set_logit_bias.argtypes = [vp, vp, vp, i]
         L.q4_parse_sampling_controls.argtypes = [C.c_char_p, C.POINTER(SamplingControls)]
         L.q4_process_logits.argtypes = [vp, i, C.POINTER(SamplingControls), vp, vp, i, vp, vp]
+    if hasattr(L, "q4_guide_new"):                 # (older builds under tools/ab.py do not have it)
+        L.q4_guide_new.argtypes = [C.POINTER(vp), i, i, vp]
+        L.q4_guide_delete.argtypes = [vp]
+        L.q4_set_guide.argtypes = [vp, vp]
+        L.q4_get_guide.argtypes = [vp]
+        L.q4_get_guide.restype = vp
+        L.q4_get_guide_states.argtypes = [vp, i, i, vp]
+        L.q4_guide_mask.argtypes = [vp, i, vp, vp, vp, vp]
+        L.q4_tokenizer_piece.argtypes = [vp, i, C.POINTER(C.c_void_p), C.POINTER(i)]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -357,6 +368,37 @@ def process_logits(logits, n, controls=None, logit_bias=None, tokens=None, pos=N
                                   pos.ptr if pos else None))
 
 
+class Guide:
+    """q4_guide: a token automaton on the device. table: uint16 [S, V], an entry a state or GUIDE_DEAD (llama_cu_awq_amd.guide builds them from
+    choices or a regular expression). Immutable; may be attached to several models of the same vocabulary; close() fails while one still holds it."""
+
+    def __init__(self, table):
+        table = np.ascontiguousarray(table, dtype=np.uint16)
+        if table.ndim != 2:
+            raise ValueError("a guide's table is [states, vocabulary]")
+        self.n_states, self.vocab_size = int(table.shape[0]), int(table.shape[1])
+        h = C.c_void_p()
+        check(lib().q4_guide_new(C.byref(h), self.n_states, self.vocab_size, table.ctypes.data))
+        self.h = h.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(lib().q4_guide_delete(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def guide_mask(logits, n, guide, state_ring, tokens, pos):
+    """q4_guide_mask over DevBufs: one guide launch -- advances the automaton at the position in `pos` (one int32) from state_ring[pos - 1] and the ring
+    entry tokens[pos], writes state_ring[pos] and -inf over the logits (n halves) the new state forbids."""
+    check(lib().q4_guide_mask(logits.ptr, n, guide.h, state_ring.ptr, tokens.ptr, pos.ptr))
+
+
 def greedy_screen_op(x, w, n, d, rms_w=None):
     """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
     tok, cand = C.c_int(), C.c_int()
@@ -388,7 +430,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None):
+                 logit_bias=None, guide=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -424,6 +466,8 @@ class Transformer:
                 self.set_sampling(**sampling)
             if logit_bias is not None:
                 self.set_logit_bias(logit_bias)
+            if guide is not None:
+                self.set_guide(guide)
         except Exception:
             self.close()
             raise
@@ -515,6 +559,18 @@ class Transformer:
         ids, bias = _bias_arrays(logit_bias)
         check(lib().q4_sampler_set_logit_bias(self.sampler, ids.ctypes.data, bias.ctypes.data, ids.shape[0]))
 
+    def set_guide(self, guide):
+        """Guided decoding (q4_set_guide): a Guide, or None for off. Every generating step then masks what the automaton's state forbids; the state
+        is kept on the device by position and starts at 0 behind the prompt."""
+        check(lib().q4_set_guide(self.h, guide.h if guide is not None else None))
+        self._guide = guide             # (keeps the handle alive while the model holds it)
+
+    def guide_states(self, first_pos, n):
+        """the automaton's state at positions first_pos .. first_pos + n - 1 (GUIDE_NONE: no guided step ran there); synchronises"""
+        out = np.empty(n, dtype=np.int32)
+        check(lib().q4_get_guide_states(self.h, first_pos, n, out.ctypes.data))
+        return out
+
     def set_logprobs(self, top_k):
         """Per-token log-probability records inside the decode step: None / -1 off, 0 the chosen or target token only, K <= 20 also the top K."""
         check(lib().q4_set_logprobs(self.h, -1 if top_k is None else int(top_k)))
@@ -573,6 +629,7 @@ class Transformer:
 class Tokenizer:
     def __init__(self, path, vocab_size):
         self.h = lib().q4_tokenizer_new(path.encode(), vocab_size)
+        self.vocab_size = vocab_size
         if not self.h:
             raise Q4Error("couldn't load %s" % path)
 
@@ -585,6 +642,15 @@ class Tokenizer:
 
     def decode(self, prev, tok):
         return lib().q4_tokenizer_decode(self.h, prev, tok)
+
+    def piece(self, tok):
+        """the raw bytes of a vocabulary entry, as the file holds them (q4_tokenizer_piece)"""
+        p, n = C.c_void_p(), C.c_int()
+        check(lib().q4_tokenizer_piece(self.h, int(tok), C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def pieces(self):
+        return [self.piece(i) for i in range(self.vocab_size)]
 
     def close(self):
         if self.h:

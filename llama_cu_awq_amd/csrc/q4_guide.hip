@@ -1,0 +1,241 @@
+// q4_guide.hip -- guided decoding: a token automaton masks the step's fp16 logits in place, in front of the sampling controls' launch and the argmax
+// or the sampler. Not in the reference.
+// A guide is a dense table next[S][V] of uint16_t (a state in [0, S), or Q4_GUIDE_DEAD: the state forbids the token), immutable, on the device as S rows of
+// V rounded up to 8 entries -- a row is read in 16-byte pieces --: 2 * S * V bytes, 64 KB per state at 32000 tokens, 262 MB at the 4096 states a guide may
+// have. The automaton's state lives on the device by position, in a ring state[seq_len] of int per model (Q4_GUIDE_NONE: no guided step ran here,
+// Q4_GUIDE_OFFTRACK: a token the guide forbids was consumed; sticky).
+// ONE 1024-thread block, the partition of q4_logprobs.hip and q4_logit_process.hip: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last
+// whole chunk, one tail element. With p = *pPos:
+//   1. prev = p > 0 ? state[p - 1] : NONE
+//   2. s = 0 if prev == NONE; OFFTRACK if prev == OFFTRACK or prev is outside [0, S); else with t = tokens[p] (the pinned ring, read by position the way
+//      copy_embedding_kernel and the penalty window read it): next[prev][t] if 0 <= t < V and the entry is a state, else OFFTRACK
+//   3. state[p] = s (one lane, a plain store)
+//   4. s != OFFTRACK: every i < n with next[s][i] == DEAD becomes the half 0xFC00 (-inf); every other entry keeps its 16 bits -- NaN payloads, -0 and
+//      infinities included. s == OFFTRACK: the logits stay as they are.
+// The thread's first four chunks of the logits (all of them up to 32 x 1024 logits) are requested BEFORE the dependent chain p -> state[p - 1] ->
+// tokens[p] -> next[prev][t] -- four dependent reads (the position beside the block's fields, the state, the ring entry, the table's entry), one of
+// them across PCIe -- so the chain hides behind the logits' load instead of standing in front of
+// it; larger vocabularies read the rest in a loop behind the chain. No atomics, no arrival order: the same input gives the same bytes on every launch.
+// Nothing that comes out of memory indexes anything unchecked: p against [0, seq_len), prev and the table's entry against [0, S), t against [0, V) -- a
+// garbage ring gives OFFTRACK, never a read out of bounds.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "q4_device.h"
+#include "q4_model.h"
+using namespace q4;
+
+// the handle of the C ABI: the device table and how many live models hold it
+struct q4_guide {
+    uint16_t* table;     // device, [S][stride]
+    int S, V, stride;    // stride: V rounded up to 8
+    mutable int attached;   // (a guide is handed around as const: immutable but for this count)
+};
+
+namespace {
+
+constexpr int GM_T = 1024, GM_Q = 4;                   // threads, register-resident 16-byte chunks per thread
+
+// what the kernel reads: one small device block per model (or the op-level launcher's), rewritten in stream order when the guide changes, so a captured
+// graph holds the block's address and nothing of the guide
+struct GuideBlock {
+    const uint16_t* table;
+    int* state;
+    int S, V, stride, seq_len;
+};
+
+__device__ __forceinline__ u32x4 mask_chunk(const u32x4& q, const u32x4& r, bool& changed) {
+    u32x4 o = q;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const unsigned lo = (r[d] & 0xFFFFu) == 0xFFFFu ? 0xFFFFu : 0u, hi = (r[d] >> 16) == 0xFFFFu ? 0xFFFF0000u : 0u;
+        const unsigned dead = lo | hi;
+        o[d] = (q[d] & ~dead) | (0xFC00FC00u & dead);
+        changed = changed || o[d] != q[d];
+    }
+    return o;
+}
+
+// The block's pointers come out of memory, so the compiler knows no address space for them and would read through them with flat VECTOR loads -- which
+// return in order behind the logits' loads and would put the whole chain behind them. Cast to the global address space, the chain's reads are uniform
+// loads on the scalar unit's own counter (the table's entry as the aligned 32-bit word that holds it: the scalar unit has no 16-bit load).
+#define GM_GLOBAL __attribute__((address_space(1)))
+
+__global__ void __launch_bounds__(GM_T) guide_mask_kernel(q4_half* logits, int n, const GuideBlock* __restrict__ blk, const int* tokens, const int* pPos) {
+    const int tid = threadIdx.x;
+    const int n8 = n >> 3, tail = n8 * 8 + tid;
+    u32x4* lv = reinterpret_cast<u32x4*>(logits);
+    // the logits first: their requests are in flight while the chain below resolves
+    u32x4 pq[GM_Q];
+#pragma unroll
+    for (int kq = 0; kq < GM_Q; kq++) {
+        const int u = tid + kq * GM_T;
+        pq[kq] = u < n8 ? lv[u] : (u32x4){0u, 0u, 0u, 0u};
+    }
+
+    // ---- steps 1 - 3 (block-uniform: every thread resolves the same chain)
+    const int p = *pPos;
+    const GM_GLOBAL uint16_t* table = (const GM_GLOBAL uint16_t*)blk->table;
+    int* state = blk->state;
+    const int S = blk->S, V = blk->V, stride = blk->stride, seq_len = blk->seq_len;
+    if (p < 0 || p >= seq_len || n > stride) return;
+    const int prev = p > 0 ? ((const GM_GLOBAL int*)state)[p - 1] : (int)Q4_GUIDE_NONE;
+    int s = Q4_GUIDE_OFFTRACK;
+    if (prev == Q4_GUIDE_NONE) s = 0;
+    else if (prev >= 0 && prev < S) {
+        const int t = tokens[p];
+        if (t >= 0 && t < V) {
+            const size_t at = (size_t)prev * stride + t;
+            const int e = (int)((((const GM_GLOBAL uint32_t*)table)[at >> 1] >> ((at & 1) * 16)) & 0xFFFFu);
+            if (e < S) s = e;                                  // (DEAD is above every state)
+        }
+    }
+    if (tid == 0) state[p] = s;
+    if (s == Q4_GUIDE_OFFTRACK) return;
+
+    // ---- step 4
+    const GM_GLOBAL uint16_t* row = table + (size_t)s * stride;
+    const GM_GLOBAL u32x4* rv = (const GM_GLOBAL u32x4*)row;
+    u32x4 rq[GM_Q];                                            // (requested together: one wait for the row, not one per chunk)
+#pragma unroll
+    for (int kq = 0; kq < GM_Q; kq++) {
+        const int u = tid + kq * GM_T;
+        rq[kq] = u < n8 ? rv[u] : (u32x4){0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int kq = 0; kq < GM_Q; kq++) {
+        const int u = tid + kq * GM_T;
+        if (u < n8) {
+            bool changed = false;
+            const u32x4 o = mask_chunk(pq[kq], rq[kq], changed);
+            if (changed) lv[u] = o;
+        }
+    }
+    for (int u = tid + GM_Q * GM_T; u < n8; u += GM_T) {     // more than 32 x 1024 logits: the rest, chunk by chunk
+        bool changed = false;
+        const u32x4 q = lv[u], r = rv[u];
+        const u32x4 o = mask_chunk(q, r, changed);
+        if (changed) lv[u] = o;
+    }
+    if (tail < n && row[tail] == 0xFFFFu) logits[tail] = (q4_half)0xFC00u;
+}
+
+GuideBlock* g_op_block = nullptr;      // q4_guide_mask's own block
+
+int launch(q4_half* logits, int n, const GuideBlock* dev, const int* tokens, const int* pPos) {
+    Q4_LAUNCH(guide_mask_kernel, dim3(1), dim3(GM_T), 0, logits, n, dev, tokens, pPos);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+
+int ring_to_none(const Model* m, int first, int count) {
+    if (first < 0 || count < 0 || first + count > m->guide_len) return Q4_ERR_ARG;
+    Q4_HIP(hipMemsetAsync(m->guide_state + first, 0xFF, (size_t)count * sizeof(int), g_stream));
+    return Q4_OK;
+}
+
+}  // namespace
+
+namespace q4 {
+
+int launch_guide_step(const Model* m, const Config* p, RunState* s) {
+    return launch(s->logits, p->vocab_size, (const GuideBlock*)m->guide_block, &(s->shared_data->tokens[0]), s->pos);
+}
+int guide_clear_positions(const Model* m, int pos, int nsteps) { return ring_to_none(m, pos, nsteps); }
+int guide_clear_ring(const Model* m) { return ring_to_none(m, 0, m->guide_len); }
+// q4_free_transformer: the graphs that hold the block are gone and the device has drained
+void guide_release(Model* m) {
+    if (m->guide) m->guide->attached--;
+    if (m->guide_state) (void)hipFree(m->guide_state);
+    if (m->guide_block) (void)hipFree(m->guide_block);
+    m->guide = nullptr; m->guide_state = nullptr; m->guide_block = nullptr; m->guide_len = 0;
+}
+
+}  // namespace q4
+
+extern "C" {
+
+int q4_guide_new(q4_guide** out, int n_states, int vocab_size, const uint16_t* next) {
+    if (!out || !next || n_states < 1 || n_states > Q4_GUIDE_MAX_STATES || vocab_size < 1) return Q4_ERR_ARG;
+    for (int s = 0; s < n_states; s++) {
+        const uint16_t* row = next + (size_t)s * vocab_size;
+        bool live = false;
+        for (int i = 0; i < vocab_size; i++) {
+            if (row[i] == Q4_GUIDE_DEAD) continue;
+            if (row[i] >= n_states) return Q4_ERR_ARG;
+            live = true;
+        }
+        if (!live) return Q4_ERR_ARG;
+    }
+    const int stride = (vocab_size + 7) / 8 * 8;
+    const size_t bytes = (size_t)n_states * stride * sizeof(uint16_t);
+    uint16_t* table = nullptr;
+    if (hipMalloc((void**)&table, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+    std::vector<uint16_t> padded((size_t)n_states * stride, (uint16_t)Q4_GUIDE_DEAD);
+    for (int s = 0; s < n_states; s++) memcpy(&padded[(size_t)s * stride], next + (size_t)s * vocab_size, (size_t)vocab_size * sizeof(uint16_t));
+    if (hipMemcpy(table, padded.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(table);
+        return Q4_ERR_HIP;
+    }
+    q4_guide* g = (q4_guide*)calloc(1, sizeof(q4_guide));
+    if (!g) { (void)hipFree(table); return Q4_ERR_ALLOC; }
+    g->table = table; g->S = n_states; g->V = vocab_size; g->stride = stride;
+    *out = g;
+    return Q4_OK;
+}
+int q4_guide_delete(q4_guide* g) {
+    if (!g || g->attached > 0) return Q4_ERR_ARG;
+    if (g_stream) Q4_HIP(hipStreamSynchronize(g_stream));     // a launch of a model that held it until a moment ago may still read the table
+    Q4_HIP(hipFree(g->table));
+    free(g);
+    return Q4_OK;
+}
+
+int q4_set_guide(Transformer* t, const q4_guide* g) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || (g && g->V != t->config.vocab_size)) return Q4_ERR_ARG;
+    if (!g && !m->guide) return Q4_OK;                         // off, and (possibly) never on: nothing to allocate or clear
+    if (g && !m->guide_block) {                                // the first guide of this model: the ring and the block, kept until q4_free_transformer
+        int* ring = nullptr;
+        void* block = nullptr;
+        if (hipMalloc((void**)&ring, (size_t)t->config.seq_len * sizeof(int)) != hipSuccess || hipMalloc(&block, sizeof(GuideBlock)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ring) (void)hipFree(ring);
+            return Q4_ERR_ALLOC;
+        }
+        m->guide_state = ring;
+        m->guide_len = t->config.seq_len;
+        m->guide_block = block;
+    }
+    if (g && g != m->guide) {                                  // (pageable: staged before the call returns)
+        const GuideBlock host = {g->table, m->guide_state, g->S, g->V, g->stride, m->guide_len};
+        Q4_HIP(hipMemcpyAsync(m->guide_block, &host, sizeof(host), hipMemcpyHostToDevice, g_stream));
+    }
+    if (m->guide) m->guide->attached--;
+    if (g) g->attached++;
+    m->guide = g;
+    return guide_clear_ring(m);
+}
+const q4_guide* q4_get_guide(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m ? m->guide : nullptr;
+}
+int q4_get_guide_states(const Transformer* t, int first_pos, int n, int* out) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !m->guide || !out || first_pos < 0 || n < 0 || (long long)first_pos + n > m->guide_len) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    if (n > 0) Q4_HIP(hipMemcpy(out, m->guide_state + first_pos, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    return Q4_OK;
+}
+
+int q4_guide_mask(q4_half* logits, int n, const q4_guide* g, int* state_ring, const int* tokens, const int* pPos) {
+    if (!logits || !g || n != g->V || !state_ring || !tokens || !pPos) return Q4_ERR_ARG;
+    if (!g_op_block) Q4_HIP(hipMalloc((void**)&g_op_block, sizeof(GuideBlock)));
+    const GuideBlock host = {g->table, state_ring, g->S, g->V, g->stride, Q4_MAX_SEQ_LEN};
+    Q4_HIP(hipMemcpyAsync(g_op_block, &host, sizeof(host), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
+    return launch(logits, n, g_op_block, tokens, pPos);
+}
+
+}  // extern "C"

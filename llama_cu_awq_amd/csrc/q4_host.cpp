@@ -69,6 +69,12 @@ struct Tokenizer* q4_tokenizer_new(const char* tokenizer_path, int vocab_size) {
 
 void q4_tokenizer_delete(struct Tokenizer* t) { delete t; }
 int q4_tokenizer_max_token_length(const struct Tokenizer* t) { return (int)t->max_token_length; }
+int q4_tokenizer_piece(const struct Tokenizer* t, int id, const char** bytes, int* len) {
+    if (!t || !bytes || !len || id < 0 || id >= t->vocab_size) return Q4_ERR_ARG;
+    *bytes = t->vocab[id].data();
+    *len = (int)t->vocab[id].size();
+    return Q4_OK;
+}
 
 const char* q4_tokenizer_decode(struct Tokenizer* t, int prev_token, int token) {  // decode :68-79
     const char* piece = t->vocab[token].c_str();

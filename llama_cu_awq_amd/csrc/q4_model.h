@@ -32,6 +32,10 @@ struct Model {
     float* lp_top = nullptr;        // [seq_len][K]
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
+    const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model
+    int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)
+    int guide_len = 0;
+    void* guide_block = nullptr;    // what the guide launch reads: {table, ring, sizes}; captured graphs hold its address
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
 using Models = std::map<const RunState*, Model>;
@@ -64,5 +68,11 @@ const void* sampling_controls_block(const Sampler* sampler);
 int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block);
 int launch_logit_process_step(const void* block, const Config* p, RunState* s);
 void sampling_controls_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
+// q4_guide.hip. The guide launch of a generating step, between the record launch and the sampling controls' launch; NONE over the ring positions of a
+// prompt group, or over the whole ring (both in stream order, outside any capture); what q4_free_transformer releases
+int launch_guide_step(const Model* m, const Config* p, RunState* s);
+int guide_clear_positions(const Model* m, int pos, int nsteps);
+int guide_clear_ring(const Model* m);
+void guide_release(Model* m);
 
 }  // namespace q4

@@ -388,8 +388,9 @@ void q4_free_transformer(Transformer* t) {                                      
     drop_graphs_of(&t->state);
     auto it = models().find(&t->state);
     if (it != models().end()) {
-        const Model& m = it->second;
+        Model& m = it->second;
         hipDeviceSynchronize();
+        guide_release(&m);
         for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);

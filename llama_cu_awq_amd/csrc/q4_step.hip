@@ -41,7 +41,8 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
 
 // graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
 // bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in), bit5 = the classifier as screen + refine (cls_screen.h),
-// bit6 = the sampling controls' launch (q4_logit_process.hip; the address of the Sampler's parameter block baked in, none of its values). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// bit6 = the sampling controls' launch (q4_logit_process.hip; the address of the Sampler's parameter block baked in, none of its values),
+// bit7 = the guide launch (q4_guide.hip; the address of the model's guide block baked in, nothing of the guide). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -51,23 +52,24 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][128];
-    bool captured[Q4_MAX_GRAPHS][128];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][256];
+    bool captured[Q4_MAX_GRAPHS][256];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
     const void* controls;              // the parameter block the set's graphs with the sampling controls' launch read
+    const void* guide;                 // the guide block the set's graphs with the guide launch read
 };
 static GraphSet g_sets[GRAPH_OWNERS];
 static unsigned long long g_set_clock = 0;
 static int g_graph_captures = 0;
 // a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
 // mask: 0 drops every variant and gives the set up; 4 the sampled variants (what they have baked in is forgotten); 16 those with the record launch;
-// 64 those with the sampling controls' launch
+// 64 those with the sampling controls' launch; 128 those with the guide launch
 static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 128; v++)
+        for (int v = 0; v < 256; v++)
             if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
@@ -76,6 +78,7 @@ static void drop_graphs(GraphSet& gs, int mask) {
     if (!mask) gs.owner = nullptr;
     if (!mask || (mask & 4)) { gs.sampler = nullptr; gs.coins = nullptr; }
     if (!mask || (mask & 64)) gs.controls = nullptr;
+    if (!mask || (mask & 128)) gs.guide = nullptr;
 }
 void drop_graphs_of(const RunState* s) {
     for (GraphSet& gs : g_sets)
@@ -102,11 +105,11 @@ static GraphSet& graph_set_of(const RunState* owner, const Config* p, const Tran
 
 // A step runs its classifier as screen + refine only when nothing but the greedy token is taken from its logits: a greedy generating step of a token
 // loop (may_screen: the public per-step entry points never pass it -- their callers read RunState::logits), no fp32 copy, no log-probability records, a
-// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls (their launch rewrites
-// whole logits).
+// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls and no guide (their
+// launches rewrite whole logits).
 static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits, const Sampler* sampler) {
     return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
-           !sampling_controls_on(sampler) &&
+           !sampling_controls_on(sampler) && !m->guide &&
            cls_screen_shape(m->screen.n, m->screen.d);
 }
 
@@ -304,20 +307,28 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     if (pos < 0 || pos + nsteps > p->seq_len) return Q4_ERR_ARG;
     const Model* lpm = model_of(s);                                                // q4_set_logprobs: a record launch between the classifier and the sampler
     const bool screened = step_screens(lpm, may_screen != 0, gen_token, greedy, copyLogits, pSampler);
+    // q4_set_guide: a prompt group puts NONE at its positions (in stream order, outside the graph, where the coin ring's copy sits); a generating step
+    // carries the guide launch between the record launch and the controls' launch
+    const Model* guided = lpm && lpm->guide ? lpm : nullptr;
+    if (guided && !gen_token) { Q4_TRY(guide_clear_positions(guided, pos, nsteps)); guided = nullptr; }
     if (lpm && lpm->logprobs_k < 0) lpm = nullptr;
     // q4_sampler_set_controls / _set_logit_bias: a launch that rewrites the logits between the record launch and the argmax / sampler of a generating step
     const void* controls = nullptr;
     if (gen_token && sampling_controls_on(pSampler)) Q4_TRY(sampling_controls_prepare(pSampler, p->vocab_size, &controls));
-    // the record of a generating step whose logits the controls rewrite: the chosen token need not be the raw logits' largest, so a greedy step keeps
-    // the raw logits aside and looks its token up behind the argmax, the way a sampled step does
-    const bool lp_greedy = greedy && !controls, lp_pick = lpm && gen_token && (!greedy || controls);
+    // the record of a generating step whose logits the controls or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
+    // step keeps the raw logits aside and looks its token up behind the argmax, the way a sampled step does
+    const bool lp_greedy = greedy && !controls && !guided, lp_pick = lpm && gen_token && (!greedy || controls || guided);
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
         const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0) | (screened ? 32 : 0) |
-                            (controls ? 64 : 0);
+                            (controls ? 64 : 0) | (guided ? 128 : 0);
+        if (guided && gs.guide != guided->guide_block) {
+            drop_graphs(gs, 128);
+            gs.guide = guided->guide_block;
+        }
         if (controls && gs.controls != controls) {
             drop_graphs(gs, 64);
             gs.controls = controls;
@@ -343,7 +354,8 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
                 rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0, screened);
                 if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
                 if (!rc && lpm) rc = launch_logprobs_step(lpm, p, s, gen_token, lp_greedy);   // (before the sampler: it advances the position and overwrites the logits)
-                if (!rc && controls) rc = launch_logit_process_step(controls, p, s);       // (behind the records: they describe the model's raw logits)
+                if (!rc && guided) rc = launch_guide_step(guided, p, s);                   // (behind the records: they describe the model's raw logits;
+                if (!rc && controls) rc = launch_logit_process_step(controls, p, s);       //  the mask first: top-k counts allowed tokens)
                 if (!rc && greedy) {
                     if (feed && i + 1 < nsteps)
                         rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
@@ -376,6 +388,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false, screened));   // :374
     if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
     if (lpm) Q4_TRY(launch_logprobs_step(lpm, p, s, gen_token, lp_greedy));
+    if (guided) Q4_TRY(launch_guide_step(guided, p, s));
     if (controls) Q4_TRY(launch_logit_process_step(controls, p, s));
     Q4_TRY(sample_impl(pSampler, s, gen_token, true));
     return lp_pick ? launch_logprobs_pick(lpm, p, s) : Q4_OK;
@@ -385,7 +398,9 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
 int q4_reset_sequence(RunState* s, const int* prompt_tokens, int num_prompt_tokens) {
     Q4_HIP(hipMemsetAsync(s->pos, 0, sizeof(int), g_stream));                     // llama2_q4.cu:461
     if (g_rearm_after > 0 && --g_rearm_after == 0 && g_fusion == 1) { g_fusion = g_rearm_level; q4_reset_graphs(); }   // probation over
-    Q4_TRY(clear_handoff_state(s, model_of(s), false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
+    const Model* m = model_of(s);
+    if (m && m->guide) Q4_TRY(guide_clear_ring(m));        // a new sequence starts at the guide's state 0
+    Q4_TRY(clear_handoff_state(s, m, false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
     Q4_HIP(hipStreamSynchronize(g_stream));
     s->shared_data->pos = 0;                                                       // :462
     if (prompt_tokens && num_prompt_tokens > 0)
