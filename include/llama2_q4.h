@@ -419,6 +419,70 @@ int q4_get_guide_states(const Transformer* t, int first_pos, int n, int* out);  
  * process, on the device that was current at its first call, and (like q4_guide_delete) orders itself against the current q4 stream only. */
 int q4_guide_mask(q4_half* logits, int n, const q4_guide* g, int* state_ring, const int* tokens, const int* pPos);
 
+/* ---- sequence snapshots and prompt-prefix reuse (q4_snapshot.hip, q4_kv_copy.hip; not in the reference) --------------------------
+ * Everything a sequence keeps is indexed by position -- the K / V cache [layer][seq_len][kv_dim], the token ring, the coin ring, the guide's state ring,
+ * the log-probability records, the penalty window -- and the device keeps its own position. These entry points start a sequence somewhere else than at
+ * position 0, over K / V rows that are already in place, and keep a prefix's rows to put them back later or into another model of the same checkpoint.
+ * All of it is opt-in: a caller who uses none of them gets the launches, the graphs and the tokens it got before. Nothing is added to the decode step. */
+typedef struct q4_snapshot q4_snapshot;                 /* opaque, device-resident, immutable */
+struct q4_snapshot_info {                               /* (the record shares its name with the function that fills it: write `struct q4_snapshot_info`) */
+    int n_pos;                                          /* positions [0, n_pos) */
+    int kv_format;                                      /* Q4_KV_FP16 / Q4_KV_FP8 */
+    int n_layers, n_kv_heads, head_size;
+    float rope_theta;
+    unsigned long long fingerprint;                     /* of the checkpoint file: its header without seq_len, its size, its first and last 64 KiB */
+    unsigned long long device_bytes;                    /* the packed rows */
+    unsigned long long export_bytes;                    /* what q4_snapshot_export writes */
+};
+/* q4_reset_sequence that starts at start_pos: the same hand-off clearing, the same probation countdown, the guide ring to NONE; the device position and
+ * SharedData::pos become start_pos, the ring receives tokens[0 .. num_tokens), and the K / V rows below start_pos stay as they are. The caller's contract:
+ * those rows were computed from tokens[0 .. start_pos) -- by this model since its last q4_reset_sequence (start_pos below the current position is the
+ * roll-back: regenerate an answer, edit the last turn), or put there by q4_snapshot_restore. Q4_ERR_ARG unless 0 <= start_pos <= num_tokens - 1 (the last
+ * prompt token always runs: it produces the logits) and start_pos <= seq_len. start_pos = 0 is exactly q4_reset_sequence. Behind the resumed position a
+ * guide starts at state 0, as behind any prompt; log-probability records below start_pos are left as they are. */
+int q4_resume_sequence(RunState* s, const int* tokens, int num_tokens, int start_pos);
+/* Synchronises the stream, then returns the largest start_pos that is safe for `tokens` as the model stands: the length of the common prefix of tokens
+ * and the ring, capped by the positions the device has completed and by num_tokens - 1. 0 for a model whose rows are suspect: q4_handoff_status has
+ * reported a time-out and no q4_reset_sequence has followed. A null pointer, num_tokens < 1 or a Transformer the library did not build: -Q4_ERR_ARG
+ * (the one negative value it returns). */
+int q4_common_prefix(const Transformer* t, const int* tokens, int num_tokens);
+/* q4_generate_ids starting at start_pos (q4_generate_ids is the start_pos = 0 call of it). The loop draws one coin per step whether or not the step
+ * samples, so start_pos coins are drawn from the sampler and discarded first: with the same seed a resumed sampled generation produces the full one's
+ * tokens, and a reused Sampler stands at the same state after either. out_tokens holds the whole ring from index 0; timed_tokens is the reference's rule
+ * over the steps this call ran (one less than their number). The retry after a hand-off time-out runs from position 0 with a full reset; so does a prompt
+ * with an EOS token inside [1, start_pos), where the full loop would have stopped. A start_pos outside [0, num_prompt_tokens - 1] or above seq_len, or a
+ * null pointer: -1.0 (like every failure of q4_generate_ids) with q4_last_error set, nothing touched. */
+double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos,
+                            int* out_tokens, int* timed_tokens, double* seconds);
+/* Synchronises, then copies the K and V rows (an FP8 model's row exponents too) of positions [0, n_pos) of every layer into a packed device buffer:
+ * [K|V][layer][n_pos][kv_dim] in the cache's own element type, then for an FP8 model [K|V][layer][n_kv_heads][n_pos] exponent bytes; keeps
+ * tokens[0 .. n_pos) of the ring on the host. Q4_ERR_ARG unless 1 <= n_pos <= the positions the device has completed (SharedData::pos), and for a model
+ * whose rows are suspect (q4_common_prefix). An FP8 model's fp16 staging rows are the current position's and are not part of a snapshot. */
+int q4_snapshot_new(q4_snapshot** out, const Transformer* t, int n_pos);
+/* Stream-ordered on the q4 stream: copies the rows back into positions [0, n_pos) of t, which may be another Transformer of the same checkpoint, also
+ * one opened with another seq_len. Does not move the position or touch the ring: follow with q4_resume_sequence or q4_generate_ids_from at any
+ * start_pos <= n_pos, with tokens that begin with the snapshot's. The restored prefix counts as a prompt: the guide ring is NONE there, so the automaton
+ * starts at state 0 behind it, as behind any prompt; log-probability records below n_pos are left as they are. Q4_ERR_ARG, nothing copied: another
+ * checkpoint (fingerprint), geometry (layers, kv heads, head size), rope_theta or K / V format, or n_pos above t's seq_len. */
+int q4_snapshot_restore(Transformer* t, const q4_snapshot* s);
+int q4_snapshot_delete(q4_snapshot* s);                 /* synchronises the q4 stream first: a restore may still be reading */
+int q4_snapshot_info(const q4_snapshot* s, struct q4_snapshot_info* out);
+int q4_snapshot_tokens(const q4_snapshot* s, int* out); /* out: n_pos ints */
+/* The serialised form, little-endian: a 48-byte header {u32 magic "Q4SN", u32 version 1, i32 kv_format, i32 n_layers, i32 n_kv_heads, i32 head_size,
+ * i32 n_pos, f32 rope_theta, u64 fingerprint, u64 payload_bytes}, n_pos i32 tokens, then the packed rows as above. q4_snapshot_export writes
+ * export_bytes bytes (a smaller capacity: Q4_ERR_ARG); q4_snapshot_import checks with q4_snapshot_check first, then allocates and uploads.
+ * q4_snapshot_check touches no GPU: the magic, the version, kv_format in {0, 1}, n_layers / n_kv_heads / head_size in [1, 65536], n_pos in
+ * [1, Q4_MAX_SEQ_LEN], a finite rope_theta, and `bytes` exactly the size the header implies -- computed in 64 bits with overflow checks before anything
+ * is allocated; a truncated, padded, negative-count or overflowing blob is Q4_ERR_ARG. out may be NULL. */
+int q4_snapshot_export(const q4_snapshot* s, void* host, size_t capacity);
+int q4_snapshot_import(q4_snapshot** out, const void* host, size_t bytes);
+int q4_snapshot_check(const void* host, size_t bytes, struct q4_snapshot_info* out);
+/* Op-level form of the copy launch (q4_kv_copy.hip): run r < outer moves run_bytes bytes from src + r * src_stride to dst + r * dst_stride on the q4
+ * stream -- 16-byte accesses where source and destination share their offset from a 16-byte boundary, bytes elsewhere; any alignment, 64-bit offsets.
+ * Q4_ERR_ARG without a launch: a null pointer, a negative argument, run_bytes above either stride when outer > 1, source and destination ranges (first
+ * byte of the first run to last byte of the last) that overlap. */
+int q4_copy_runs(void* dst, const void* src, long long outer, long long dst_stride, long long src_stride, long long run_bytes);
+
 /* build_transformer(Transformer*, char* checkpoint_path, bool perplexity) llama2_q4.cu:408-426 (prints the
  * same "Model params" / "Loading Weights... done!" lines unless quiet), free_transformer :428-432 */
 int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perplexity);

@@ -54,6 +54,15 @@ class CliArgs(C.Structure):
                 ("seed_from_time", C.c_int)]
 
 
+class SnapshotInfo(C.Structure):
+    """struct q4_snapshot_info"""
+    _fields_ = [("n_pos", C.c_int), ("kv_format", C.c_int), ("n_layers", C.c_int), ("n_kv_heads", C.c_int), ("head_size", C.c_int),
+                ("rope_theta", C.c_float), ("fingerprint", C.c_ulonglong), ("device_bytes", C.c_ulonglong), ("export_bytes", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SamplingControls(C.Structure):
     """q4_sampling_controls; the defaults are the neutral values (everything off)"""
     _fields_ = [("top_k", C.c_int), ("min_p", C.c_float), ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float),
@@ -85,6 +94,8 @@ SYMBOLS = [
     "q4_set_greedy_screen", "q4_get_greedy_screen", "q4_screen_candidates", "q4_greedy_screen_op",
     "q4_sampler_set_controls", "q4_sampler_get_controls", "q4_sampler_set_logit_bias", "q4_parse_sampling_controls", "q4_process_logits",
     "q4_guide_new", "q4_guide_delete", "q4_set_guide", "q4_get_guide", "q4_get_guide_states", "q4_guide_mask", "q4_tokenizer_piece",
+    "q4_resume_sequence", "q4_common_prefix", "q4_generate_ids_from", "q4_snapshot_new", "q4_snapshot_restore", "q4_snapshot_delete", "q4_snapshot_info",
+    "q4_snapshot_tokens", "q4_snapshot_export", "q4_snapshot_import", "q4_snapshot_check", "q4_copy_runs",
 ]
 
 _lib = None
@@ -235,6 +246,21 @@ def lib():
         L.q4_get_guide_states.argtypes = [vp, i, i, vp]
         L.q4_guide_mask.argtypes = [vp, i, vp, vp, vp, vp]
         L.q4_tokenizer_piece.argtypes = [vp, i, C.POINTER(C.c_void_p), C.POINTER(i)]
+    if hasattr(L, "q4_snapshot_new"):              # (older builds under tools/ab.py do not have it)
+        ll = C.c_longlong
+        L.q4_resume_sequence.argtypes = [C.POINTER(RunState), vp, i, i]
+        L.q4_common_prefix.argtypes = [vp, vp, i]
+        L.q4_generate_ids_from.argtypes = [vp, vp, vp, i, i, i, vp, C.POINTER(i), C.POINTER(C.c_double)]
+        L.q4_generate_ids_from.restype = C.c_double
+        L.q4_snapshot_new.argtypes = [C.POINTER(vp), vp, i]
+        L.q4_snapshot_restore.argtypes = [vp, vp]
+        L.q4_snapshot_delete.argtypes = [vp]
+        L.q4_snapshot_info.argtypes = [vp, C.POINTER(SnapshotInfo)]
+        L.q4_snapshot_tokens.argtypes = [vp, vp]
+        L.q4_snapshot_export.argtypes = [vp, vp, C.c_size_t]
+        L.q4_snapshot_import.argtypes = [C.POINTER(vp), vp, C.c_size_t]
+        L.q4_snapshot_check.argtypes = [vp, C.c_size_t, C.POINTER(SnapshotInfo)]
+        L.q4_copy_runs.argtypes = [vp, vp, ll, ll, ll, ll]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -399,6 +425,58 @@ def guide_mask(logits, n, guide, state_ring, tokens, pos):
     check(lib().q4_guide_mask(logits.ptr, n, guide.h, state_ring.ptr, tokens.ptr, pos.ptr))
 
 
+def copy_runs(dst, src, outer, dst_stride, src_stride, run_bytes, dst_offset=0, src_offset=0):
+    """q4_copy_runs over DevBufs: run r < outer moves run_bytes bytes from src + src_offset + r * src_stride to dst + dst_offset + r * dst_stride, in
+    stream order (q4_kv_copy.hip: the launch that takes and restores snapshots)."""
+    check(lib().q4_copy_runs(dst.ptr + dst_offset, src.ptr + src_offset, outer, dst_stride, src_stride, run_bytes))
+
+
+def snapshot_check(blob):
+    """q4_snapshot_check: validates a serialised snapshot without touching the GPU; the header's fields as a dict, or Q4Error"""
+    blob = bytes(blob)
+    info = SnapshotInfo()
+    check(lib().q4_snapshot_check(blob, len(blob), C.byref(info)))
+    return info.as_dict()
+
+
+class Snapshot:
+    """q4_snapshot: the K / V rows of positions [0, n_pos) of a model, packed on the device, with the tokens they were computed from. Immutable. Made by
+    Transformer.snapshot() or Snapshot.from_bytes(); given to Transformer.restore() or generate_ids(reuse=...) of any model of the same checkpoint."""
+
+    def __init__(self, handle):
+        self.h = handle
+        info = SnapshotInfo()
+        check(lib().q4_snapshot_info(self.h, C.byref(info)))
+        self.info = info.as_dict()
+        self.n_pos = info.n_pos
+        self.nbytes = info.device_bytes
+        self.tokens = np.empty(self.n_pos, dtype=np.int32)
+        check(lib().q4_snapshot_tokens(self.h, self.tokens.ctypes.data))
+
+    def to_bytes(self):
+        out = np.empty(self.info["export_bytes"], dtype=np.uint8)
+        check(lib().q4_snapshot_export(self.h, out.ctypes.data, out.nbytes))
+        return out.tobytes()
+
+    @classmethod
+    def from_bytes(cls, b):
+        b = bytes(b)
+        h = C.c_void_p()
+        check(lib().q4_snapshot_import(C.byref(h), b, len(b)))
+        return cls(h.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(lib().q4_snapshot_delete(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def greedy_screen_op(x, w, n, d, rms_w=None):
     """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
     tok, cand = C.c_int(), C.c_int()
@@ -523,19 +601,70 @@ class Transformer:
     def token(self, i):
         return lib().q4_shared_token(self.state, i)
 
-    def generate_ids(self, prompt_tokens, steps):
-        """generate() on token ids: returns (tokens ring [pos+1], tok/s, timed_tokens, seconds)."""
+    def generate_ids(self, prompt_tokens, steps, reuse=None):
+        """generate() on token ids: returns (tokens ring [pos+1], tok/s, timed_tokens, seconds). reuse=True: the steps of the prompt's common prefix with
+        what this model ran last are skipped, their K / V rows reused in place (common_prefix); reuse=<Snapshot>: the snapshot is restored first and the
+        run starts at the common prefix of the prompt and the snapshot's tokens. timed_tokens then counts the steps that ran."""
+        t = np.ascontiguousarray(prompt_tokens, dtype=np.int32)
+        if reuse is None or reuse is False:
+            return self.generate_ids_from(t, steps, 0)
+        if reuse is True:
+            return self.generate_ids_from(t, steps, self.common_prefix(t))
+        self.restore(reuse)
+        n = min(reuse.n_pos, t.shape[0] - 1)
+        differ = np.nonzero(reuse.tokens[:n] != t[:n])[0]
+        return self.generate_ids_from(t, steps, int(differ[0]) if differ.size else n)
+
+    def generate_ids_from(self, prompt_tokens, steps, start_pos):
+        """q4_generate_ids_from: generate_ids over K / V rows [0, start_pos) that are already in place (computed from prompt_tokens[:start_pos])."""
         t = np.ascontiguousarray(prompt_tokens, dtype=np.int32)
         if steps <= 0 or steps > self.config.seq_len:          # the C side clamps the same way (llama2_q4.cu:690)
             steps = self.config.seq_len
         out = np.zeros(steps + 2, dtype=np.int32)
         timed = C.c_int()
         secs = C.c_double()
-        tps = lib().q4_generate_ids(self.h, self.sampler, t.ctypes.data, t.shape[0], steps, out.ctypes.data, C.byref(timed),
-                                    C.byref(secs))
+        L = lib()
+        if start_pos == 0:
+            tps = L.q4_generate_ids(self.h, self.sampler, t.ctypes.data, t.shape[0], steps, out.ctypes.data, C.byref(timed), C.byref(secs))
+        else:
+            tps = L.q4_generate_ids_from(self.h, self.sampler, t.ctypes.data, t.shape[0], steps, int(start_pos), out.ctypes.data, C.byref(timed),
+                                         C.byref(secs))
         if tps < 0:
-            raise Q4Error("generate failed: " + lib().q4_last_error().decode())
-        return out[: timed.value + 2], tps, timed.value, secs.value
+            raise Q4Error("generate failed: " + L.q4_last_error().decode())
+        return out[: self.pos_after(timed.value, start_pos, t) + 1], tps, timed.value, secs.value
+
+    @staticmethod
+    def pos_after(timed, start_pos, prompt):
+        """the loop's final position from timed_tokens = pos - 1 - start (a prefix with an EOS inside runs from 0: q4_generate_ids_from)"""
+        start = 0 if start_pos > 1 and (np.asarray(prompt[1:start_pos]) == 2).any() else start_pos
+        return timed + 1 + start
+
+    def resume(self, tokens, start_pos):
+        """q4_resume_sequence: reset() that starts at start_pos over the K / V rows already there (computed from tokens[:start_pos])"""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        check(lib().q4_resume_sequence(self.state, t.ctypes.data, t.shape[0], int(start_pos)))
+
+    def common_prefix(self, tokens):
+        """q4_common_prefix: the largest start_pos that is safe for `tokens` as the model stands; synchronises"""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        n = lib().q4_common_prefix(self.h, t.ctypes.data, t.shape[0])
+        if n < 0:
+            check(-n)
+        return n
+
+    def snapshot(self, n_pos=None):
+        """q4_snapshot_new: a Snapshot of positions [0, n_pos); None: every position the device has completed"""
+        if n_pos is None:
+            check(lib().q4_stream_synchronize())
+            n_pos = self.pos()
+        h = C.c_void_p()
+        check(lib().q4_snapshot_new(C.byref(h), self.h, int(n_pos)))
+        return Snapshot(h.value)
+
+    def restore(self, snap):
+        """q4_snapshot_restore: the snapshot's rows back into positions [0, snap.n_pos), in stream order; the position does not move (follow with
+        resume() or generate_ids_from())"""
+        check(lib().q4_snapshot_restore(self.h, snap.h))
 
     def screen_candidates(self):
         """(last, max, total, steps) of the model's screened greedy steps (q4_screen_candidates); synchronises."""

@@ -163,9 +163,59 @@ static void die_on(int rc) {
 extern "C" __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
                                                                                     int copyLogits, Sampler* pSampler, int may_screen);
 
+// Q4_PROMPT_CACHE=FILE (generate mode): a serialised snapshot of an earlier run's prompt positions. Everything about it goes to stderr; a file that is
+// missing, fails q4_snapshot_check or belongs to another model is reported and ignored.
+static q4_snapshot* prompt_cache_load(const char* path, Transformer* t) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return nullptr;                                                        // absent: the run writes it
+    std::vector<char> blob;
+    long size = -1;
+    if (fseek(f, 0, SEEK_END) == 0) size = ftell(f);
+    bool ok = size > 0 && fseek(f, 0, SEEK_SET) == 0;
+    if (ok) {
+        blob.resize((size_t)size);
+        ok = fread(blob.data(), 1, blob.size(), f) == blob.size();
+    }
+    fclose(f);
+    q4_snapshot* snap = nullptr;
+    if (!ok || q4_snapshot_import(&snap, blob.data(), blob.size()) != Q4_OK) {
+        fprintf(stderr, "Q4_PROMPT_CACHE: %s is not a usable snapshot; ignored\n", path);
+        return nullptr;
+    }
+    if (q4_snapshot_restore(t, snap) != Q4_OK) {
+        fprintf(stderr, "Q4_PROMPT_CACHE: %s was taken from another model or K / V format; ignored\n", path);
+        q4_snapshot_delete(snap);
+        return nullptr;
+    }
+    return snap;
+}
+static void prompt_cache_save(const char* path, const Transformer* t, int n_pos) {
+    q4_snapshot* snap = nullptr;
+    struct q4_snapshot_info info;
+    if (q4_snapshot_new(&snap, t, n_pos) != Q4_OK) { fprintf(stderr, "Q4_PROMPT_CACHE: no snapshot of %d positions\n", n_pos); return; }
+    bool ok = q4_snapshot_info(snap, &info) == Q4_OK;
+    std::vector<char> blob;
+    if (ok) { blob.resize((size_t)info.export_bytes); ok = q4_snapshot_export(snap, blob.data(), blob.size()) == Q4_OK; }
+    q4_snapshot_delete(snap);
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE* f = ok ? fopen(tmp.c_str(), "wb") : nullptr;
+    ok = f && fwrite(blob.data(), 1, blob.size(), f) == blob.size();
+    if (f) ok = fclose(f) == 0 && ok;
+    if (ok) ok = rename(tmp.c_str(), path) == 0;
+    if (!ok) { fprintf(stderr, "Q4_PROMPT_CACHE: cannot write %s\n", path); remove(tmp.c_str()); }
+}
+
+static double generate_cached(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sampler, const char* prompt, int steps,
+                              int* timed_tokens_out, double* seconds_out, const char* cache_path);
 // generate(), llama2_q4.cu:436-492
 double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sampler, const char* prompt, int steps,
                    int* timed_tokens_out, double* seconds_out) {
+    return generate_cached(transformer, tokenizer, sampler, prompt, steps, timed_tokens_out, seconds_out, nullptr);
+}
+// ... with a prompt cache (null: none): the positions of the prompt's common prefix with the cached snapshot are not run; their pieces are printed from
+// the prompt's tokens, so stdout is what the full run prints
+static double generate_cached(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sampler, const char* prompt, int steps,
+                              int* timed_tokens_out, double* seconds_out, const char* cache_path) {
     if (prompt == NULL) prompt = "";
     int num_prompt_tokens = 0;
     int* prompt_tokens = (int*)malloc((strlen(prompt) + 3) * sizeof(int));
@@ -177,16 +227,40 @@ double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sample
         exit(EXIT_FAILURE);
     }
     RunState* state = &transformer->state;
+    // the prompt cache: restore, then skip the positions the snapshot's tokens share with the prompt -- none of them past an EOS, where the loop stops
+    int start_pos = 0, covered = 0;
+    if (cache_path) {
+        if (q4_snapshot* snap = prompt_cache_load(cache_path, transformer)) {
+            struct q4_snapshot_info info;
+            die_on(q4_snapshot_info(snap, &info));
+            std::vector<int> had(info.n_pos);
+            die_on(q4_snapshot_tokens(snap, had.data()));
+            while (covered < info.n_pos && covered < num_prompt_tokens && had[covered] == prompt_tokens[covered]) covered++;
+            start_pos = covered < num_prompt_tokens - 1 ? covered : num_prompt_tokens - 1;
+            if (start_pos > steps) start_pos = 0;
+            for (int i = 1; i < start_pos; i++)
+                if (prompt_tokens[i] == eos_token || prompt_tokens[i] >= transformer->config.vocab_size) start_pos = 0;
+            die_on(q4_snapshot_delete(snap));                                          // (synchronises: the rows are in place)
+        }
+    }
     const unsigned long long rng0 = sampler->rng_state;
     int timed_tokens = 0;
     double time = 0.0;
+    int ran_from = 0;
     for (int attempt = 0;; attempt++) {
         long start = time_in_ms();
         int next;
         int token = prompt_tokens[0];
-        int pos = 0;
-        die_on(q4_reset_sequence(state, prompt_tokens, num_prompt_tokens));            // :461-463
-        int queued = 0, group_start = 0;
+        int pos = attempt == 0 ? start_pos : 0;                                        // the retry after a time-out trusts no row
+        ran_from = pos;
+        if (pos == 0) die_on(q4_reset_sequence(state, prompt_tokens, num_prompt_tokens));   // :461-463
+        else die_on(q4_resume_sequence(state, prompt_tokens, num_prompt_tokens, pos));
+        for (int i = 1; i < pos; i++) {                                                // what the skipped steps' iterations print
+            safe_printf(q4_tokenizer_decode(tokenizer, token, prompt_tokens[i]));
+            token = prompt_tokens[i];
+        }
+        for (int i = 0; i < pos; i++) (void)random_f32(&sampler->rng_state);           // ... and their coins (one per step, sampler.h:45)
+        int queued = pos, group_start = pos;
         unsigned long long group_rng = sampler->rng_state;
         bool stopped = false;
         while (pos < steps) {
@@ -219,7 +293,7 @@ double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sample
             for (int i = group_start; i <= pos; i++) (void)random_f32(&sampler->rng_state);
         }
         time = (end - start) / 1000.0;
-        timed_tokens = pos - 1;
+        timed_tokens = pos - 1 - ran_from;                                             // (the steps this run executed)
         if (q4_handoff_status(state) == Q4_OK) break;
         // a bounded in-launch wait ran out: the text above is invalid. The library has cleared its hand-off state and dropped
         // to fusion level 1 (no in-launch waits): say so and generate again, once
@@ -228,6 +302,11 @@ double q4_generate(Transformer* transformer, struct Tokenizer* tokenizer, Sample
         sampler->rng_state = rng0;
     }
     printf("\nachieved tok/s: %f. Tokens: %d, seconds: %g\n", timed_tokens / time, timed_tokens, time);   // :489
+    if (cache_path) {      // keep the prompt's positions for the next run, unless the file already covers them
+        die_on(q4_stream_synchronize());
+        const int done = q4_shared_pos(state), n_save = done < num_prompt_tokens ? done : num_prompt_tokens;
+        if (n_save >= 1 && covered < n_save) prompt_cache_save(cache_path, transformer, n_save);
+    }
     free(prompt_tokens);
     if (timed_tokens_out) *timed_tokens_out = timed_tokens;
     if (seconds_out) *seconds_out = time;
@@ -478,7 +557,9 @@ int q4_main(int argc, char** argv) {
     if (a.perplexity) {
         q4_parse_dataset_and_compute_perplexity(a.dataset_path, tokenizer, &transformer, &sampler);
     } else if (strcmp(a.mode, "generate") == 0) {
-        q4_generate(&transformer, tokenizer, &sampler, a.prompt, steps, nullptr, nullptr);
+        // Q4_PROMPT_CACHE=FILE: the prompt's K / V rows are kept in FILE and reused by the next run that shares a prefix with it
+        const char* cache = getenv("Q4_PROMPT_CACHE");
+        generate_cached(&transformer, tokenizer, &sampler, a.prompt, steps, nullptr, nullptr, cache && *cache ? cache : nullptr);
     } else if (strcmp(a.mode, "chat") == 0) {
         q4_chat(&transformer, tokenizer, &sampler, a.prompt, a.system_prompt, steps);
     } else {

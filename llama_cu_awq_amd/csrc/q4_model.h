@@ -36,6 +36,8 @@ struct Model {
     int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)
     int guide_len = 0;
     void* guide_block = nullptr;    // what the guide launch reads: {table, ring, sizes}; captured graphs hold its address
+    unsigned long long fingerprint = 0;   // of the checkpoint file (q4_build_transformer): the header without seq_len, the file's size, its first and last 64 KiB; what a snapshot is matched by
+    bool rows_suspect = false;      // q4_handoff_status reported a time-out and no q4_reset_sequence has followed: the K / V rows below the position are not to be reused (q4_common_prefix)
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
 using Models = std::map<const RunState*, Model>;
@@ -74,5 +76,12 @@ int launch_guide_step(const Model* m, const Config* p, RunState* s);
 int guide_clear_positions(const Model* m, int pos, int nsteps);
 int guide_clear_ring(const Model* m);
 void guide_release(Model* m);
+// q4_kv_copy.hip. One launch that copies up to KV_COPY_MAX_RUNS strided runs on the launch stream: run r of an entry moves run_bytes bytes from
+// src + r * src_stride to dst + r * dst_stride, r < outer. Q4_ERR_ARG without a launch: a null pointer, a negative field, run_bytes above a stride when
+// outer > 1, source and destination ranges that overlap
+enum { KV_COPY_MAX_RUNS = 4 };
+struct CopyRun { void* dst; const void* src; long long outer, dst_stride, src_stride, run_bytes; };
+int copy_runs_check(const CopyRun& c);
+int launch_copy_runs(const CopyRun* runs, int n);
 
 }  // namespace q4

@@ -190,6 +190,33 @@ static double measure_kv_price(const Config* p, RunState* s, unsigned* sync) {
     return ticks_per_pos > nominal / 3.0 && ticks_per_pos < nominal * 3.0 ? ticks_per_pos : 0.0;
 }
 
+// What a snapshot of K / V rows is matched to its checkpoint by (q4_snapshot.hip): FNV-1a (64 bits) over the header with seq_len left out -- the rows of a
+// position do not depend on it, and a snapshot may be restored into a model of the same file opened with another context length --, the file's size, and
+// the file's first and last 64 KiB behind the header. Leaves the file positioned behind the header, where the loader expects it. 0 is never returned.
+static unsigned long long checkpoint_fingerprint(FILE* file, const Config* p) {
+    unsigned long long h = 0xcbf29ce484222325ull;
+    auto mix = [&h](const void* data, size_t n) {
+        const unsigned char* b = (const unsigned char*)data;
+        for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; }
+    };
+    Config c = *p;
+    c.seq_len = 0;
+    mix(&c, sizeof(c));
+    const long header = (long)sizeof(Config), window = 64 * 1024;
+    long size = 0;
+    if (fseek(file, 0, SEEK_END) == 0) size = ftell(file);
+    if (size < header) size = header;
+    const long long size64 = size;
+    mix(&size64, sizeof(size64));
+    std::vector<unsigned char> buf(window);
+    const long first = size - header < window ? size - header : window;
+    if (first > 0 && fseek(file, header, SEEK_SET) == 0) mix(buf.data(), fread(buf.data(), 1, (size_t)first, file));
+    const long last_at = size - window > header ? size - window : header;
+    if (size - last_at > 0 && fseek(file, last_at, SEEK_SET) == 0) mix(buf.data(), fread(buf.data(), 1, (size_t)(size - last_at), file));
+    (void)fseek(file, header, SEEK_SET);
+    return h ? h : 1;
+}
+
 // everything behind the header and the record's registration; the caller closes the file and, on failure, leaves through q4_free_transformer
 static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
     const Config* p = &t->config;
@@ -370,6 +397,7 @@ int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perple
     // the first allocation exists: the record is registered, and from here every failure leaves through q4_free_transformer
     Model& m = models()[&t->state] = Model{};
     m.kv_format = g_kv_format;
+    m.fingerprint = checkpoint_fingerprint(file, p);
     if (m.kv_format == Q4_KV_FP8 && !kv8_head_size_ok(p->dim / p->n_heads)) {
         snprintf(g_last_error, sizeof(g_last_error), "FP8 KV cache: head size %d is not supported (64, 128 or 256)", p->dim / p->n_heads);
         printf("%s\n", g_last_error);

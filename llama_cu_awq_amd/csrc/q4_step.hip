@@ -395,17 +395,48 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
 }
 
 // ---------------------------------------------------------------------------------------------------
-int q4_reset_sequence(RunState* s, const int* prompt_tokens, int num_prompt_tokens) {
-    Q4_HIP(hipMemsetAsync(s->pos, 0, sizeof(int), g_stream));                     // llama2_q4.cu:461
+// What q4_reset_sequence and q4_resume_sequence share: the position (the device's and SharedData::pos) becomes start_pos, the probation after a
+// time-out counts the sequence, the guide ring goes to NONE, the hand-off counters and granules are cleared, the ring receives the tokens.
+static int begin_sequence(RunState* s, const int* tokens, int num_tokens, int start_pos) {
+    if (start_pos == 0) Q4_HIP(hipMemsetAsync(s->pos, 0, sizeof(int), g_stream));                     // llama2_q4.cu:461
+    else Q4_HIP(hipMemcpyAsync(s->pos, &start_pos, sizeof(int), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
     if (g_rearm_after > 0 && --g_rearm_after == 0 && g_fusion == 1) { g_fusion = g_rearm_level; q4_reset_graphs(); }   // probation over
-    const Model* m = model_of(s);
+    Model* m = model_of(s);
     if (m && m->guide) Q4_TRY(guide_clear_ring(m));        // a new sequence starts at the guide's state 0
     Q4_TRY(clear_handoff_state(s, m, false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
     Q4_HIP(hipStreamSynchronize(g_stream));
-    s->shared_data->pos = 0;                                                       // :462
-    if (prompt_tokens && num_prompt_tokens > 0)
-        memcpy((void*)s->shared_data->tokens, prompt_tokens, sizeof(int) * num_prompt_tokens);   // :463
+    if (m && start_pos == 0) m->rows_suspect = false;      // every row the sequence reads is written again
+    s->shared_data->pos = start_pos;                                               // :462
+    if (tokens && num_tokens > 0)
+        memcpy((void*)s->shared_data->tokens, tokens, sizeof(int) * num_tokens);   // :463
     return Q4_OK;
+}
+int q4_reset_sequence(RunState* s, const int* prompt_tokens, int num_prompt_tokens) {
+    return begin_sequence(s, prompt_tokens, num_prompt_tokens, 0);
+}
+// q4_reset_sequence that starts at start_pos: the K / V rows below it stay (the caller's contract: they were computed from tokens[0 .. start_pos)).
+int q4_resume_sequence(RunState* s, const int* tokens, int num_tokens, int start_pos) {
+    if (!s || !s->pos || !s->shared_data || !tokens || num_tokens < 1 || num_tokens > Q4_MAX_SEQ_LEN || start_pos < 0 || start_pos > num_tokens - 1) return Q4_ERR_ARG;
+    const Model* m = model_of(s);
+    if (m) {      // the Config of a Transformer the library built sits in front of its RunState
+        const Transformer* t = reinterpret_cast<const Transformer*>(reinterpret_cast<const char*>(s) - offsetof(Transformer, state));
+        if (start_pos > t->config.seq_len) return Q4_ERR_ARG;
+    }
+    return begin_sequence(s, tokens, num_tokens, start_pos);
+}
+// The largest start_pos q4_resume_sequence may be given for `tokens` as the model stands: the common prefix of tokens and the ring, no longer than the
+// positions the device has completed, nor than num_tokens - 1 (the last prompt token always runs: it produces the logits).
+int q4_common_prefix(const Transformer* t, const int* tokens, int num_tokens) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !tokens || num_tokens < 1) return -Q4_ERR_ARG;
+    if (hipStreamSynchronize(g_stream) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (m->rows_suspect) return 0;
+    int limit = t->state.shared_data->pos;
+    if (limit > num_tokens - 1) limit = num_tokens - 1;
+    if (limit > t->config.seq_len) limit = t->config.seq_len;
+    int n = 0;
+    while (n < limit && t->state.shared_data->tokens[n] == tokens[n]) n++;
+    return n;
 }
 int q4_shared_pos(const RunState* s) { return s->shared_data->pos; }
 
@@ -438,11 +469,12 @@ static int group_may_screen(int pos, int k, int steps) { return pos + k < steps 
 // once with q4_set_fusion(level).
 int q4_handoff_status(const RunState* s) {
     Q4_HIP(hipStreamSynchronize(g_stream));
-    const Model* m = model_of(s);
+    Model* m = model_of(s);
     if (!m || !m->sync) return Q4_OK;
     unsigned flag = 0;
     Q4_HIP(hipMemcpy(&flag, m->sync + SYNC_ERROR, sizeof(flag), hipMemcpyDeviceToHost));
     if (flag) {
+        m->rows_suspect = true;     // until the next q4_reset_sequence: nothing computed since the time-out may be kept (q4_common_prefix)
         Q4_TRY(clear_handoff_state(s, m, true));
         g_handoff_timeouts++;
         if (g_fusion >= 3) {    // one transient stall (a profiler attaching, a co-tenant) must not cost every later sequence its 3 %
@@ -481,15 +513,31 @@ int q4_shared_token(const RunState* s, int index) { return s->shared_data->token
 // launch step `pos`, then look at the token produced by the PREVIOUS step; same throughput rule (pos-1)/elapsed.
 double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps,
                        int* out_tokens, int* timed_tokens_out, double* seconds_out) {
-    if (num_prompt_tokens < 1) return -1.0;
+    return q4_generate_ids_from(t, sampler, prompt_tokens, num_prompt_tokens, steps, 0, out_tokens, timed_tokens_out, seconds_out);
+}
+// ... starting at start_pos, over K / V rows [0, start_pos) that are already in place (q4_resume_sequence's contract). The loop draws one coin per step
+// whether or not the step samples, so the skipped steps' coins are drawn and discarded first: with the same seed a resumed sampled generation produces
+// the full one's tokens, and a reused Sampler stands where the full run leaves it.
+double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos,
+                            int* out_tokens, int* timed_tokens_out, double* seconds_out) {
+    if (!t || !sampler || !prompt_tokens || num_prompt_tokens < 1) return -1.0;
     if (steps <= 0 || steps > t->config.seq_len) steps = t->config.seq_len;        // :690
+    if (start_pos < 0 || start_pos > num_prompt_tokens - 1 || start_pos > t->config.seq_len) {
+        snprintf(g_last_error, sizeof(g_last_error), "q4_generate_ids_from: start_pos %d outside [0, %d] (%s)", start_pos, num_prompt_tokens - 1, q4_status_string(Q4_ERR_ARG));
+        return -1.0;
+    }
+    // the full loop stops at the first EOS it meets in the ring behind index 0, a prompt's included: a prefix that holds one is not skipped
+    for (int i = 1; i < start_pos; i++)
+        if (prompt_tokens[i] == 2) start_pos = 0;
     const unsigned long long rng0 = sampler->rng_state;
     for (int attempt = 0;; attempt++) {
         struct timespec t0, t1;
         clock_gettime(CLOCK_MONOTONIC, &t0);
-        int pos = 0, queued = 0, group_start = 0;
+        const int start = attempt == 0 ? start_pos : 0;      // the retry after a time-out trusts no row
+        int pos = start, queued = start, group_start = start;
+        if (start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start)) return -1.0;
+        for (int i = 0; i < start; i++) (void)random_f32(&sampler->rng_state);
         unsigned long long group_rng = sampler->rng_state;   // sampler state in front of the group of steps queued last
-        if (q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens)) return -1.0;
         bool stopped = false;
         while (pos < steps) {
             // the reference synchronises and then launches step `pos` (:468-470); here the launch goes out first, queued
@@ -519,7 +567,7 @@ double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_token
             for (int i = group_start; i <= pos; i++) (void)random_f32(&sampler->rng_state);
         }
         const double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
-        const int timed_tokens = pos - 1;                                              // :488
+        const int timed_tokens = pos - 1 - start;                                      // :488, over the steps this call ran
         if (q4_handoff_status(&t->state)) {     // a timed-out in-launch wait: the library is at fusion level 1 now, state cleared
             if (attempt == 0) { sampler->rng_state = rng0; continue; }                 // redo the whole sequence once
             return -1.0;
