@@ -483,6 +483,52 @@ int q4_snapshot_check(const void* host, size_t bytes, struct q4_snapshot_info* o
  * byte of the first run to last byte of the last) that overlap. */
 int q4_copy_runs(void* dst, const void* src, long long outer, long long dst_stride, long long src_stride, long long run_bytes);
 
+/* ---- context shift (q4_kv_shift.hip; not in the reference) ----------------------------------------
+ * A sequence ends at seq_len: the K / V cache has that many rows. Context shift (the StreamingLLM / llama.cpp operation) keeps the first n_keep
+ * positions, discards the n_discard = D positions behind them, slides everything above down by D and goes on at position n_pos - D: V rows move bit
+ * for bit, K rows -- stored rotated -- are rotated by -D positions on the way, in ONE in-place launch off the per-token path; no weight is read.
+ * The model then attends over rows that were computed WITH the discarded tokens in view: this is NOT what re-ingesting the surviving tokens gives.
+ * What is guaranteed is the operation: deterministic, and specified exactly. With (c, s) = row D of the model's rotation table at pair index i,
+ * a = float(k[i]), b = float(k[i + head_size/2]), every operation one IEEE fp32 operation:
+ *   k'[i] = half_rne((a * c) + (b * s))      k'[i + head_size/2] = half_rne((b * c) - (a * s))
+ * An FP8 K row is dequantised first (byte * 2^e, exactly fp16) and its rotated halves quantised again by the format's rule (new exponent, new
+ * bytes); V bytes and exponents move as they are. Every shift therefore rounds the moved K rows once more (twice for FP8: to half and to e4m3), and
+ * repeated shifts compound that. Opt-in: without these calls and without a setting, the launches, graphs, bits and return values are unchanged. */
+/* Synchronises the q4 stream. With K0 = n_keep, D = n_discard, M = n_pos - K0 - D (M = 0: a pure truncation): K / V rows (FP8: and exponents) K0 + j <-
+ * K0 + D + j, j < M, in every layer, K rotated as above; ring tokens[K0 + j] <- tokens[K0 + D + j], j < n_ring - K0 - D (n_ring covers the token the
+ * last step chose and prompt tokens that still wait behind it); the device position and SharedData::pos become n_pos - D; with a guide attached the
+ * state ring moves like the rows and entry n_pos - D - 1 receives the old entry n_pos - 1 (the automaton continues; nothing is cleared); with
+ * log-probability records on they move like the rows (record p still describes the token at ring index p + 1); the hand-off counters and granules are
+ * cleared as by q4_resume_sequence -- no probation countdown, no guide reset, rows_suspect stays. Untouched: rows and ring entries below K0, rows at
+ * or above n_pos, the coin ring, the sampler, the logits, an FP8 model's staging rows, captured graphs. Rows [n_pos - D, n_pos) are unspecified
+ * afterwards. Until the next q4_reset_sequence q4_common_prefix returns at most the smallest n_keep the sequence was shifted at: the rows above are no
+ * longer "computed from tokens[0 .. start_pos)". q4_snapshot_new stays allowed: a snapshot of a shifted sequence restores that sequence's state, not
+ * the state a fresh run over its tokens would reach.
+ * Q4_ERR_ARG, nothing touched, no launch: a Transformer the library did not build or whose rows are suspect (q4_common_prefix); unless 0 <= n_keep,
+ * 1 <= n_discard, n_keep + n_discard <= n_pos <= min(SharedData::pos, seq_len) and n_pos + 1 <= n_ring <= Q4_MAX_SEQ_LEN. (n_pos is explicit for the
+ * reason q4_snapshot_new's is: after a stop at EOS up to Q4_MULTI_STEPS - 1 surplus steps may have run.) */
+int q4_shift_context(Transformer* t, int n_pos, int n_keep, int n_discard, int n_ring);
+/* The setting the library's own loops follow: n_discard = 0 is off (default). On: q4_generate_ids / q4_generate_ids_from / q4_generate accept steps
+ * above seq_len, up to Q4_MAX_SEQ_LEN - 1; when the next step would run at position seq_len the loop waits for what is queued, calls
+ * q4_shift_context(t, seq_len, n_keep, n_discard, seq_len + 1) and continues; out_tokens (steps + 1 ints) receives the whole history, evicted tokens
+ * included; the prompt must fit as before; one coin is drawn per step; the shift's time is inside `seconds`; after a shift a hand-off time-out is not
+ * retried (-1.0, q4_last_error set). q4_chat shifts before any step whose position would be seq_len and `steps` bounds the steps it runs.
+ * Q4_ERR_ARG: a negative value, n_keep + n_discard > seq_len, a Transformer the library did not build. */
+int q4_set_context_shift(Transformer* t, int n_keep, int n_discard);
+int q4_get_context_shift(const Transformer* t, int* n_keep, int* n_discard);
+/* "keep=4,discard=256": both keys optional in any order, keep defaults to 0. Q4_ERR_ARG and the outputs untouched: an unknown key, a malformed or
+ * negative number, discard missing or 0. */
+int q4_parse_context_shift(const char* text, int* n_keep, int* n_discard);
+/* Synchronises; row `pos` of the model's own rotation table: head_size/2 (cos, sin) pairs of floats. Q4_ERR_ARG: pos outside [0, seq_len). */
+int q4_get_rope_row(const Transformer* t, int pos, float* cos_sin);
+/* Op-level form of the launch, on the q4 stream; device pointers. k, v: [n_layers][seq_len][n_kv_heads * head_size] halves (Q4_KV_FP16) or e4m3 bytes
+ * (Q4_KV_FP8, then k_exp, v_exp: [n_layers][n_kv_heads][seq_len] exponent bytes); cos_sin: [head_size/2] (cos, sin) pairs, the rotation of n_discard
+ * positions. Q4_ERR_ARG without a launch: a null k, v or cos_sin, null exponents or a base that is not 16-byte aligned with Q4_KV_FP8, a bad format,
+ * a non-positive count (n_keep may be 0), an odd head size, an FP8 head size outside {64, 128, 256}, n_keep + n_discard > n_pos, n_pos > seq_len.
+ * n_pos == n_keep + n_discard launches nothing. */
+int q4_kv_shift(void* k, void* v, int8_t* k_exp, int8_t* v_exp, int kv_format, int n_layers, int seq_len, int n_kv_heads, int head_size,
+                int n_pos, int n_keep, int n_discard, const float* cos_sin);
+
 /* build_transformer(Transformer*, char* checkpoint_path, bool perplexity) llama2_q4.cu:408-426 (prints the
  * same "Model params" / "Loading Weights... done!" lines unless quiet), free_transformer :428-432 */
 int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perplexity);

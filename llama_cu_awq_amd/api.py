@@ -96,6 +96,7 @@ SYMBOLS = [
     "q4_guide_new", "q4_guide_delete", "q4_set_guide", "q4_get_guide", "q4_get_guide_states", "q4_guide_mask", "q4_tokenizer_piece",
     "q4_resume_sequence", "q4_common_prefix", "q4_generate_ids_from", "q4_snapshot_new", "q4_snapshot_restore", "q4_snapshot_delete", "q4_snapshot_info",
     "q4_snapshot_tokens", "q4_snapshot_export", "q4_snapshot_import", "q4_snapshot_check", "q4_copy_runs",
+    "q4_shift_context", "q4_set_context_shift", "q4_get_context_shift", "q4_parse_context_shift", "q4_get_rope_row", "q4_kv_shift",
 ]
 
 _lib = None
@@ -261,6 +262,13 @@ def lib():
         L.q4_snapshot_import.argtypes = [C.POINTER(vp), vp, C.c_size_t]
         L.q4_snapshot_check.argtypes = [vp, C.c_size_t, C.POINTER(SnapshotInfo)]
         L.q4_copy_runs.argtypes = [vp, vp, ll, ll, ll, ll]
+    if hasattr(L, "q4_shift_context"):             # (older builds under tools/ab.py do not have it)
+        L.q4_shift_context.argtypes = [vp, i, i, i, i]
+        L.q4_set_context_shift.argtypes = [vp, i, i]
+        L.q4_get_context_shift.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
+        L.q4_parse_context_shift.argtypes = [C.c_char_p, C.POINTER(i), C.POINTER(i)]
+        L.q4_get_rope_row.argtypes = [vp, i, vp]
+        L.q4_kv_shift.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -508,7 +516,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None):
+                 logit_bias=None, guide=None, context_shift=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -546,6 +554,8 @@ class Transformer:
                 self.set_logit_bias(logit_bias)
             if guide is not None:
                 self.set_guide(guide)
+            if context_shift is not None:
+                self.set_context_shift(*context_shift)
         except Exception:
             self.close()
             raise
@@ -618,8 +628,10 @@ class Transformer:
     def generate_ids_from(self, prompt_tokens, steps, start_pos):
         """q4_generate_ids_from: generate_ids over K / V rows [0, start_pos) that are already in place (computed from prompt_tokens[:start_pos])."""
         t = np.ascontiguousarray(prompt_tokens, dtype=np.int32)
-        if steps <= 0 or steps > self.config.seq_len:          # the C side clamps the same way (llama2_q4.cu:690)
+        limit = MAX_SEQ_LEN - 1 if self.context_shift()[1] > 0 else self.config.seq_len      # (a model that shifts generates past seq_len)
+        if steps <= 0:                                          # the C side clamps the same way (llama2_q4.cu:690)
             steps = self.config.seq_len
+        steps = min(steps, limit)
         out = np.zeros(steps + 2, dtype=np.int32)
         timed = C.c_int()
         secs = C.c_double()
@@ -651,6 +663,36 @@ class Transformer:
         if n < 0:
             check(-n)
         return n
+
+    def set_context_shift(self, n_keep, n_discard):
+        """q4_set_context_shift: generate_ids (and the library's other token loops) then shift at seq_len instead of stopping -- keep the first n_keep
+        positions, discard the n_discard behind them, slide the rest down -- and `steps` may pass seq_len. n_discard = 0: off."""
+        check(lib().q4_set_context_shift(self.h, int(n_keep), int(n_discard)))
+
+    def context_shift(self):
+        """(n_keep, n_discard) of the setting; n_discard 0: off"""
+        L = lib()
+        if not hasattr(L, "q4_get_context_shift"):             # (older builds under tools/ab.py do not have it)
+            return 0, 0
+        k, d = C.c_int(), C.c_int()
+        check(L.q4_get_context_shift(self.h, C.byref(k), C.byref(d)))
+        return k.value, d.value
+
+    def shift_context(self, n_keep, n_discard, n_pos=None, n_ring=None):
+        """q4_shift_context: K / V rows, ring tokens, guide states and log-probability records of positions [n_keep + n_discard, n_pos) move down by
+        n_discard, the K rows rotated by as many positions, in place; the position becomes n_pos - n_discard. n_pos None: every completed position;
+        n_ring None: n_pos + 1 (the ring up to the token the last step chose). The rows then hold what was computed with the discarded tokens in view:
+        not what ingesting the surviving tokens would give. Synchronises."""
+        if n_pos is None:
+            check(lib().q4_stream_synchronize())
+            n_pos = min(self.pos(), self.config.seq_len)
+        check(lib().q4_shift_context(self.h, int(n_pos), int(n_keep), int(n_discard), int(n_pos + 1 if n_ring is None else n_ring)))
+
+    def rope_row(self, pos):
+        """row `pos` of the model's rotation table: [head_size/2, 2] float32 (cos, sin); synchronises"""
+        out = np.empty((self.config.dim // self.config.n_heads // 2, 2), dtype=np.float32)
+        check(lib().q4_get_rope_row(self.h, int(pos), out.ctypes.data))
+        return out
 
     def snapshot(self, n_pos=None):
         """q4_snapshot_new: a Snapshot of positions [0, n_pos); None: every position the device has completed"""

@@ -247,12 +247,17 @@ static double generate_cached(Transformer* transformer, struct Tokenizer* tokeni
     int timed_tokens = 0;
     double time = 0.0;
     int ran_from = 0;
+    // q4_set_context_shift: at seq_len the rows slide instead of the loop ending; `pos` counts steps, the device runs step pos at position pos - off
+    int shift_keep = 0, shift_discard = 0, off = 0;
+    (void)q4_get_context_shift(transformer, &shift_keep, &shift_discard);
+    const int seq_len = transformer->config.seq_len;
     for (int attempt = 0;; attempt++) {
         long start = time_in_ms();
         int next;
         int token = prompt_tokens[0];
         int pos = attempt == 0 ? start_pos : 0;                                        // the retry after a time-out trusts no row
         ran_from = pos;
+        off = 0;
         if (pos == 0) die_on(q4_reset_sequence(state, prompt_tokens, num_prompt_tokens));   // :461-463
         else die_on(q4_resume_sequence(state, prompt_tokens, num_prompt_tokens, pos));
         for (int i = 1; i < pos; i++) {                                                // what the skipped steps' iterations print
@@ -268,16 +273,20 @@ static double generate_cached(Transformer* transformer, struct Tokenizer* tokeni
             // launch, :468-470) -- same device order, the GPU never idles between tokens; greedy steps inside one bin go out
             // Q4_MULTI_STEPS at a time
             if (pos >= queued) {
-                const int k = q4_steps_that_fit(pos, num_prompt_tokens, steps, &transformer->config, sampler);
+                if (shift_discard > 0 && pos - off == seq_len) {                       // (synchronises: everything queued has finished)
+                    die_on(q4_shift_context(transformer, seq_len, shift_keep, shift_discard, seq_len + 1));
+                    off += shift_discard;
+                }
+                const int k = q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &transformer->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
                 // (every group but the one with the generation's last step may screen its classifier: nobody reads those logits)
-                die_on(run_transformer_steps_screenable(pos, k, pos >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + k < steps));
+                die_on(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + k < steps));
                 queued = pos + k;
             }
-            die_on(q4_wait_pos(state, pos));                                           // :468
+            die_on(q4_wait_pos(state, pos - off));                                     // :468
             if (pos > 0) {
-                next = q4_shared_token(state, pos);                                    // output token of the previous iteration
+                next = q4_shared_token(state, pos - off);                              // output token of the previous iteration
                 if (next >= transformer->config.vocab_size) next = 0;                  // :474
                 const char* piece = q4_tokenizer_decode(tokenizer, token, next);
                 safe_printf(piece);
@@ -298,11 +307,12 @@ static double generate_cached(Transformer* transformer, struct Tokenizer* tokeni
         // a bounded in-launch wait ran out: the text above is invalid. The library has cleared its hand-off state and dropped
         // to fusion level 1 (no in-launch waits): say so and generate again, once
         if (attempt > 0) die_on(Q4_ERR_HIP);
+        if (off > 0) die_on(Q4_ERR_HIP);                                               // (a shifted sequence is not generated again)
         printf("\n[%s -- generating again]\n", q4_last_error());
         sampler->rng_state = rng0;
     }
     printf("\nachieved tok/s: %f. Tokens: %d, seconds: %g\n", timed_tokens / time, timed_tokens, time);   // :489
-    if (cache_path) {      // keep the prompt's positions for the next run, unless the file already covers them
+    if (cache_path && off == 0) {      // keep the prompt's positions for the next run, unless the file already covers them
         die_on(q4_stream_synchronize());
         const int done = q4_shared_pos(state), n_save = done < num_prompt_tokens ? done : num_prompt_tokens;
         if (n_save >= 1 && covered < n_save) prompt_cache_save(cache_path, transformer, n_save);
@@ -337,6 +347,9 @@ void q4_chat(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sam
     int token = 0;
     int pos = 0;
     RunState* state = &transformer->state;
+    // q4_set_context_shift: `pos` counts steps (what `steps` bounds); the ring index and the step's position are the device's, which a shift lowers
+    int shift_keep = 0, shift_discard = 0;
+    (void)q4_get_context_shift(transformer, &shift_keep, &shift_discard);
     system_prompt[0] = '\0';
     die_on(q4_reset_sequence(state, nullptr, 0));                                  // :526-527
     while (pos < steps) {
@@ -358,15 +371,22 @@ void q4_chat(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sam
             user_turn = 0;
             printf("Assistant: ");
             die_on(q4_stream_synchronize());
-            for (int i = 0; i < num_prompt_tokens && pos + i < Q4_MAX_SEQ_LEN; i++)
-                transformer->state.shared_data->tokens[pos + i] = prompt_tokens[i];   // :573
+            const int at = q4_shared_pos(state);
+            for (int i = 0; i < num_prompt_tokens && at + i < Q4_MAX_SEQ_LEN; i++)
+                transformer->state.shared_data->tokens[at + i] = prompt_tokens[i];    // :573
         }
         die_on(q4_stream_synchronize());                                           // :578
+        if (shift_discard > 0 && q4_shared_pos(state) == transformer->config.seq_len) {   // the ring behind the position: the token the last step chose, or the turn's tokens that still wait
+            const int waiting = num_prompt_tokens - user_idx > 1 ? num_prompt_tokens - user_idx : 1;
+            const int n_ring = transformer->config.seq_len + waiting < Q4_MAX_SEQ_LEN ? transformer->config.seq_len + waiting : Q4_MAX_SEQ_LEN;
+            die_on(q4_shift_context(transformer, transformer->config.seq_len, shift_keep, shift_discard, n_ring));
+        }
+        const int at = q4_shared_pos(state);
         // (q4_run_transformer's step; a greedy generating step may screen its classifier: only its token is read. Not the last one.)
-        die_on(run_transformer_steps_screenable(q4_shared_pos(state), 1, user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + 1 < steps));
+        die_on(run_transformer_steps_screenable(at, 1, user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + 1 < steps));
         user_idx++;
         if (user_idx > 0) {
-            next = q4_shared_token(state, pos);                                    // :584
+            next = q4_shared_token(state, at);                                     // :584
             if (next == eos_token) {
                 user_turn = 1;
                 printf("\n");
@@ -541,8 +561,19 @@ int q4_main(int argc, char** argv) {
     Transformer transformer;
     int rc = q4_build_transformer(&transformer, a.checkpoint_path, a.perplexity);
     if (rc) exit(rc == Q4_ERR_IO ? 1 : EXIT_FAILURE);
+    // ... and the context shift (q4_parse_context_shift): Q4_CONTEXT_SHIFT="keep=4,discard=256"; with it -n may pass seq_len
+    const char* shift = getenv("Q4_CONTEXT_SHIFT");
+    const bool shifting = shift && *shift;
+    if (shifting) {
+        int keep = 0, discard = 0;
+        if (q4_parse_context_shift(shift, &keep, &discard) || q4_set_context_shift(&transformer, keep, discard)) {
+            fprintf(stderr, "Q4_CONTEXT_SHIFT: cannot use '%s' (keys: keep, discard; discard >= 1, keep + discard <= %d; e.g. keep=4,discard=256)\n", shift, transformer.config.seq_len);
+            exit(EXIT_FAILURE);
+        }
+    }
     int steps = a.steps;
-    if (steps <= 0 || steps > transformer.config.seq_len) steps = transformer.config.seq_len;   // :690
+    if (steps <= 0 || (!shifting && steps > transformer.config.seq_len)) steps = transformer.config.seq_len;   // :690
+    if (shifting && steps > Q4_MAX_SEQ_LEN - 1) steps = Q4_MAX_SEQ_LEN - 1;
 
     struct Tokenizer* tokenizer = q4_tokenizer_new(a.tokenizer_path, transformer.config.vocab_size);
     if (!tokenizer) exit(EXIT_FAILURE);

@@ -37,6 +37,8 @@ struct Model {
     int guide_len = 0;
     void* guide_block = nullptr;    // what the guide launch reads: {table, ring, sizes}; captured graphs hold its address
     unsigned long long fingerprint = 0;   // of the checkpoint file (q4_build_transformer): the header without seq_len, the file's size, its first and last 64 KiB; what a snapshot is matched by
+    int shift_keep = 0, shift_discard = 0;   // q4_set_context_shift: what the library's own token loops shift by at seq_len; discard 0: off
+    int shifted_keep = -1;          // the smallest n_keep of the q4_shift_context calls since the last q4_reset_sequence, -1: none -- rows above it are not "computed from the ring's tokens" (q4_common_prefix)
     bool rows_suspect = false;      // q4_handoff_status reported a time-out and no q4_reset_sequence has followed: the K / V rows below the position are not to be reused (q4_common_prefix)
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
@@ -83,5 +85,9 @@ enum { KV_COPY_MAX_RUNS = 4 };
 struct CopyRun { void* dst; const void* src; long long outer, dst_stride, src_stride, run_bytes; };
 int copy_runs_check(const CopyRun& c);
 int launch_copy_runs(const CopyRun* runs, int n);
+// q4_kv_shift.hip. One in-place launch on the launch stream: rows [n_keep + n_discard, n_pos) of every layer move down by n_discard, K rows rotated by
+// cos_sin ([head_size/2] (cos, sin) pairs on the device). The argument checks of q4_kv_shift (llama2_q4.h); n_pos == n_keep + n_discard launches nothing
+int launch_kv_shift(void* k, void* v, int8_t* k_exp, int8_t* v_exp, int kv_format, int n_layers, int seq_len, int n_kv_heads, int head_size, int n_pos,
+                    int n_keep, int n_discard, const float* cos_sin);
 
 }  // namespace q4

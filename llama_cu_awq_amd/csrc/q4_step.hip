@@ -8,6 +8,7 @@
 #include <string.h>
 #include <time.h>
 #include <stddef.h>
+#include <vector>
 #include "q4_model.h"
 
 namespace q4 {
@@ -405,7 +406,7 @@ static int begin_sequence(RunState* s, const int* tokens, int num_tokens, int st
     if (m && m->guide) Q4_TRY(guide_clear_ring(m));        // a new sequence starts at the guide's state 0
     Q4_TRY(clear_handoff_state(s, m, false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
     Q4_HIP(hipStreamSynchronize(g_stream));
-    if (m && start_pos == 0) m->rows_suspect = false;      // every row the sequence reads is written again
+    if (m && start_pos == 0) { m->rows_suspect = false; m->shifted_keep = -1; }   // every row the sequence reads is written again
     s->shared_data->pos = start_pos;                                               // :462
     if (tokens && num_tokens > 0)
         memcpy((void*)s->shared_data->tokens, tokens, sizeof(int) * num_tokens);   // :463
@@ -434,11 +435,114 @@ int q4_common_prefix(const Transformer* t, const int* tokens, int num_tokens) {
     int limit = t->state.shared_data->pos;
     if (limit > num_tokens - 1) limit = num_tokens - 1;
     if (limit > t->config.seq_len) limit = t->config.seq_len;
+    if (m->shifted_keep >= 0 && limit > m->shifted_keep) limit = m->shifted_keep;   // q4_shift_context: the rows above were computed with discarded tokens in view
     int n = 0;
     while (n < limit && t->state.shared_data->tokens[n] == tokens[n]) n++;
     return n;
 }
 int q4_shared_pos(const RunState* s) { return s->shared_data->pos; }
+
+// ---------------------------------------------------------------------------------------------------
+// context shift (q4_kv_shift.hip holds the launch; llama2_q4.h the contract). Not in the reference.
+// rows [first, first + n) of a small device ring of `width` bytes per row, moved down by D through the host (the call synchronises anyway)
+static int shift_ring_rows(void* ring, size_t width, int first, int n, int D) {
+    if (!ring || n <= 0 || width == 0) return Q4_OK;
+    std::vector<char> host((size_t)n * width);
+    Q4_HIP(hipMemcpy(host.data(), (char*)ring + (size_t)first * width, host.size(), hipMemcpyDeviceToHost));
+    Q4_HIP(hipMemcpy((char*)ring + (size_t)(first - D) * width, host.data(), host.size(), hipMemcpyHostToDevice));
+    return Q4_OK;
+}
+int q4_shift_context(Transformer* t, int n_pos, int n_keep, int n_discard, int n_ring) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const Config* p = &t->config;
+    RunState* s = &t->state;
+    const int done = s->shared_data->pos;
+    if (m->rows_suspect || n_keep < 0 || n_discard < 1 || (long long)n_keep + n_discard > n_pos || n_pos > done || n_pos > p->seq_len ||
+        n_ring < n_pos + 1 || n_ring > Q4_MAX_SEQ_LEN)
+        return Q4_ERR_ARG;
+    const int head_size = p->dim / p->n_heads, D = n_discard, first = n_keep + D, M = n_pos - first;
+    if (M > 0) {
+        if (!m->rope_table) {
+            snprintf(g_last_error, sizeof(g_last_error), "q4_shift_context: the model has no rotation table");
+            return Q4_ERR_UNSUPPORTED_SIZE;
+        }
+        Q4_TRY(launch_kv_shift(s->key_cache, s->value_cache, m->k_exp, m->v_exp, m->kv_format, p->n_layers, p->seq_len, p->n_kv_heads, head_size, n_pos,
+                               n_keep, D, (const float*)(m->rope_table + (size_t)D * (head_size / 2))));
+    }
+    const int new_pos = n_pos - D;
+    Q4_HIP(hipMemcpyAsync(s->pos, &new_pos, sizeof(int), hipMemcpyHostToDevice, g_stream));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    if (m->guide && m->guide_state) {
+        int last = Q4_GUIDE_NONE;
+        Q4_HIP(hipMemcpy(&last, m->guide_state + n_pos - 1, sizeof(int), hipMemcpyDeviceToHost));
+        Q4_TRY(shift_ring_rows(m->guide_state, sizeof(int), first, M, D));
+        if (new_pos >= 1) Q4_HIP(hipMemcpy(m->guide_state + new_pos - 1, &last, sizeof(int), hipMemcpyHostToDevice));   // (M > 0: the moved entry already)
+    }
+    if (m->logprobs_k >= 0) {
+        const size_t K = (size_t)m->logprobs_k;
+        Q4_TRY(shift_ring_rows(m->lp_lse, sizeof(float), first, M, D));
+        Q4_TRY(shift_ring_rows(m->lp_token, sizeof(float), first, M, D));
+        Q4_TRY(shift_ring_rows(m->lp_ids, K * sizeof(int), first, M, D));
+        Q4_TRY(shift_ring_rows(m->lp_top, K * sizeof(float), first, M, D));
+    }
+    Q4_TRY(clear_handoff_state(s, m, false));     // as after a roll-back: counters and granules; the error word stays for q4_handoff_status
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    int* ring = (int*)s->shared_data->tokens;
+    memmove(ring + n_keep, ring + first, (size_t)(n_ring - first) * sizeof(int));
+    s->shared_data->pos = new_pos;
+    if (m->shifted_keep < 0 || n_keep < m->shifted_keep) m->shifted_keep = n_keep;
+    return Q4_OK;
+}
+int q4_set_context_shift(Transformer* t, int n_keep, int n_discard) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || n_keep < 0 || n_discard < 0 || (long long)n_keep + n_discard > t->config.seq_len) return Q4_ERR_ARG;
+    m->shift_keep = n_keep;
+    m->shift_discard = n_discard;
+    return Q4_OK;
+}
+int q4_get_context_shift(const Transformer* t, int* n_keep, int* n_discard) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    if (n_keep) *n_keep = m->shift_keep;
+    if (n_discard) *n_discard = m->shift_discard;
+    return Q4_OK;
+}
+int q4_parse_context_shift(const char* text, int* n_keep, int* n_discard) {
+    if (!text || !n_keep || !n_discard) return Q4_ERR_ARG;
+    long keep = 0, discard = 0;
+    const char* p = text;
+    while (*p) {
+        const char* eq = strchr(p, '=');
+        const char* end = strchr(p, ',');
+        if (!end) end = p + strlen(p);
+        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
+        char key[32], val[32];
+        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
+        memcpy(key, p, eq - p); key[eq - p] = 0;
+        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        long* dst = !strcmp(key, "keep") ? &keep : !strcmp(key, "discard") ? &discard : nullptr;
+        if (!dst || val[0] < '0' || val[0] > '9') return Q4_ERR_ARG;          // (no sign, no leading blank)
+        char* rest = nullptr;
+        *dst = strtol(val, &rest, 10);
+        if (*rest || *dst > Q4_MAX_SEQ_LEN) return Q4_ERR_ARG;
+        p = *end ? end + 1 : end;
+        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
+    }
+    if (discard < 1) return Q4_ERR_ARG;                        // off is the absence of a setting, not a text
+    *n_keep = (int)keep;
+    *n_discard = (int)discard;
+    return Q4_OK;
+}
+int q4_get_rope_row(const Transformer* t, int pos, float* cos_sin) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !m->rope_table || !cos_sin || pos < 0 || pos >= t->config.seq_len) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const size_t hp = (size_t)(t->config.dim / t->config.n_heads) / 2;
+    Q4_HIP(hipMemcpy(cos_sin, m->rope_table + (size_t)pos * hp, hp * sizeof(float2), hipMemcpyDeviceToHost));
+    return Q4_OK;
+}
 
 // How many steps a token loop may queue at once from `pos`: Q4_MULTI_STEPS when graphs are on, the sampler is greedy, the
 // whole group generates (or the whole group feeds prompt tokens), ends by `steps` and stays inside one sequence-length
@@ -521,7 +625,12 @@ double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_token
 double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos,
                             int* out_tokens, int* timed_tokens_out, double* seconds_out) {
     if (!t || !sampler || !prompt_tokens || num_prompt_tokens < 1) return -1.0;
-    if (steps <= 0 || steps > t->config.seq_len) steps = t->config.seq_len;        // :690
+    // q4_set_context_shift: the loop shifts at seq_len instead of stopping there, so steps may pass it. `pos` below counts steps (it indexes the history);
+    // the device runs step `pos` at position pos - off, off being the positions discarded so far
+    const Model* sm = model_of(&t->state);
+    const int seq_len = t->config.seq_len, shift_keep = sm ? sm->shift_keep : 0, shift_discard = sm ? sm->shift_discard : 0;
+    if (steps <= 0) steps = seq_len;
+    else if (steps > (shift_discard > 0 ? Q4_MAX_SEQ_LEN - 1 : seq_len)) steps = shift_discard > 0 ? Q4_MAX_SEQ_LEN - 1 : seq_len;   // :690
     if (start_pos < 0 || start_pos > num_prompt_tokens - 1 || start_pos > t->config.seq_len) {
         snprintf(g_last_error, sizeof(g_last_error), "q4_generate_ids_from: start_pos %d outside [0, %d] (%s)", start_pos, num_prompt_tokens - 1, q4_status_string(Q4_ERR_ARG));
         return -1.0;
@@ -530,11 +639,12 @@ double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_
     for (int i = 1; i < start_pos; i++)
         if (prompt_tokens[i] == 2) start_pos = 0;
     const unsigned long long rng0 = sampler->rng_state;
+    std::vector<int> history;                                // of a run that shifts: every token by step, the evicted ones too
     for (int attempt = 0;; attempt++) {
         struct timespec t0, t1;
         clock_gettime(CLOCK_MONOTONIC, &t0);
         const int start = attempt == 0 ? start_pos : 0;      // the retry after a time-out trusts no row
-        int pos = start, queued = start, group_start = start;
+        int pos = start, queued = start, group_start = start, off = 0;
         if (start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start)) return -1.0;
         for (int i = 0; i < start; i++) (void)random_f32(&sampler->rng_state);
         unsigned long long group_rng = sampler->rng_state;   // sampler state in front of the group of steps queued last
@@ -545,15 +655,22 @@ double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_
             // Greedy steps inside one bin go out Q4_MULTI_STEPS at a time (one graph replay); a stop at EOS leaves at most
             // Q4_MULTI_STEPS - 1 surplus steps behind, which the next q4_reset_sequence discards.
             if (pos >= queued) {
-                const int k = q4_steps_that_fit(pos, num_prompt_tokens, steps, &t->config, sampler);
+                if (shift_discard > 0 && pos - off == seq_len) {     // the wall: everything queued has to finish (q4_shift_context synchronises), then the rows slide
+                    if (hipStreamSynchronize(g_stream) != hipSuccess) { (void)hipGetLastError(); return -1.0; }
+                    if (history.empty()) history.resize((size_t)steps + 1);
+                    for (int i = off ? shift_keep : 0; i <= seq_len && off + i <= steps; i++) history[off + i] = t->state.shared_data->tokens[i];
+                    if (q4_shift_context(t, seq_len, shift_keep, shift_discard, seq_len + 1)) return -1.0;
+                    off += shift_discard;
+                }
+                const int k = q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                if (run_transformer_steps_screenable(pos, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos, k, steps))) return -1.0;
+                if (run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off))) return -1.0;
                 queued = pos + k;
             }
-            if (q4_wait_pos(&t->state, pos)) return -1.0;                              // :468
+            if (q4_wait_pos(&t->state, pos - off)) return -1.0;                        // :468
             if (pos > 0) {
-                int next = t->state.shared_data->tokens[pos];                          // :473
+                int next = t->state.shared_data->tokens[pos - off];                    // :473
                 if (next >= t->config.vocab_size) next = 0;                            // :474
                 if (next == 2) { stopped = true; break; }                              // eos_token, :477
             }
@@ -569,12 +686,17 @@ double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_
         const double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
         const int timed_tokens = pos - 1 - start;                                      // :488, over the steps this call ran
         if (q4_handoff_status(&t->state)) {     // a timed-out in-launch wait: the library is at fusion level 1 now, state cleared
-            if (attempt == 0) { sampler->rng_state = rng0; continue; }                 // redo the whole sequence once
+            if (attempt == 0 && off == 0) { sampler->rng_state = rng0; continue; }     // redo the whole sequence once (shifted rows cannot be redone)
             return -1.0;
         }
         if (out_tokens) {
             const int n = (pos < steps ? pos : steps) + 1;
-            for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = t->state.shared_data->tokens[i];
+            if (off) {
+                for (int i = shift_keep; i <= seq_len && off + i < n; i++) history[off + i] = t->state.shared_data->tokens[i];
+                for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = history[i];
+            } else {
+                for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = t->state.shared_data->tokens[i];
+            }
         }
         if (timed_tokens_out) *timed_tokens_out = timed_tokens;
         if (seconds_out) *seconds_out = secs;
