@@ -276,6 +276,49 @@ int q4_set_kv_format(int format);
 int q4_get_kv_format(void);
 /* the format of the model that owns this RunState; Q4_KV_FP16 for a RunState the library did not build */
 int q4_kv_format_of(const RunState* s);
+/* RoPE scaling of the models q4_build_transformer builds from now on (process-wide and read by the build, like q4_set_kv_format; a model's scaling is
+ * fixed at build time; the 32-byte file header has no room for it). Q4_ROPE_NONE (default): the angles are pos / powf(rope_theta, 2i / head_size), every
+ * launch and every bit as without this call. Otherwise the model gets head_size/2 per-pair frequencies inv_freq[i], computed in double and rounded once to
+ * float: with f_i = pow((double)rope_theta, -(2.0 * i) / head_size),
+ *   Q4_ROPE_LINEAR (position interpolation, Hugging Face rope_scaling type "linear"): f_i / factor;
+ *   Q4_ROPE_LLAMA3 (Llama-3.1 / 3.2, Hugging Face _compute_llama3_parameters): with wl = 2 pi / f_i and orig = original_max_position,
+ *     wl < orig / high_freq_factor keeps f_i, wl > orig / low_freq_factor gives f_i / factor, otherwise with
+ *     s = (orig / wl - low_freq_factor) / (high_freq_factor - low_freq_factor) the result is (1 - s) * f_i / factor + s * f_i;
+ *   Q4_ROPE_CUSTOM: the given floats as they are (per-pair factor lists, frequencies of another theta); n_freqs != head_size / 2 fails the build with
+ *     Q4_ERR_ARG and a q4_last_error text.
+ * The model's rotation table [seq_len][head_size/2] then holds (cosf(a), sinf(a)) of a = (float)pos * inv_freq[i], one fp32 multiply, and everything that
+ * rotates reads it (fusion level 0 computes the same bits from the device copy of inv_freq): no launch is added to or changed in the decode step. For such
+ * a model the table is mandatory -- a failed allocation is Q4_ERR_ALLOC, a table above 2^30 entries Q4_ERR_UNSUPPORTED_SIZE, never a fall-back to unscaled
+ * angles. LINEAR with factor 1 is not the NONE path: its frequencies may differ from 1 / powf in the last bit. FP8 models, snapshots (a scaled model's
+ * fingerprint also covers its frequencies) and context shift work as for any model. Not covered: YaRN / longrope (an attention factor), dynamic NTK. */
+enum { Q4_ROPE_NONE = 0, Q4_ROPE_LINEAR = 1, Q4_ROPE_LLAMA3 = 2, Q4_ROPE_CUSTOM = 3, Q4_ROPE_MAX_PAIRS = 256 };
+typedef struct {
+    int kind;
+    float factor;                 /* LINEAR, LLAMA3: finite, >= 1 */
+    float low_freq_factor;        /* LLAMA3: finite, > 0, < high_freq_factor */
+    float high_freq_factor;
+    int original_max_position;    /* LLAMA3: >= 1 */
+    int n_freqs;                  /* CUSTOM: head_size / 2, 1 .. Q4_ROPE_MAX_PAIRS */
+    const float* inv_freq;        /* CUSTOM: host array, copied; each finite and >= 0 */
+} q4_rope_scaling;
+/* NULL or kind NONE: off. Q4_ERR_ARG: anything above violated or an unknown kind; nothing changes, no GPU touched. Fields the kind does not use are ignored. */
+int q4_set_rope_scaling(const q4_rope_scaling* s);
+int q4_get_rope_scaling(q4_rope_scaling* out);        /* inv_freq points at the library's copy (CUSTOM), else NULL */
+/* the scaling of a built model (inv_freq: the model's own frequency array, whatever the kind; NULL for an unscaled model). Q4_ERR_ARG: a Transformer the
+ * library did not build */
+int q4_rope_scaling_of(const Transformer* t, q4_rope_scaling* out);
+/* "none" | "linear,factor=4" | "llama3,factor=8,low=1,high=4,orig=8192": the kind first, then its keys, all of them, in any order. Q4_ERR_ARG and *out
+ * untouched: an unknown kind or key, a key twice or missing, a malformed number, a value q4_set_rope_scaling refuses. (CUSTOM has no text form.) */
+int q4_parse_rope_scaling(const char* text, q4_rope_scaling* out);
+/* Host only, no GPU: the head_size/2 frequencies a model of this head size and theta gets under s, as defined above; s NULL or kind NONE gives the f_i
+ * themselves (rounded to float). Q4_ERR_ARG: a scaling the setter refuses, an odd or non-positive head_size, a theta that is not finite and positive,
+ * CUSTOM with n_freqs != head_size / 2. */
+int q4_rope_inv_freq(const q4_rope_scaling* s, int head_size, float rope_theta, float* out);
+int q4_get_rope_inv_freq(const Transformer* t, float* out);          /* head_size/2 floats; Q4_ERR_ARG for an unscaled model: it has no frequency array */
+/* Op-level form of fusion level 0's rotation for a scaled model: q4_rope_rotation with the angle (float)*pPos * inv_freq_dev[i], inv_freq_dev
+ * [head_size/2] floats on the device */
+int q4_rope_rotation_freqs(q4_half* q, q4_half* k, int num_heads, int num_kv_heads, int head_size, const int* pPos, int loff,
+                           const float* inv_freq_dev);
 /* 1: at fusion levels 4 / 5 a layer's FFN half of these sizes runs as one launch on the current device and stream (csrc/gemv_ffn_pair.h) */
 int q4_ffn_pair_covers(int dim, int hidden_dim);
 /* 1 (default): hipGraph capture/replay as USE_CUDA_GRAPHS llama2_q4.cu:33; 0: eager launches with the exact context length (the
@@ -430,7 +473,8 @@ struct q4_snapshot_info {                               /* (the record shares it
     int kv_format;                                      /* Q4_KV_FP16 / Q4_KV_FP8 */
     int n_layers, n_kv_heads, head_size;
     float rope_theta;
-    unsigned long long fingerprint;                     /* of the checkpoint file: its header without seq_len, its size, its first and last 64 KiB */
+    unsigned long long fingerprint;                     /* of the checkpoint file: its header without seq_len, its size, its first and last 64 KiB; a model with
+                                                           RoPE scaling: that, mixed with the fp32 bits of its frequencies (two settings that give the same frequencies interchange) */
     unsigned long long device_bytes;                    /* the packed rows */
     unsigned long long export_bytes;                    /* what q4_snapshot_export writes */
 };
@@ -463,7 +507,7 @@ int q4_snapshot_new(q4_snapshot** out, const Transformer* t, int n_pos);
  * one opened with another seq_len. Does not move the position or touch the ring: follow with q4_resume_sequence or q4_generate_ids_from at any
  * start_pos <= n_pos, with tokens that begin with the snapshot's. The restored prefix counts as a prompt: the guide ring is NONE there, so the automaton
  * starts at state 0 behind it, as behind any prompt; log-probability records below n_pos are left as they are. Q4_ERR_ARG, nothing copied: another
- * checkpoint (fingerprint), geometry (layers, kv heads, head size), rope_theta or K / V format, or n_pos above t's seq_len. */
+ * checkpoint or other RoPE frequencies (fingerprint), geometry (layers, kv heads, head size), rope_theta or K / V format, or n_pos above t's seq_len. */
 int q4_snapshot_restore(Transformer* t, const q4_snapshot* s);
 int q4_snapshot_delete(q4_snapshot* s);                 /* synchronises the q4 stream first: a restore may still be reading */
 int q4_snapshot_info(const q4_snapshot* s, struct q4_snapshot_info* out);
@@ -491,6 +535,7 @@ int q4_copy_runs(void* dst, const void* src, long long outer, long long dst_stri
  * What is guaranteed is the operation: deterministic, and specified exactly. With (c, s) = row D of the model's rotation table at pair index i,
  * a = float(k[i]), b = float(k[i + head_size/2]), every operation one IEEE fp32 operation:
  *   k'[i] = half_rne((a * c) + (b * s))      k'[i + head_size/2] = half_rne((b * c) - (a * s))
+ * This holds for a model with RoPE scaling as well: row D of its table is the rotation of D positions for any per-pair frequency.
  * An FP8 K row is dequantised first (byte * 2^e, exactly fp16) and its rotated halves quantised again by the format's rule (new exponent, new
  * bytes); V bytes and exponents move as they are. Every shift therefore rounds the moved K rows once more (twice for FP8: to half and to e4m3), and
  * repeated shifts compound that. Opt-in: without these calls and without a setting, the launches, graphs, bits and return values are unchanged. */

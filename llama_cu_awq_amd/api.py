@@ -20,6 +20,8 @@ KV_FORMATS = {"fp16": KV_FP16, "fp8": KV_FP8}
 MAX_TOP_LOGPROBS = 20           # Q4_MAX_TOP_LOGPROBS
 MAX_PENALTY_WINDOW = 1024       # Q4_MAX_PENALTY_WINDOW
 MAX_LOGIT_BIAS = 256            # Q4_MAX_LOGIT_BIAS
+ROPE_NONE, ROPE_LINEAR, ROPE_LLAMA3, ROPE_CUSTOM, ROPE_MAX_PAIRS = 0, 1, 2, 3, 256   # Q4_ROPE_*
+ROPE_KINDS = {"none": ROPE_NONE, "default": ROPE_NONE, "linear": ROPE_LINEAR, "llama3": ROPE_LLAMA3, "custom": ROPE_CUSTOM}
 GUIDE_MAX_STATES, GUIDE_DEAD, GUIDE_NONE, GUIDE_OFFTRACK = 4096, 0xFFFF, -1, -2   # Q4_GUIDE_*
 
 
@@ -63,6 +65,70 @@ class SnapshotInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RopeScaling(C.Structure):
+    """q4_rope_scaling; the default is kind NONE"""
+    _fields_ = [("kind", C.c_int), ("factor", C.c_float), ("low_freq_factor", C.c_float), ("high_freq_factor", C.c_float),
+                ("original_max_position", C.c_int), ("n_freqs", C.c_int), ("inv_freq", C.POINTER(C.c_float))]
+
+    def as_dict(self):
+        """the setting in Hugging Face's spelling (custom: with a copy of the frequencies); None for kind NONE"""
+        if self.kind == ROPE_LINEAR:
+            return {"rope_type": "linear", "factor": self.factor}
+        if self.kind == ROPE_LLAMA3:
+            return {"rope_type": "llama3", "factor": self.factor, "low_freq_factor": self.low_freq_factor, "high_freq_factor": self.high_freq_factor,
+                    "original_max_position_embeddings": self.original_max_position}
+        if self.kind == ROPE_CUSTOM:
+            return {"kind": "custom", "inv_freq": np.array(self.inv_freq[:self.n_freqs], dtype=np.float32)}
+        return None
+
+
+def rope_scaling_struct(scaling):
+    """None, the text form ("linear,factor=4", "llama3,factor=8,low=1,high=4,orig=8192", "none"), a dict in Hugging Face's rope_scaling spelling
+    (rope_type or type, factor, low_freq_factor, high_freq_factor, original_max_position_embeddings), dict(kind="custom", inv_freq=array) or a
+    RopeScaling -> (RopeScaling, the array it points into or None: keep it alive as long as the struct). Checked by the library, not here."""
+    if scaling is None:
+        return RopeScaling(), None
+    if isinstance(scaling, RopeScaling):
+        return scaling, None
+    if isinstance(scaling, str):
+        r = RopeScaling()
+        if lib().q4_parse_rope_scaling(scaling.encode(), C.byref(r)):
+            raise ValueError("rope_scaling: cannot use %r (none | linear,factor=F | llama3,factor=F,low=L,high=H,orig=N)" % (scaling,))
+        return r, None
+    if not isinstance(scaling, dict):
+        raise ValueError("rope_scaling: None, a text, a dict or a RopeScaling, not %r" % (scaling,))
+    kind = scaling.get("kind", scaling.get("rope_type", scaling.get("type")))
+    if kind not in ROPE_KINDS:
+        raise ValueError("rope_scaling: kind %r is not supported (linear, llama3, custom; yarn, longrope and dynamic are not)" % (kind,))
+    r = RopeScaling(kind=ROPE_KINDS[kind])
+    keep = None
+    if r.kind in (ROPE_LINEAR, ROPE_LLAMA3):
+        r.factor = float(scaling["factor"])
+    if r.kind == ROPE_LLAMA3:
+        r.low_freq_factor = float(scaling["low_freq_factor"])
+        r.high_freq_factor = float(scaling["high_freq_factor"])
+        r.original_max_position = int(scaling["original_max_position_embeddings"])
+    if r.kind == ROPE_CUSTOM:
+        keep = np.ascontiguousarray(scaling["inv_freq"], dtype=np.float32).reshape(-1)
+        r.n_freqs = keep.shape[0]
+        r.inv_freq = keep.ctypes.data_as(C.POINTER(C.c_float))
+    return r, keep
+
+
+def rope_inv_freq(scaling, head_size, theta):
+    """q4_rope_inv_freq (host only): the head_size/2 float32 frequencies a model of this head size and rope_theta gets under `scaling` (any form
+    Transformer(rope_scaling=...) accepts; None: the unscaled pow(theta, -2i/head_size), rounded to float)."""
+    r, keep = rope_scaling_struct(scaling)
+    out = np.empty(max(int(head_size) // 2, 1), dtype=np.float32)
+    check(lib().q4_rope_inv_freq(C.byref(r), int(head_size), float(theta), out.ctypes.data))
+    return out
+
+
+def RoPERotationFreqs(q, k, num_heads, num_kv_heads, head_size, pPos, loff, inv_freq):
+    """q4_rope_rotation_freqs over DevBufs: RoPERotation with the angle pos * inv_freq[i] (inv_freq: head_size/2 float32 on the device)"""
+    check(lib().q4_rope_rotation_freqs(q.ptr, k.ptr, num_heads, num_kv_heads, head_size, pPos.ptr, loff, inv_freq.ptr))
+
+
 class SamplingControls(C.Structure):
     """q4_sampling_controls; the defaults are the neutral values (everything off)"""
     _fields_ = [("top_k", C.c_int), ("min_p", C.c_float), ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float),
@@ -97,6 +163,8 @@ SYMBOLS = [
     "q4_resume_sequence", "q4_common_prefix", "q4_generate_ids_from", "q4_snapshot_new", "q4_snapshot_restore", "q4_snapshot_delete", "q4_snapshot_info",
     "q4_snapshot_tokens", "q4_snapshot_export", "q4_snapshot_import", "q4_snapshot_check", "q4_copy_runs",
     "q4_shift_context", "q4_set_context_shift", "q4_get_context_shift", "q4_parse_context_shift", "q4_get_rope_row", "q4_kv_shift",
+    "q4_set_rope_scaling", "q4_get_rope_scaling", "q4_rope_scaling_of", "q4_parse_rope_scaling", "q4_rope_inv_freq", "q4_get_rope_inv_freq",
+    "q4_rope_rotation_freqs",
 ]
 
 _lib = None
@@ -269,6 +337,14 @@ def lib():
         L.q4_parse_context_shift.argtypes = [C.c_char_p, C.POINTER(i), C.POINTER(i)]
         L.q4_get_rope_row.argtypes = [vp, i, vp]
         L.q4_kv_shift.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
+    if hasattr(L, "q4_set_rope_scaling"):          # (older builds under tools/ab.py do not have it)
+        L.q4_set_rope_scaling.argtypes = [C.POINTER(RopeScaling)]
+        L.q4_get_rope_scaling.argtypes = [C.POINTER(RopeScaling)]
+        L.q4_rope_scaling_of.argtypes = [vp, C.POINTER(RopeScaling)]
+        L.q4_parse_rope_scaling.argtypes = [C.c_char_p, C.POINTER(RopeScaling)]
+        L.q4_rope_inv_freq.argtypes = [C.POINTER(RopeScaling), i, f, vp]
+        L.q4_get_rope_inv_freq.argtypes = [vp, vp]
+        L.q4_rope_rotation_freqs.argtypes = [vp, vp, i, i, i, vp, i, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -516,7 +592,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None, context_shift=None):
+                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -527,6 +603,20 @@ class Transformer:
         if not has and kv != "fp16":
             raise Q4Error("this build of the library has no FP8 K / V cache")
         before = L.q4_get_kv_format() if has else KV_FP16
+        # ... and so is the RoPE scaling (rope_scaling_struct lists the accepted forms)
+        has_rope = hasattr(L, "q4_set_rope_scaling")   # (older builds under tools/ab.py do not have it: unscaled only)
+        if not has_rope and rope_scaling is not None:
+            raise Q4Error("this build of the library has no RoPE scaling")
+        rope, rope_keep = rope_scaling_struct(rope_scaling) if has_rope else (None, None)
+        rope_before = RopeScaling()
+        if has_rope:
+            check(L.q4_get_rope_scaling(C.byref(rope_before)))
+            if rope_before.kind == ROPE_CUSTOM:        # (points at the library's copy, which the next call rewrites)
+                rope_before_keep = np.array(rope_before.inv_freq[:rope_before.n_freqs], dtype=np.float32)
+                rope_before.inv_freq = rope_before_keep.ctypes.data_as(C.POINTER(C.c_float))
+            if L.q4_set_rope_scaling(C.byref(rope)):
+                raise ValueError("rope_scaling: %r is refused (factor >= 1; llama3: 0 < low_freq_factor < high_freq_factor, "
+                                 "original_max_position_embeddings >= 1; custom: 1 .. %d finite frequencies >= 0)" % (rope_scaling, ROPE_MAX_PAIRS))
         if has:
             check(L.q4_set_kv_format(KV_FORMATS[kv]))
         try:
@@ -534,6 +624,9 @@ class Transformer:
         finally:
             if has:
                 L.q4_set_kv_format(before)
+            if has_rope:
+                L.q4_set_rope_scaling(C.byref(rope_before))
+        del rope_keep
         self.kv_format = kv
         if not self.h:
             raise Q4Error("build_transformer failed: %s %s" % (L.q4_status_string(st.value).decode(), L.q4_last_error().decode()))
@@ -687,6 +780,26 @@ class Transformer:
             check(lib().q4_stream_synchronize())
             n_pos = min(self.pos(), self.config.seq_len)
         check(lib().q4_shift_context(self.h, int(n_pos), int(n_keep), int(n_discard), int(n_pos + 1 if n_ring is None else n_ring)))
+
+    @property
+    def rope_scaling(self):
+        """the model's RoPE scaling (q4_rope_scaling_of) in Hugging Face's spelling, dict(kind="custom", inv_freq=...) for custom frequencies, None for
+        an unscaled model"""
+        L = lib()
+        if not hasattr(L, "q4_rope_scaling_of"):               # (older builds under tools/ab.py do not have it)
+            return None
+        r = RopeScaling()
+        check(L.q4_rope_scaling_of(self.h, C.byref(r)))
+        if r.kind == ROPE_CUSTOM:
+            return {"kind": "custom", "inv_freq": self.rope_inv_freq()}
+        return r.as_dict()
+
+    def rope_inv_freq(self):
+        """q4_get_rope_inv_freq: the head_size/2 float32 frequencies the model's rotation table was built from; Q4Error for an unscaled model (its
+        table comes from rope_theta: it has no frequency array)"""
+        out = np.empty(self.config.dim // self.config.n_heads // 2, dtype=np.float32)
+        check(lib().q4_get_rope_inv_freq(self.h, out.ctypes.data))
+        return out
 
     def rope_row(self, pos):
         """row `pos` of the model's rotation table: [head_size/2, 2] float32 (cos, sin); synchronises"""

@@ -31,7 +31,7 @@ bool layer_att_covers(int dim, int hidden, int kv_dim, int n_heads, int seq_len_
 }
 
 // fusion level 5: the launch also runs rmsnorm + q/k/v + RoPE + KV write of the NEXT layer. Multi-head models with 128-wide heads and a rotation table
-// (every Llama-2-7B-shaped model): a block's eight RoPE pairs stay inside one head.
+// (every Llama-2-7B-shaped model): a block's eight RoPE pairs stay inside one head. Phase 3 has no on-the-fly angle at all: the table is the model's own, scaled or not.
 bool ffn_qkv_covers(int dim, int hidden, int kv_dim, int head_size, bool have_rope_table) {
     if (!ffn_pair_covers(dim, hidden) || kv_dim != dim || !have_rope_table || head_size < 16 || (head_size & 1)) return false;
     const int nb = cu_count(), hp = head_size / 2;

@@ -64,7 +64,7 @@ struct GemvArgs {
     int head_size;
     float rope_theta;
     unsigned long long* dbg;   // ABL == 3 only: per-wave s_memtime stamps
-    const float2* rope_table;  // [seq_len][head_size/2] (cos, sin) built with the reference's formula; null: compute
+    const float2* rope_table;  // [seq_len][head_size/2] (cos, sin) built with the reference's formula (or from the model's scaled frequencies); null: compute, unscaled
     int early;                 // waves in the first `early` slots of a SIMD issue their weight loads before the staging ends
     unsigned* bump;            // QKV: epoch word of the FOLLOWING attention + o-proj launch, advanced once by block (0, 0)
     int kv_stage;              // QKV: out[1] / out[2] are ROWS (the FP8 cache's fp16 staging rows, attention_kv8.h), not caches: no loff + pos * N
@@ -616,7 +616,7 @@ __device__ __forceinline__ void gemv_q4_body(const GemvArgs& a, const unsigned v
             if (a.rope_table != nullptr) {   // same bits as the on-the-fly path: the table was filled by rope_angle()
                 const float2 cs = a.rope_table[(size_t)pos * hp + i];
                 fcr = cs.x; fci = cs.y;
-            } else {
+            } else {   // unscaled models and the per-kernel API only: a model with RoPE scaling always has its table (q4_build_transformer fails without one)
                 rope_angle(i, a.head_size, pos, a.rope_theta, fcr, fci);
             }
             r = (row & 2) ? (other * fci + me * fcr) : (me * fcr - other * fci);    // :345-346

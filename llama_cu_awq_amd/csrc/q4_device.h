@@ -107,6 +107,14 @@ __device__ __forceinline__ void rope_angle(int i, int head_size, int pos, float 
     fci = sinf(val);
 }
 
+// ... of a model with RoPE scaling (q4_set_rope_scaling): the pair's own frequency from the model's inv_freq array, one fp32 multiply. Everything that
+// rotates for a scaled model -- the table kernel, the level-0 rotation kernel -- takes (cos, sin) from here, so a table row and the on-the-fly path agree bit for bit
+__device__ __forceinline__ void rope_angle_freq(float inv_freq, int pos, float& fcr, float& fci) {
+    const float val = (float)pos * inv_freq;
+    fcr = cosf(val);
+    fci = sinf(val);
+}
+
 // normalise 8 halves: half(x * (ss * w))   gpu_kernels.h:100-102
 // Mixed-precision FMAs read the fp16 halves directly (no v_cvt) and round the fp32 product once to fp16:
 //   t = ss * float(w)            v_fma_mix_f32      (fp32)

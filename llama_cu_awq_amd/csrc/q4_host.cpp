@@ -550,6 +550,14 @@ int q4_main(int argc, char** argv) {
     const char* kv = getenv("Q4_KV_CACHE");
     if (kv && strcmp(kv, "fp8") == 0) q4_set_kv_format(Q4_KV_FP8);
     else if (kv && *kv && strcmp(kv, "fp16") != 0) { fprintf(stderr, "Q4_KV_CACHE: unknown format '%s' (fp16 or fp8)\n", kv); exit(EXIT_FAILURE); }
+    // ... the RoPE scaling of the model (q4_parse_rope_scaling): Q4_ROPE_SCALING="llama3,factor=8,low=1,high=4,orig=8192"
+    const char* rope = getenv("Q4_ROPE_SCALING");
+    q4_rope_scaling scaling;
+    if (rope && *rope && (q4_parse_rope_scaling(rope, &scaling) || q4_set_rope_scaling(&scaling))) {
+        fprintf(stderr, "Q4_ROPE_SCALING: cannot use '%s' (none | linear,factor=F | llama3,factor=F,low=L,high=H,orig=N; F >= 1, 0 < L < H, N >= 1; "
+                        "e.g. llama3,factor=8,low=1,high=4,orig=8192)\n", rope);
+        exit(EXIT_FAILURE);
+    }
     // ... and so do the sampling controls (q4_parse_sampling_controls): Q4_SAMPLING="top_k=40,min_p=0.05,repeat_penalty=1.1,last_n=64"
     const char* sampling = getenv("Q4_SAMPLING");
     q4_sampling_controls controls;

@@ -77,6 +77,8 @@ int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, con
                      const int* pPos, int head_size, float rope_theta, const float2* rope_table, unsigned* bump,
                      bool kv_stage = false);   // kv_stage: kc / vc are the FP8 cache's fp16 staging rows [kv_dim], written without loff + pos * kv_dim
 int rope_table_build(float2** out, int seq_len, int head_size, float theta);   // (cos,sin) table for the fused QKV epilogue
+// ... of a model with RoPE scaling, from its device inv_freq [head_size/2]. Mandatory: Q4_ERR_ALLOC / Q4_ERR_UNSUPPORTED_SIZE (above 2^30 entries) instead of "no table"
+int rope_table_build_freqs(float2** out, int seq_len, int head_size, const float* inv_freq_dev);
 int launch_attention(q4_half* output, const q4_half* q, const q4_half* key_cache, const q4_half* value_cache,
                      int num_heads, int head_size, int kv_mul, int max_seq_len, const int* pPos, float* scratch,
                      size_t scratch_bytes, unsigned* arrive);   // arrive: n_heads zeroed counters (split-context merge by the last block) or null

@@ -117,6 +117,26 @@ __global__ void rope_kernel(q4_half* sq, q4_half* sk_base, int num_kv_heads, int
     }
 }
 
+// The same rotation for a model with RoPE scaling: the angle from the model's per-pair frequencies (rope_angle_freq), the arithmetic of rope_kernel
+__global__ void rope_freqs_kernel(q4_half* sq, q4_half* sk_base, int num_kv_heads, int head_size, const int* pPos, int loff,
+                                  const float* __restrict__ inv_freq) {
+    const int pos = *pPos;
+    const int h = blockIdx.x;
+    q4_half* q = sq + (size_t)h * head_size;
+    const int i = threadIdx.x;
+    float fcr, fci;
+    rope_angle_freq(inv_freq[i], pos, fcr, fci);
+    const float q0 = h2f(q[i]), q1 = h2f(q[i + head_size / 2]);
+    q[i] = f2h(q0 * fcr - q1 * fci);
+    q[i + head_size / 2] = f2h(q0 * fci + q1 * fcr);
+    if (h < num_kv_heads) {
+        q4_half* k = sk_base + (size_t)loff + (size_t)pos * num_kv_heads * head_size + (size_t)h * head_size;
+        const float k0 = h2f(k[i]), k1 = h2f(k[i + head_size / 2]);
+        k[i] = f2h(k0 * fcr - k1 * fci);
+        k[i + head_size / 2] = f2h(k0 * fci + k1 * fcr);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // MultiHeadAttention: attention_body / attention_kernel live in attention.h (shared with the fused launch, layer_attn.hip)
 // Long contexts: attention_split_body / attention_split_kernel / attention_combine_kernel live in attention.h
@@ -225,6 +245,36 @@ int rope_table_build(float2** out, int seq_len, int head_size, float theta) {
     return Q4_OK;
 }
 
+// ... of a model with RoPE scaling: row pos, pair i = (cos, sin)((float)pos * inv_freq[i]), inv_freq [head_size/2] on the device
+__global__ void rope_table_freqs_kernel(float2* table, int seq_len, int head_size, const float* __restrict__ inv_freq) {
+    const int hp = head_size >> 1;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)seq_len * hp) return;
+    float c, s;
+    rope_angle_freq(inv_freq[idx % hp], (int)(idx / hp), c, s);
+    table[idx] = make_float2(c, s);
+}
+
+// For a scaled model the table is mandatory: "null: compute" computes UNSCALED angles. No table is an error, never a fall-back.
+int rope_table_build_freqs(float2** out, int seq_len, int head_size, const float* inv_freq_dev) {
+    *out = nullptr;
+    const size_t n = (size_t)seq_len * (head_size / 2);
+    if (n == 0 || n > (1u << 30) || !inv_freq_dev) {
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: a rotation table of %zu entries is not supported (1 .. 2^30)", n);
+        return Q4_ERR_UNSUPPORTED_SIZE;
+    }
+    if (hipMalloc((void**)out, n * sizeof(float2)) != hipSuccess) {
+        *out = nullptr;
+        (void)hipGetLastError();
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: no device memory for the rotation table (%zu bytes)", n * sizeof(float2));
+        return Q4_ERR_ALLOC;
+    }
+    Q4_LAUNCH(rope_table_freqs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, *out, seq_len, head_size, inv_freq_dev);
+    Q4_LAUNCH_CHECK();
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    return Q4_OK;
+}
+
 // ---- fused-path launchers used by the network -----------------------------------------------------
 static void fill_mat(GemvMat& m, const QWeight* w) { m.w = w->weight; m.z = w->zeros; m.s = w->scales; }
 
@@ -249,7 +299,8 @@ int launch_qkv_fused(q4_half* q, q4_half* kc, q4_half* vc, const q4_half* x, con
     a.out[0] = q; a.out[1] = kc; a.out[2] = vc;
     a.x = x; a.rms_w = rms_w; a.pPos = pPos; a.loff = loff;
     a.rope = head_size > 0; a.head_size = head_size > 0 ? head_size : 2; a.rope_theta = rope_theta;
-    a.rope_table = head_size > 0 ? rope_table : nullptr;   // [seq_len][head_size/2] for THIS model, or null: compute
+    a.rope_table = head_size > 0 ? rope_table : nullptr;   // [seq_len][head_size/2] for THIS model, or null: compute from rope_theta (UNSCALED angles: run_network never
+                                                           // comes here without the table for a model with RoPE scaling)
     a.early = g_tune[TUNE_QKV].early;
     a.bump = bump;
     a.kv_stage = kv_stage ? 1 : 0;
@@ -366,6 +417,15 @@ int q4_rope_rotation(q4_half* q, q4_half* k, int num_heads, int num_kv_heads, in
     if (head_size < 2 || head_size / 2 > 1024) return Q4_ERR_UNSUPPORTED_SIZE;
     Q4_LAUNCH(rope_kernel, dim3(num_heads), dim3(head_size / 2), 0, q, k, num_kv_heads, head_size, pPos,
                        loff, rope_theta);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+
+int q4_rope_rotation_freqs(q4_half* q, q4_half* k, int num_heads, int num_kv_heads, int head_size, const int* pPos, int loff,
+                           const float* inv_freq_dev) {
+    if (head_size < 2 || (head_size & 1) || head_size / 2 > 1024) return Q4_ERR_UNSUPPORTED_SIZE;
+    if (!q || !k || !pPos || !inv_freq_dev || num_heads < 1 || num_kv_heads < 0 || num_kv_heads > num_heads) return Q4_ERR_ARG;
+    Q4_LAUNCH(rope_freqs_kernel, dim3(num_heads), dim3(head_size / 2), 0, q, k, num_kv_heads, head_size, pPos, loff, inv_freq_dev);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }

@@ -1,6 +1,7 @@
 // q4_model.h -- what the library keeps beside a Transformer, and what q4_model.hip, q4_network.hip and q4_step.hip share (not part of the C ABI).
 #pragma once
 #include <map>
+#include <vector>
 #include "q4_internal.h"
 #include "cls_screen.h"
 
@@ -15,6 +16,9 @@ struct Model {
     void* shared = nullptr;
     void* logits_array = nullptr;
     float2* rope_table = nullptr;   // [seq_len][head_size/2] (cos, sin), lives exactly as long as the Transformer
+    q4_rope_scaling rope = {};      // fixed at build time (q4_set_rope_scaling). kind Q4_ROPE_NONE: the table comes from rope_theta (rope_angle) and the two arrays below are empty;
+    std::vector<float> inv_freq;    // else [head_size/2] frequencies (q4_rope_inv_freq), the table comes from them (rope_angle_freq) and is mandatory,
+    float* inv_freq_dev = nullptr;  // and their device copy, which fusion level 0's rotation launch reads. rope.inv_freq is not kept: q4_rope_scaling_of points it at inv_freq
     unsigned* sync = nullptr;       // hand-off words of the attention -> o-proj launch (layout: q4_internal.h SYNC_*), null: the five-launch sequence
     size_t sync_words = 0;          // word 0 is the sticky error flag
     size_t att_bytes = 0;           // bytes of RunState::att (the split-context records live there)
@@ -51,6 +55,9 @@ static inline Model* model_of(const RunState* s) {
 }
 
 #define Q4_TRY(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
+
+// q4_model.hip: the process-wide setting q4_build_transformer reads (q4_set_rope_scaling); its inv_freq points at the library's copy
+extern q4_rope_scaling g_rope_scaling;
 
 // q4_network.hip. have_embedding: the preceding launch of the stream (the greedy sampler of the previous step, inside one graph replay) has left
 // the token's embedding row in s->x already

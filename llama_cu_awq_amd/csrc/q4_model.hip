@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <chrono>
 #include <type_traits>
 #include <vector>
 #include "q4_model.h"
@@ -14,6 +15,8 @@ namespace q4 {
 hipStream_t g_stream = nullptr;
 int g_fusion = 5;
 int g_kv_format = Q4_KV_FP16;
+q4_rope_scaling g_rope_scaling = {};          // q4_set_rope_scaling; a CUSTOM setting's inv_freq points at g_rope_custom
+static float g_rope_custom[Q4_ROPE_MAX_PAIRS];
 int g_multi_steps = Q4_MULTI_STEPS;   // greedy steps per graph replay in the token loops (profiling build: q4_set_gemv_early(7, n))
 int g_use_graphs = 1;
 int g_quiet = 0;
@@ -217,6 +220,72 @@ static unsigned long long checkpoint_fingerprint(FILE* file, const Config* p) {
     return h ? h : 1;
 }
 
+// what q4_set_rope_scaling, q4_parse_rope_scaling and q4_rope_inv_freq accept (llama2_q4.h)
+static bool rope_scaling_ok(const q4_rope_scaling* s) {
+    if (!s || s->kind == Q4_ROPE_NONE) return true;
+    const bool factor_ok = isfinite(s->factor) && s->factor >= 1.0f;
+    switch (s->kind) {
+        case Q4_ROPE_LINEAR: return factor_ok;
+        case Q4_ROPE_LLAMA3:
+            return factor_ok && isfinite(s->low_freq_factor) && isfinite(s->high_freq_factor) && s->low_freq_factor > 0.0f &&
+                   s->low_freq_factor < s->high_freq_factor && s->original_max_position >= 1;
+        case Q4_ROPE_CUSTOM:
+            if (s->n_freqs < 1 || s->n_freqs > Q4_ROPE_MAX_PAIRS || !s->inv_freq) return false;
+            for (int i = 0; i < s->n_freqs; i++)
+                if (!isfinite(s->inv_freq[i]) || s->inv_freq[i] < 0.0f) return false;
+            return true;
+    }
+    return false;
+}
+
+// the text form q4_parse_rope_scaling reads ("Model params" prints it); CUSTOM has none
+static void rope_scaling_text(const q4_rope_scaling& r, char* out, size_t n) {
+    switch (r.kind) {
+        case Q4_ROPE_LINEAR: snprintf(out, n, "linear,factor=%g", r.factor); break;
+        case Q4_ROPE_LLAMA3:
+            snprintf(out, n, "llama3,factor=%g,low=%g,high=%g,orig=%d", r.factor, r.low_freq_factor, r.high_freq_factor, r.original_max_position);
+            break;
+        case Q4_ROPE_CUSTOM: snprintf(out, n, "custom,n_freqs=%d", r.n_freqs); break;
+        default: snprintf(out, n, "none");
+    }
+}
+
+// The scaled model's frequencies, their device copy, its (mandatory) table, and its fingerprint: the checkpoint's mixed with the frequencies' fp32 bits
+static int build_scaled_rope(Model& m, const Config* p) {
+    const int head_size = p->dim / p->n_heads, hp = head_size / 2;
+    if (head_size < 2 || (head_size & 1)) {
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: head size %d is not even", head_size);
+        return Q4_ERR_ARG;
+    }
+    if (m.rope.kind == Q4_ROPE_CUSTOM && m.rope.n_freqs != hp) {
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: %d custom frequencies for a head size of %d (needs %d)", m.rope.n_freqs, head_size, hp);
+        return Q4_ERR_ARG;
+    }
+    m.inv_freq.resize(hp);
+    if (q4_rope_inv_freq(&m.rope, head_size, p->rope_theta, m.inv_freq.data())) {
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: no frequencies for head size %d and rope_theta %g", head_size, p->rope_theta);
+        return Q4_ERR_ARG;
+    }
+    m.rope.inv_freq = nullptr;     // (pointed at g_rope_custom, which the next q4_set_rope_scaling rewrites)
+    if (hipMalloc((void**)&m.inv_freq_dev, hp * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        m.inv_freq_dev = nullptr;
+        snprintf(g_last_error, sizeof(g_last_error), "rope scaling: no device memory for %d frequencies", hp);
+        return Q4_ERR_ALLOC;
+    }
+    Q4_HIP(hipMemcpy(m.inv_freq_dev, m.inv_freq.data(), hp * sizeof(float), hipMemcpyHostToDevice));
+    Q4_TRY(rope_table_build_freqs(&m.rope_table, p->seq_len, head_size, m.inv_freq_dev));
+    unsigned long long h = 0xcbf29ce484222325ull;
+    auto mix = [&h](const void* data, size_t n) {
+        const unsigned char* b = (const unsigned char*)data;
+        for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; }
+    };
+    mix(&m.fingerprint, sizeof(m.fingerprint));
+    mix(m.inv_freq.data(), hp * sizeof(float));
+    m.fingerprint = h ? h : 1;
+    return Q4_OK;
+}
+
 // everything behind the header and the record's registration; the caller closes the file and, on failure, leaves through q4_free_transformer
 static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
     const Config* p = &t->config;
@@ -264,7 +333,12 @@ static int load_model(Transformer* t, Model& m, FILE* file, int perplexity) {
         s->logits_array = (float*)m.logits_array;
     }
     // fused QKV + RoPE epilogue (multi-head and grouped-query models alike): table of this model's own seq_len
-    Q4_TRY(rope_table_build(&m.rope_table, p->seq_len, p->dim / p->n_heads, p->rope_theta));
+    const auto rope_t0 = std::chrono::steady_clock::now();
+    if (m.rope.kind != Q4_ROPE_NONE) Q4_TRY(build_scaled_rope(m, p));
+    else Q4_TRY(rope_table_build(&m.rope_table, p->seq_len, p->dim / p->n_heads, p->rope_theta));
+    if (getenv("Q4_DEBUG_ROPE"))     // (tools/bench_rope_scaling.py reads it: frequencies, allocation, the table launch and its synchronise)
+        fprintf(stderr, "llama2_q4: rope table: %zu entries, scaling kind %d, built in %.3f ms\n", (size_t)p->seq_len * (p->dim / p->n_heads / 2), m.rope.kind,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - rope_t0).count());
     const size_t sync_words = ffn_pair_sync_offset(p->dim) + ffn_pair_sync_words(p->dim, p->hidden_dim);
     if (hipMalloc((void**)&m.sync, sync_words * sizeof(unsigned)) == hipSuccess) {
         zero_on_stream(m.sync, sync_words * sizeof(unsigned));
@@ -384,6 +458,11 @@ int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perple
     if (!g_quiet)
         printf("\nModel params:- \ndim: %d \nhidden_dim: %d\nn_heads: %d\nn_kv_heads: %d\nn_layers: %d\nseq_len: %d\nvocab_size: %d\nrope_theta: %g\n",
                p->dim, p->hidden_dim, p->n_heads, p->n_kv_heads, p->n_layers, p->seq_len, p->vocab_size, p->rope_theta);   // :416-417
+    if (!g_quiet && g_rope_scaling.kind != Q4_ROPE_NONE) {      // one more line, for a scaled model only
+        char text[128];
+        rope_scaling_text(g_rope_scaling, text, sizeof(text));
+        printf("rope_scaling: %s\n", text);
+    }
     if (p->dim <= 0 || p->n_heads <= 0 || p->n_kv_heads <= 0 || p->n_layers <= 0 || p->vocab_size <= 0 || p->seq_len <= 0 ||
         p->dim % p->n_heads || p->n_heads % p->n_kv_heads || (p->dim & 31) || (p->hidden_dim & 31) ||
         p->seq_len > Q4_MAX_SEQ_LEN) {
@@ -397,6 +476,7 @@ int q4_build_transformer(Transformer* t, const char* checkpoint_path, int perple
     // the first allocation exists: the record is registered, and from here every failure leaves through q4_free_transformer
     Model& m = models()[&t->state] = Model{};
     m.kv_format = g_kv_format;
+    m.rope = g_rope_scaling;
     m.fingerprint = checkpoint_fingerprint(file, p);
     if (m.kv_format == Q4_KV_FP8 && !kv8_head_size_ok(p->dim / p->n_heads)) {
         snprintf(g_last_error, sizeof(g_last_error), "FP8 KV cache: head size %d is not supported (64, 128 or 256)", p->dim / p->n_heads);
@@ -419,7 +499,7 @@ void q4_free_transformer(Transformer* t) {                                      
         Model& m = it->second;
         hipDeviceSynchronize();
         guide_release(&m);
-        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.sync, m.lp_ring, m.screen.base})
+        for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.inv_freq_dev, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);
         models().erase(it);
@@ -435,6 +515,118 @@ int q4_set_kv_format(int format) {
 }
 int q4_get_kv_format(void) { return g_kv_format; }
 int q4_kv_format_of(const RunState* s) { const Model* m = model_of(s); return m ? m->kv_format : Q4_KV_FP16; }
+
+int q4_set_rope_scaling(const q4_rope_scaling* s) {
+    if (!rope_scaling_ok(s) || (s && (s->kind < Q4_ROPE_NONE || s->kind > Q4_ROPE_CUSTOM))) return Q4_ERR_ARG;
+    q4_rope_scaling r = {};
+    if (s && s->kind != Q4_ROPE_NONE) {
+        r.kind = s->kind;
+        if (s->kind != Q4_ROPE_CUSTOM) r.factor = s->factor;
+        if (s->kind == Q4_ROPE_LLAMA3) {
+            r.low_freq_factor = s->low_freq_factor; r.high_freq_factor = s->high_freq_factor; r.original_max_position = s->original_max_position;
+        }
+        if (s->kind == Q4_ROPE_CUSTOM) {
+            r.n_freqs = s->n_freqs;
+            memmove(g_rope_custom, s->inv_freq, (size_t)s->n_freqs * sizeof(float));     // (the caller may hand back q4_get_rope_scaling's own pointer)
+            r.inv_freq = g_rope_custom;
+        }
+    }
+    g_rope_scaling = r;
+    return Q4_OK;
+}
+int q4_get_rope_scaling(q4_rope_scaling* out) {
+    if (!out) return Q4_ERR_ARG;
+    *out = g_rope_scaling;
+    return Q4_OK;
+}
+int q4_rope_scaling_of(const Transformer* t, q4_rope_scaling* out) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !out) return Q4_ERR_ARG;
+    *out = m->rope;
+    out->inv_freq = m->inv_freq.empty() ? nullptr : m->inv_freq.data();
+    return Q4_OK;
+}
+int q4_get_rope_inv_freq(const Transformer* t, float* out) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !out || m->inv_freq.empty()) return Q4_ERR_ARG;
+    memcpy(out, m->inv_freq.data(), m->inv_freq.size() * sizeof(float));
+    return Q4_OK;
+}
+int q4_rope_inv_freq(const q4_rope_scaling* s, int head_size, float rope_theta, float* out) {
+    if (!out || head_size < 2 || (head_size & 1) || !isfinite(rope_theta) || !(rope_theta > 0.0f) || !rope_scaling_ok(s)) return Q4_ERR_ARG;
+    const int hp = head_size / 2, kind = s ? s->kind : Q4_ROPE_NONE;
+    if (kind < Q4_ROPE_NONE || kind > Q4_ROPE_CUSTOM) return Q4_ERR_ARG;
+    if (kind == Q4_ROPE_CUSTOM) {
+        if (s->n_freqs != hp) return Q4_ERR_ARG;
+        memmove(out, s->inv_freq, (size_t)hp * sizeof(float));
+        return Q4_OK;
+    }
+    for (int i = 0; i < hp; i++) {
+        const double f = pow((double)rope_theta, -(2.0 * i) / head_size);
+        double r = f;
+        if (kind == Q4_ROPE_LINEAR) {
+            r = f / (double)s->factor;
+        } else if (kind == Q4_ROPE_LLAMA3) {           // Hugging Face _compute_llama3_parameters
+            const double factor = s->factor, low = s->low_freq_factor, high = s->high_freq_factor, orig = s->original_max_position;
+            const double wl = 2.0 * M_PI / f;
+            if (wl < orig / high) r = f;
+            else if (wl > orig / low) r = f / factor;
+            else {
+                const double sm = (orig / wl - low) / (high - low);
+                r = (1.0 - sm) * f / factor + sm * f;
+            }
+        }
+        out[i] = (float)r;
+    }
+    return Q4_OK;
+}
+// "none" | "linear,factor=4" | "llama3,factor=8,low=1,high=4,orig=8192"
+int q4_parse_rope_scaling(const char* text, q4_rope_scaling* out) {
+    if (!text || !out) return Q4_ERR_ARG;
+    const char* end = strchr(text, ',');
+    if (!end) end = text + strlen(text);
+    const size_t kl = (size_t)(end - text);
+    q4_rope_scaling r = {};
+    if (kl == 4 && !strncmp(text, "none", 4)) r.kind = Q4_ROPE_NONE;
+    else if (kl == 6 && !strncmp(text, "linear", 6)) r.kind = Q4_ROPE_LINEAR;
+    else if (kl == 6 && !strncmp(text, "llama3", 6)) r.kind = Q4_ROPE_LLAMA3;
+    else return Q4_ERR_ARG;
+    const char* const keys[] = {"factor", "low", "high", "orig"};
+    const int n_keys = r.kind == Q4_ROPE_LINEAR ? 1 : r.kind == Q4_ROPE_LLAMA3 ? 4 : 0;
+    int seen = 0;
+    const char* p = *end ? end + 1 : end;
+    if (*end && !*p) return Q4_ERR_ARG;                        // a trailing comma
+    while (*p) {
+        const char* eq = strchr(p, '=');
+        end = strchr(p, ',');
+        if (!end) end = p + strlen(p);
+        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
+        char key[32], val[48];
+        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
+        memcpy(key, p, eq - p); key[eq - p] = 0;
+        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        int k = 0;
+        while (k < n_keys && strcmp(key, keys[k])) k++;
+        if (k == n_keys || (seen & (1 << k))) return Q4_ERR_ARG;
+        seen |= 1 << k;
+        if (!((val[0] >= '0' && val[0] <= '9') || val[0] == '.')) return Q4_ERR_ARG;     // (no sign, no leading blank, no "inf" / "nan")
+        char* rest = nullptr;
+        if (k == 3) {
+            const long v = strtol(val, &rest, 10);
+            if (*rest || v < 1 || v > 0x7fffffffL) return Q4_ERR_ARG;
+            r.original_max_position = (int)v;
+        } else {
+            const float v = strtof(val, &rest);
+            if (*rest || !isfinite(v)) return Q4_ERR_ARG;
+            (k == 0 ? r.factor : k == 1 ? r.low_freq_factor : r.high_freq_factor) = v;
+        }
+        p = *end ? end + 1 : end;
+        if (*end && !*p) return Q4_ERR_ARG;
+    }
+    if (seen != (1 << n_keys) - 1 || !rope_scaling_ok(&r)) return Q4_ERR_ARG;
+    *out = r;
+    return Q4_OK;
+}
 
 double q4_kv_stream_price(const RunState* s) { const Model* m = model_of(s); return m ? m->kv_price : 0.0; }
 

@@ -77,6 +77,8 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
     const int kv_mul = p->n_heads / p->n_kv_heads;
     const Model* m = model_of(s);
     const float2* rope_table = m ? m->rope_table : nullptr;
+    const bool scaled = m && m->rope.kind != Q4_ROPE_NONE;     // RoPE scaling: every rotation from the model's table (level 0: from its frequencies), never from rope_theta
+    if (scaled && (!rope_table || !m->inv_freq_dev)) return Q4_ERR_ARG;
     unsigned* sync = m ? m->sync : nullptr;
     const bool kv8 = m && m->kv_format == Q4_KV_FP8;
     uint8_t* const k8 = (uint8_t*)s->key_cache;     // (FP8 models: the caches are bytes)
@@ -113,7 +115,8 @@ int q4::run_network(const int* pPos, const Config* p, RunState* s, const Transfo
                 Q4_TRY(q4_matmul_q4(s->key_cache + loff, s->xb, &L->wq_k, dim, kv_dim, 0, 0, pPos));
                 Q4_TRY(q4_matmul_q4(s->value_cache + loff, s->xb, &L->wq_v, dim, kv_dim, 0, 0, pPos));
             }
-            Q4_TRY(q4_rope_rotation(s->q, s->key_cache + loff, p->n_heads, p->n_kv_heads, head_size, pPos, 0, p->rope_theta));   // :317
+            if (scaled) Q4_TRY(q4_rope_rotation_freqs(s->q, s->key_cache + loff, p->n_heads, p->n_kv_heads, head_size, pPos, 0, m->inv_freq_dev));
+            else Q4_TRY(q4_rope_rotation(s->q, s->key_cache + loff, p->n_heads, p->n_kv_heads, head_size, pPos, 0, p->rope_theta));   // :317
         }
         if (kv8) {
             const size_t eoff = (size_t)l * p->n_kv_heads * p->seq_len;

@@ -9,6 +9,8 @@
 // The blob, little-endian: a 48-byte header {u32 magic "Q4SN", u32 version 1, i32 kv_format, i32 n_layers, i32 n_kv_heads, i32 head_size, i32 n_pos,
 // f32 rope_theta, u64 fingerprint, u64 payload_bytes}, n_pos i32 tokens, the payload. q4_snapshot_check accepts a blob only when every count is in
 // range and `bytes` is exactly what the header implies, computed in 64 bits with overflow checks before anything is allocated.
+// fingerprint is Model::fingerprint: the checkpoint file's, and for a model with RoPE scaling that mixed with the fp32 bits of its frequencies (q4_model.hip) --
+// rows rotated by other frequencies are refused by the same comparison, the header stays version 1.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
