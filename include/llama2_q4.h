@@ -429,6 +429,58 @@ int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out);
 int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias,
                       const int* tokens, const int* pPos);
 
+/* ---- DRY and no-repeat-n-gram penalties (q4_dry.hip; not in the reference) ----------------------
+ * The two controls of a completion API against loops: DRY ("don't repeat yourself") penalises only the token that would extend a repeated sequence, the
+ * more the longer the match; no_repeat_ngram_size is the hard ban of the same family. Both match the sequence's suffix against its own history, on the
+ * device inside the decode step: with either on, every GENERATING step that uses the sampler -- greedy or sampled, eager or in any graph variant -- runs
+ * one one-block launch BEHIND the guide's launch and IN FRONT OF the sampling controls' launch (a guide's -inf stays -inf; top-k and min-p count what
+ * DRY left). Kept beside the Sampler, keyed by its address, like the sampling controls; off by default, and then every launch list, every captured
+ * graph and every bit is what it is without these calls. The rule reads the ring in every launch and keeps no state: nothing has to be reset, rewound
+ * or moved (resume, roll-back, snapshots and context shift need no bookkeeping).
+ *   ring = the token ring (SharedData::tokens; entries compare as plain ints), p = the step's position (*pPos before the sampler advances it),
+ *   W = ring indices [start, p], start = max(0, p + 1 - last_n) (prompt tokens count), CAP = Q4_DRY_MAX_MATCH.
+ *   R   = the number of consecutive non-breaker entries going back from ring[p] (ring[p], ring[p-1], ...), counted inside W, capped at CAP; a breaker at
+ *         ring[p] gives R = 0.
+ *   M_i, for every i in [start, p) with ring[i] == ring[p]: the largest M in [1, CAP] with ring[i-j] == ring[p-j] for all 0 <= j < M and
+ *         i - (M-1) >= start (the two ranges may overlap: periodic sequences are the main case).
+ *   t = ring[i+1] is the token that would extend the repetition; a t outside [0, n) is ignored. Per distinct t: M_t = max_i M_i, L_t = min(M_t, R).
+ * Per touched t, v = float(logits[t]):
+ *   ban: no_repeat_ngram_size = N >= 2 and M_t >= N - 1: the logit becomes -inf (0xFC00). The ban ignores breakers.
+ *   DRY: otherwise, multiplier > 0 and L_t >= allowed_length: v = v - pen[L_t], ONE IEEE fp32 subtraction, finished as step 3 of the sampling
+ *        controls: a finite value clamped to +-65504 and rounded to half (nearest even), an infinity stays, a NaN becomes 0x7E00.
+ * pen[L], L = 0 .. 64, is computed on the host (q4_dry_penalty_table): multiplier * powf(base, L - allowed_length) clamped to 3.0e38 for
+ * L >= allowed_length, 0 below; it travels in the parameter block, the kernel calls no transcendental. Every other logit keeps its 16 bits. No float
+ * atomics, no arrival order: the same input gives the same bytes on every launch. No ring entry or breaker id indexes anything before it has been
+ * checked against [0, n).
+ * Log-probability records and copyLogits are taken in front of the launch and describe the raw distribution (a greedy step's token_logprob is looked up
+ * behind the argmax); after a greedy generating step RunState::logits holds the processed logits; greedy steps are not screened while DRY is on; prompt
+ * steps launch nothing. Values and breakers may change between steps without a new capture (graphs hold the address of a small device block only). */
+enum { Q4_MAX_DRY_WINDOW = 4096, Q4_DRY_MAX_MATCH = 64 };
+typedef struct {
+    float multiplier;          /* >= 0, finite; 0: no DRY penalty */
+    float base;                /* >= 1, finite */
+    int allowed_length;        /* [1, Q4_DRY_MAX_MATCH] */
+    int last_n;                /* [0, Q4_MAX_DRY_WINDOW] */
+    int no_repeat_ngram_size;  /* 0: off, else [2, Q4_DRY_MAX_MATCH + 1] */
+} q4_dry_controls;
+/* NULL: off (the defaults {0, 1.75, 2, 1024, 0} come back). Off also: multiplier == 0 && no_repeat_ngram_size == 0, or last_n == 0. A value outside the
+ * ranges above: Q4_ERR_ARG, nothing changes, the GPU is not touched. */
+int q4_sampler_set_dry(Sampler* sampler, const q4_dry_controls* controls);
+int q4_sampler_get_dry(const Sampler* sampler, q4_dry_controls* out);
+/* Sequence breakers: single tokens a match does not reach across. ids: a host array of any number of distinct ids >= 0, copied; n = 0 clears. The step
+ * turns them into a vocabulary bitmap on the device. Q4_ERR_ARG: a negative or repeated id. An id at or above the vocabulary is found by the first step
+ * that uses the sampler with a model: that step returns Q4_ERR_ARG. */
+int q4_sampler_set_dry_breakers(Sampler* sampler, const int* ids, int n);
+/* "multiplier=0.8,base=1.75,allowed=2,last_n=1024,ngram=0": any subset of the keys in any order; a key left out keeps that value (multiplier: 0).
+ * Q4_ERR_ARG and *out untouched: an unknown key, a malformed number, a trailing comma, a value q4_sampler_set_dry refuses. */
+int q4_parse_dry(const char* text, q4_dry_controls* out);
+/* Host only: pen[0 .. 64] as above. Q4_ERR_ARG for controls the setter refuses. */
+int q4_dry_penalty_table(const q4_dry_controls* controls, float out[65]);
+/* Op-level form of the launch on the q4 stream: logits [n] halves, tokens (the ring, at least *pPos + 1 entries) and pPos (one int) device-visible --
+ * both may be NULL: no window --, breaker_ids a host array. Anything the setters refuse, or a breaker id >= n: Q4_ERR_ARG without touching the GPU. */
+int q4_dry_penalty(q4_half* logits, int n, const q4_dry_controls* controls, const int* breaker_ids, int n_breakers, const int* tokens,
+                   const int* pPos);
+
 /* ---- guided decoding (q4_guide.hip; not in the reference) --------------------------------------
  * A constraint over tokens as a finite automaton: S states (state 0 starts), a dense table next[s][i] of uint16_t, each entry a state in [0, S) or
  * Q4_GUIDE_DEAD (state s forbids token i). A guide is immutable and lives on the device: S rows of the vocabulary rounded up to 8 entries, 2 * S * V

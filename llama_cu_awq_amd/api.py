@@ -141,6 +141,22 @@ class SamplingControls(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+MAX_DRY_WINDOW = 4096
+DRY_MAX_MATCH = 64
+DRY_BREAKER_STRINGS = ("\n", ":", "\"", "*")
+
+
+class DryControls(C.Structure):
+    """q4_dry_controls; the defaults are off (multiplier 0, no n-gram ban)"""
+    _fields_ = [("multiplier", C.c_float), ("base", C.c_float), ("allowed_length", C.c_int), ("last_n", C.c_int), ("no_repeat_ngram_size", C.c_int)]
+
+    def __init__(self, multiplier=0.0, base=1.75, allowed_length=2, last_n=1024, no_repeat_ngram_size=0):
+        super().__init__(float(multiplier), float(base), int(allowed_length), int(last_n), int(no_repeat_ngram_size))
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/llama2_q4.h declares (tests/test_abi.py checks the .so exports all of them)
 SYMBOLS = [
     "q4_status_string", "q4_last_error", "q4_set_device", "q4_stream_create", "q4_stream_create_masked", "q4_stream_destroy", "q4_set_stream",
@@ -165,6 +181,7 @@ SYMBOLS = [
     "q4_shift_context", "q4_set_context_shift", "q4_get_context_shift", "q4_parse_context_shift", "q4_get_rope_row", "q4_kv_shift",
     "q4_set_rope_scaling", "q4_get_rope_scaling", "q4_rope_scaling_of", "q4_parse_rope_scaling", "q4_rope_inv_freq", "q4_get_rope_inv_freq",
     "q4_rope_rotation_freqs",
+    "q4_sampler_set_dry", "q4_sampler_get_dry", "q4_sampler_set_dry_breakers", "q4_parse_dry", "q4_dry_penalty_table", "q4_dry_penalty",
 ]
 
 _lib = None
@@ -345,6 +362,13 @@ def lib():
         L.q4_rope_inv_freq.argtypes = [C.POINTER(RopeScaling), i, f, vp]
         L.q4_get_rope_inv_freq.argtypes = [vp, vp]
         L.q4_rope_rotation_freqs.argtypes = [vp, vp, i, i, i, vp, i, vp]
+    if hasattr(L, "q4_sampler_set_dry"):           # (older builds under tools/ab.py do not have it)
+        L.q4_sampler_set_dry.argtypes = [vp, C.POINTER(DryControls)]
+        L.q4_sampler_get_dry.argtypes = [vp, C.POINTER(DryControls)]
+        L.q4_sampler_set_dry_breakers.argtypes = [vp, vp, i]
+        L.q4_parse_dry.argtypes = [C.c_char_p, C.POINTER(DryControls)]
+        L.q4_dry_penalty_table.argtypes = [C.POINTER(DryControls), vp]
+        L.q4_dry_penalty.argtypes = [vp, i, C.POINTER(DryControls), vp, i, vp, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -478,6 +502,51 @@ def process_logits(logits, n, controls=None, logit_bias=None, tokens=None, pos=N
                                   pos.ptr if pos else None))
 
 
+def parse_dry(text):
+    """q4_parse_dry: "multiplier=0.8,base=1.75,allowed=2,last_n=1024,ngram=0" -> DryControls"""
+    c = DryControls()
+    check(lib().q4_parse_dry(text.encode(), C.byref(c)))
+    return c
+
+
+def dry_penalty_table(controls=None, **kw):
+    """q4_dry_penalty_table (host only): pen[0 .. 64] float32 -- multiplier * powf(base, L - allowed_length) clamped to 3.0e38 from allowed_length on,
+    0 below"""
+    c = controls if controls is not None else DryControls(**kw)
+    out = np.empty(DRY_MAX_MATCH + 1, dtype=np.float32)
+    check(lib().q4_dry_penalty_table(C.byref(c), out.ctypes.data))
+    return out
+
+
+def _breaker_array(breakers):
+    return np.ascontiguousarray(sorted(breakers) if isinstance(breakers, (set, frozenset)) else (breakers if breakers is not None else []),
+                                dtype=np.int32).reshape(-1)
+
+
+def dry_penalty(logits, n, controls=None, breakers=None, tokens=None, pos=None, **kw):
+    """q4_dry_penalty over DevBufs: rewrites `logits` (n halves) in place -- the DRY penalty and the n-gram ban over the window of the ring `tokens`
+    (int32) that ends at the position in `pos` (one int32). controls: a DryControls, or its fields as keywords; breakers: token ids."""
+    c = controls if controls is not None else DryControls(**kw)
+    ids = _breaker_array(breakers)
+    check(lib().q4_dry_penalty(logits.ptr, n, C.byref(c), ids.ctypes.data, ids.shape[0], tokens.ptr if tokens else None, pos.ptr if pos else None))
+
+
+def dry_breaker_ids(tokenizer, strings=DRY_BREAKER_STRINGS):
+    """the ids of every token whose piece contains one of `strings` (llama.cpp's default sequence breakers, as single tokens); a byte-fallback piece
+    <0xHH> counts as its byte"""
+    needles = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in strings]
+    out = []
+    for i, piece in enumerate(tokenizer.pieces()):
+        if len(piece) == 6 and piece.startswith(b"<0x") and piece.endswith(b">"):
+            try:
+                piece = bytes([int(piece[3:5], 16)])
+            except ValueError:
+                pass
+        if any(s in piece for s in needles):
+            out.append(i)
+    return out
+
+
 class Guide:
     """q4_guide: a token automaton on the device. table: uint16 [S, V], an entry a state or GUIDE_DEAD (llama_cu_awq_amd.guide builds them from
     choices or a regular expression). Immutable; may be attached to several models of the same vocabulary; close() fails while one still holds it."""
@@ -592,7 +661,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None):
+                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -649,6 +718,10 @@ class Transformer:
                 self.set_guide(guide)
             if context_shift is not None:
                 self.set_context_shift(*context_shift)
+            if dry is not None:
+                self.set_dry(**dry)
+            if dry_breakers is not None:
+                self.set_dry_breakers(dry_breakers, tokenizer=tokenizer)
         except Exception:
             self.close()
             raise
@@ -842,6 +915,25 @@ class Transformer:
         """{token id: bias} added to the logits of every generating step (-inf bans a token); None or {}: cleared"""
         ids, bias = _bias_arrays(logit_bias)
         check(lib().q4_sampler_set_logit_bias(self.sampler, ids.ctypes.data, bias.ctypes.data, ids.shape[0]))
+
+    def set_dry(self, **kw):
+        """DRY and the no-repeat-n-gram ban inside the decode step (q4_sampler_set_dry): multiplier, base, allowed_length, last_n,
+        no_repeat_ngram_size; no keyword: off. They rewrite the logits of every generating step behind the guide and in front of the sampling controls."""
+        check(lib().q4_sampler_set_dry(self.sampler, C.byref(DryControls(**kw)) if kw else None))
+
+    def dry(self):
+        c = DryControls()
+        check(lib().q4_sampler_get_dry(self.sampler, C.byref(c)))
+        return c.as_dict()
+
+    def set_dry_breakers(self, breakers, tokenizer=None):
+        """the single-token sequence breakers of DRY: token ids, None or [] to clear, or "default" with a Tokenizer (dry_breaker_ids)"""
+        if isinstance(breakers, str):
+            if breakers != "default" or tokenizer is None:
+                raise ValueError('dry_breakers: token ids, or "default" together with tokenizer=<Tokenizer>')
+            breakers = dry_breaker_ids(tokenizer)
+        ids = _breaker_array(breakers)
+        check(lib().q4_sampler_set_dry_breakers(self.sampler, ids.ctypes.data, ids.shape[0]))
 
     def set_guide(self, guide):
         """Guided decoding (q4_set_guide): a Guide, or None for off. Every generating step then masks what the automaton's state forbids; the state

@@ -541,6 +541,37 @@ int q4_parse_args(int argc, char** argv, q4_cli_args* a) {
     return 0;
 }
 
+// Q4_DRY_BREAKERS: "default" -- every token whose piece holds a newline, ':', '"' or '*' (a byte-fallback piece <0xHH> counts as its byte) -- or a list
+// of ids; false: not a list of numbers below the vocabulary
+static bool dry_breakers_from(const char* text, const struct Tokenizer* tokenizer, int vocab, std::vector<int>* ids) {
+    if (strcmp(text, "default") == 0) {
+        for (int id = 0; id < vocab; id++) {
+            const char* piece = nullptr;
+            int len = 0;
+            if (q4_tokenizer_piece(tokenizer, id, &piece, &len) || len <= 0) continue;
+            char byte = 0;
+            if (len == 6 && !memcmp(piece, "<0x", 3) && piece[5] == '>' && isxdigit((unsigned char)piece[3]) && isxdigit((unsigned char)piece[4])) {
+                const char hex[3] = {piece[3], piece[4], 0};
+                byte = (char)strtol(hex, nullptr, 16);
+                piece = &byte;
+                len = 1;
+            }
+            for (int i = 0; i < len; i++)
+                if (piece[i] == '\n' || piece[i] == ':' || piece[i] == '"' || piece[i] == '*') { ids->push_back(id); break; }
+        }
+        return true;
+    }
+    for (const char* p = text; *p;) {
+        if (*p < '0' || *p > '9') return false;
+        char* rest = nullptr;
+        const long v = strtol(p, &rest, 10);
+        if (v >= vocab || (*rest && *rest != ',') || (*rest == ',' && !rest[1])) return false;
+        ids->push_back((int)v);
+        p = *rest ? rest + 1 : rest;
+    }
+    return true;
+}
+
 int q4_main(int argc, char** argv) {
     q4_cli_args a;
     if (q4_parse_args(argc, argv, &a)) { error_usage_text(argv[0]); exit(EXIT_FAILURE); }
@@ -563,6 +594,13 @@ int q4_main(int argc, char** argv) {
     q4_sampling_controls controls;
     if (sampling && *sampling && q4_parse_sampling_controls(sampling, &controls)) {
         fprintf(stderr, "Q4_SAMPLING: cannot use '%s' (keys: top_k, min_p, repeat_penalty, last_n, presence, frequency; e.g. top_k=40,repeat_penalty=1.1)\n", sampling);
+        exit(EXIT_FAILURE);
+    }
+    // ... and DRY / the n-gram ban (q4_parse_dry): Q4_DRY="multiplier=0.8,ngram=4"; Q4_DRY_BREAKERS: a comma-separated id list, or "default"
+    const char* dry_text = getenv("Q4_DRY");
+    q4_dry_controls dry;
+    if (dry_text && *dry_text && q4_parse_dry(dry_text, &dry)) {
+        fprintf(stderr, "Q4_DRY: cannot use '%s' (keys: multiplier, base, allowed, last_n, ngram; e.g. multiplier=0.8,base=1.75,allowed=2,last_n=1024)\n", dry_text);
         exit(EXIT_FAILURE);
     }
 
@@ -588,6 +626,16 @@ int q4_main(int argc, char** argv) {
     Sampler sampler;
     die_on(build_sampler(&sampler, transformer.config.vocab_size, a.temperature, a.topp, a.rng_seed));
     if (sampling && *sampling) die_on(q4_sampler_set_controls(&sampler, &controls));
+    if (dry_text && *dry_text) die_on(q4_sampler_set_dry(&sampler, &dry));
+    const char* breakers = getenv("Q4_DRY_BREAKERS");
+    if (breakers && *breakers) {
+        std::vector<int> ids;
+        if (!dry_breakers_from(breakers, tokenizer, transformer.config.vocab_size, &ids) || q4_sampler_set_dry_breakers(&sampler, ids.data(), (int)ids.size())) {
+            fprintf(stderr, "Q4_DRY_BREAKERS: cannot use '%s' (distinct token ids below %d, e.g. 13,29901 -- or default: every token with a newline, ':', '\"' or '*' in it)\n",
+                    breakers, transformer.config.vocab_size);
+            exit(EXIT_FAILURE);
+        }
+    }
 
     q4_stream_t stream;
     die_on(q4_stream_create(&stream));                                             // :700

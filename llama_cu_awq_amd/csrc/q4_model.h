@@ -79,6 +79,13 @@ const void* sampling_controls_block(const Sampler* sampler);
 int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block);
 int launch_logit_process_step(const void* block, const Config* p, RunState* s);
 void sampling_controls_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
+// q4_dry.hip. The DRY / no-repeat-n-gram settings kept beside a Sampler (q4_sampler_set_dry / _set_dry_breakers), the same five entry points as the
+// sampling controls'; the launch sits behind the guide's and in front of the sampling controls'
+bool dry_on(const Sampler* sampler);
+const void* dry_block(const Sampler* sampler);
+int dry_prepare(const Sampler* sampler, int vocab, const void** block);   // Q4_ERR_ARG: a breaker id at or above the vocabulary
+int launch_dry_step(const void* block, const Config* p, RunState* s);
+void dry_forget(const Sampler* sampler);   // frees the block and the bitmap: the graphs that hold the block are gone and the stream has drained
 // q4_guide.hip. The guide launch of a generating step, between the record launch and the sampling controls' launch; NONE over the ring positions of a
 // prompt group, or over the whole ring (both in stream order, outside any capture); what q4_free_transformer releases
 int launch_guide_step(const Model* m, const Config* p, RunState* s);

@@ -43,7 +43,8 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
 // graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
 // bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in), bit5 = the classifier as screen + refine (cls_screen.h),
 // bit6 = the sampling controls' launch (q4_logit_process.hip; the address of the Sampler's parameter block baked in, none of its values),
-// bit7 = the guide launch (q4_guide.hip; the address of the model's guide block baked in, nothing of the guide). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// bit7 = the guide launch (q4_guide.hip; the address of the model's guide block baked in, nothing of the guide),
+// bit8 = the DRY launch (q4_dry.hip; the address of the Sampler's parameter block baked in, none of its values). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -53,24 +54,25 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][256];
-    bool captured[Q4_MAX_GRAPHS][256];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][512];
+    bool captured[Q4_MAX_GRAPHS][512];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
     const void* controls;              // the parameter block the set's graphs with the sampling controls' launch read
     const void* guide;                 // the guide block the set's graphs with the guide launch read
+    const void* dry;                   // the parameter block the set's graphs with the DRY launch read
 };
 static GraphSet g_sets[GRAPH_OWNERS];
 static unsigned long long g_set_clock = 0;
 static int g_graph_captures = 0;
 // a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
 // mask: 0 drops every variant and gives the set up; 4 the sampled variants (what they have baked in is forgotten); 16 those with the record launch;
-// 64 those with the sampling controls' launch; 128 those with the guide launch
+// 64 those with the sampling controls' launch; 128 those with the guide launch; 256 those with the DRY launch
 static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 256; v++)
+        for (int v = 0; v < 512; v++)
             if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
@@ -80,6 +82,7 @@ static void drop_graphs(GraphSet& gs, int mask) {
     if (!mask || (mask & 4)) { gs.sampler = nullptr; gs.coins = nullptr; }
     if (!mask || (mask & 64)) gs.controls = nullptr;
     if (!mask || (mask & 128)) gs.guide = nullptr;
+    if (!mask || (mask & 256)) gs.dry = nullptr;
 }
 void drop_graphs_of(const RunState* s) {
     for (GraphSet& gs : g_sets)
@@ -106,11 +109,11 @@ static GraphSet& graph_set_of(const RunState* owner, const Config* p, const Tran
 
 // A step runs its classifier as screen + refine only when nothing but the greedy token is taken from its logits: a greedy generating step of a token
 // loop (may_screen: the public per-step entry points never pass it -- their callers read RunState::logits), no fp32 copy, no log-probability records, a
-// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls and no guide (their
-// launches rewrite whole logits).
+// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls, no DRY and no guide
+// (their launches rewrite whole logits).
 static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits, const Sampler* sampler) {
     return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
-           !sampling_controls_on(sampler) && !m->guide &&
+           !sampling_controls_on(sampler) && !dry_on(sampler) && !m->guide &&
            cls_screen_shape(m->screen.n, m->screen.d);
 }
 
@@ -209,6 +212,12 @@ void destroy_sampler(Sampler* sampler) {
         if (g_stream) hipStreamSynchronize(g_stream);
     }
     sampling_controls_forget(sampler);
+    if (const void* block = dry_block(sampler)) {                   // ... and so do graphs with the DRY launch
+        for (GraphSet& gs : g_sets)
+            if (gs.dry == block) drop_graphs(gs, 256);
+        if (g_stream) hipStreamSynchronize(g_stream);
+    }
+    dry_forget(sampler);
     auto cr = g_coin_rings.find(sampler);
     if (cr != g_coin_rings.end()) {
         for (GraphSet& gs : g_sets)
@@ -316,19 +325,26 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     // q4_sampler_set_controls / _set_logit_bias: a launch that rewrites the logits between the record launch and the argmax / sampler of a generating step
     const void* controls = nullptr;
     if (gen_token && sampling_controls_on(pSampler)) Q4_TRY(sampling_controls_prepare(pSampler, p->vocab_size, &controls));
-    // the record of a generating step whose logits the controls or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
+    // q4_sampler_set_dry: its launch sits behind the guide's and in front of the controls'
+    const void* dry = nullptr;
+    if (gen_token && dry_on(pSampler)) Q4_TRY(dry_prepare(pSampler, p->vocab_size, &dry));
+    // the record of a generating step whose logits the controls, DRY or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
     // step keeps the raw logits aside and looks its token up behind the argmax, the way a sampled step does
-    const bool lp_greedy = greedy && !controls && !guided, lp_pick = lpm && gen_token && (!greedy || controls || guided);
+    const bool lp_greedy = greedy && !controls && !guided && !dry, lp_pick = lpm && gen_token && (!greedy || controls || guided || dry);
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
         const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0) | (screened ? 32 : 0) |
-                            (controls ? 64 : 0) | (guided ? 128 : 0);
+                            (controls ? 64 : 0) | (guided ? 128 : 0) | (dry ? 256 : 0);
         if (guided && gs.guide != guided->guide_block) {
             drop_graphs(gs, 128);
             gs.guide = guided->guide_block;
+        }
+        if (dry && gs.dry != dry) {
+            drop_graphs(gs, 256);
+            gs.dry = dry;
         }
         if (controls && gs.controls != controls) {
             drop_graphs(gs, 64);
@@ -356,7 +372,8 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
                 if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
                 if (!rc && lpm) rc = launch_logprobs_step(lpm, p, s, gen_token, lp_greedy);   // (before the sampler: it advances the position and overwrites the logits)
                 if (!rc && guided) rc = launch_guide_step(guided, p, s);                   // (behind the records: they describe the model's raw logits;
-                if (!rc && controls) rc = launch_logit_process_step(controls, p, s);       //  the mask first: top-k counts allowed tokens)
+                if (!rc && dry) rc = launch_dry_step(dry, p, s);                           //  the mask first, then DRY: top-k counts what both left)
+                if (!rc && controls) rc = launch_logit_process_step(controls, p, s);
                 if (!rc && greedy) {
                     if (feed && i + 1 < nsteps)
                         rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
@@ -390,6 +407,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
     if (lpm) Q4_TRY(launch_logprobs_step(lpm, p, s, gen_token, lp_greedy));
     if (guided) Q4_TRY(launch_guide_step(guided, p, s));
+    if (dry) Q4_TRY(launch_dry_step(dry, p, s));
     if (controls) Q4_TRY(launch_logit_process_step(controls, p, s));
     Q4_TRY(sample_impl(pSampler, s, gen_token, true));
     return lp_pick ? launch_logprobs_pick(lpm, p, s) : Q4_OK;
