@@ -481,6 +481,62 @@ int q4_dry_penalty_table(const q4_dry_controls* controls, float out[65]);
 int q4_dry_penalty(q4_half* logits, int n, const q4_dry_controls* controls, const int* breaker_ids, int n_breakers, const int* tokens,
                    const int* pPos);
 
+/* ---- typical-p, top-n-sigma and Mirostat v2 (q4_adaptive.hip; not in the reference) -------------
+ * Three truncation rules of completion APIs that take their threshold from a statistic of the whole distribution. With one of them on, every GENERATING
+ * step that uses the sampler -- greedy or sampled, eager or in any graph variant -- runs one one-block launch BEHIND the sampling controls' launch and IN
+ * FRONT OF the argmax / sampler (order in the step: guide, DRY, controls, this; typical-p and Mirostat see what top-k and min-p left; a -inf stays -inf).
+ * Kept beside the Sampler, keyed by its address; off by default, and then every launch list, every captured graph and every bit is what it is without
+ * these calls. Values may change between steps without a new capture (graphs hold the address of a small device block only); going from off to on or
+ * back captures again. Log-probability records and copyLogits are taken in front and describe the raw distribution (a greedy step's token_logprob is
+ * looked up behind the argmax); greedy steps are not screened while it is on; prompt steps launch nothing.
+ *   v_i = float(l_i) of the half logits as the launch finds them. An entry TAKES PART iff it is finite; -inf, +inf and NaN entries are left as they are
+ *   and enter no statistic. A masked entry becomes 0xFC00 (-inf) and takes no part in the stages behind; every other entry keeps its 16 bits.
+ *   Every statistic is an fp32 sum in one fixed order (q4_logprobs.hip's: per thread runs of 32 in ascending index, the runs' totals, the tail element; a
+ *   64-lane tree; a 16-lane tree) -- the same bytes on every launch. Each operation below is ONE IEEE fp32 operation (no contraction).
+ * 1. top-n-sigma (top_n_sigma > 0): m = the largest v_i, mean = (sum v_i) / count, sigma = sqrtf((sum (v_i - mean)^2) / count),
+ *    T_s = m - top_n_sigma * sigma; entry i stays iff v_i >= T_s.
+ * 2. typical-p (typical_p < 1), on what 1 left, at temperature 1: lse = m + logf(sum expf(v_i - m)); s_i = lse - v_i; p_i = expf(-s_i);
+ *    H = sum p_i * s_i; d_i = fabsf(s_i - H). Entry i stays iff d_i <= d*, d* the smallest d_i occurring for which the fp32 sum (that order) of the p_i
+ *    with d_i <= d* is >= typical_p -- a whole tier of equal d_i stays or goes together; where even the whole sum stays below typical_p, everything stays.
+ * 3. Mirostat v2 (mirostat_tau > 0), on what 1 and 2 left, at the SAMPLER's temperature t (temperature 0: the step returns Q4_ERR_ARG). State: a ring
+ *    mu[seq_len] of float per model, by position (none: a NaN, every byte 0xFF), and a side buffer of vocab floats + {side_pos, side_lse}, both allocated
+ *    by the first step that needs them. At position p (*pPos before the sampler advances it): prev = mu[p - 1], none at p = 0.
+ *      prev none: mu_p = 2 * tau (a span starts);
+ *      else if side_pos == p - 1 and tok = tokens[p] is in [0, n) with a finite side[tok]:
+ *           surprise = (side_lse - side[tok]) * 1.44269504f; mu_p = prev - eta * (surprise - tau);
+ *      else mu_p = prev (a rewind with q4_run_transformer_at).
+ *    w_i = v_i / t; lse_t = w_max + logf(sum expf(w_i - w_max)); T_m = lse_t - mu_p * 0.693147181f; entry i stays iff w_i >= T_m; the entry of largest w
+ *    (lowest index on ties) always stays. Then mu[p] = mu_p; side[i] = w_i of the entries that stayed, -inf elsewhere; side_lse = their log-sum-exp;
+ *    side_pos = p. For Mirostat as published run with topp = 1: a top-p below 1 truncates further behind it.
+ * Prompt groups run with a sampler that has the launch on write none over their positions (with it off a prompt step launches and clears nothing, as
+ * before this feature); q4_reset_sequence and q4_resume_sequence write none over the ring (every resume passes a prompt step, so a
+ * span restarts behind it). q4_shift_context moves ring entries and records with the rows, entry n_pos - n_discard - 1 receives old entry n_pos - 1, and
+ * side_pos is rebased. Snapshots carry nothing of it. A RunState the library did not build has no rings: Mirostat is Q4_ERR_ARG there. */
+enum { Q4_ADAPTIVE_RECORD = 8 };
+typedef struct {
+    float typical_p;       /* (0, 1]; 1: off */
+    float top_n_sigma;     /* >= 0, finite; 0: off */
+    float mirostat_tau;    /* >= 0, finite; 0: Mirostat off */
+    float mirostat_eta;    /* (0, 1] */
+} q4_adaptive_controls;
+/* NULL: off (the neutral values {1, 0, 0, 0.1} come back). All of typical_p == 1, top_n_sigma == 0, mirostat_tau == 0: off. A value outside the ranges
+ * above (a NaN is outside every range): Q4_ERR_ARG, nothing changes, the GPU is not touched. */
+int q4_sampler_set_adaptive(Sampler* sampler, const q4_adaptive_controls* controls);
+int q4_sampler_get_adaptive(const Sampler* sampler, q4_adaptive_controls* out);
+/* "typical_p=0.9,top_n_sigma=1.5,mirostat_tau=5,mirostat_eta=0.1": any subset of the keys in any order, each at most once; a key left out keeps its
+ * neutral value. Q4_ERR_ARG and *out untouched: an unknown key, a key given twice, a malformed number, a trailing comma, a value the setter refuses. */
+int q4_parse_adaptive(const char* text, q4_adaptive_controls* out);
+/* The records of the launches at positions [first_pos, first_pos + n): Q4_ADAPTIVE_RECORD floats each, {T_s, H, d*, mu, T_m, kept, lse, lse_t} -- kept is
+ * the number of finite entries behind the launch as the BITS of an int; a NaN where a stage was off or no launch ran. (lse and lse_t are recorded so
+ * that the masks can be recomputed exactly from the record.) Synchronises. Q4_ERR_ARG: no launch has run with this model yet, a range outside the ring. */
+int q4_get_adaptive_records(const Transformer* t, int first_pos, int n, float* out);
+/* Op-level form of the launch on the q4 stream: logits [n] halves in place. With Mirostat on: temperature > 0, mu_ring (at least *pPos + 1 floats), side
+ * (n + 2 floats; side_pos is an int), tokens (the ring) and pPos (one int) device-visible; with Mirostat off all four may be NULL and the position is
+ * not read. record: Q4_ADAPTIVE_RECORD floats on the device, or NULL. Q4_ERR_ARG without touching the GPU: anything the setter refuses, Mirostat with a
+ * temperature that is not above 0 or a missing pointer. */
+int q4_adaptive_mask(q4_half* logits, int n, const q4_adaptive_controls* controls, float temperature, float* mu_ring, float* side, const int* tokens,
+                     const int* pPos, float* record);
+
 /* ---- guided decoding (q4_guide.hip; not in the reference) --------------------------------------
  * A constraint over tokens as a finite automaton: S states (state 0 starts), a dense table next[s][i] of uint16_t, each entry a state in [0, S) or
  * Q4_GUIDE_DEAD (state s forbids token i). A guide is immutable and lives on the device: S rows of the vocabulary rounded up to 8 entries, 2 * S * V

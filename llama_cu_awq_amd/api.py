@@ -157,6 +157,21 @@ class DryControls(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+ADAPTIVE_RECORD = 8
+ADAPTIVE_RECORD_FIELDS = ("T_s", "H", "d_star", "mu", "T_m", "kept", "lse", "lse_t")
+
+
+class AdaptiveControls(C.Structure):
+    """q4_adaptive_controls; the defaults are off (typical_p 1, top_n_sigma 0, mirostat_tau 0)"""
+    _fields_ = [("typical_p", C.c_float), ("top_n_sigma", C.c_float), ("mirostat_tau", C.c_float), ("mirostat_eta", C.c_float)]
+
+    def __init__(self, typical_p=1.0, top_n_sigma=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+        super().__init__(float(typical_p), float(top_n_sigma), float(mirostat_tau), float(mirostat_eta))
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/llama2_q4.h declares (tests/test_abi.py checks the .so exports all of them)
 SYMBOLS = [
     "q4_status_string", "q4_last_error", "q4_set_device", "q4_stream_create", "q4_stream_create_masked", "q4_stream_destroy", "q4_set_stream",
@@ -182,6 +197,7 @@ SYMBOLS = [
     "q4_set_rope_scaling", "q4_get_rope_scaling", "q4_rope_scaling_of", "q4_parse_rope_scaling", "q4_rope_inv_freq", "q4_get_rope_inv_freq",
     "q4_rope_rotation_freqs",
     "q4_sampler_set_dry", "q4_sampler_get_dry", "q4_sampler_set_dry_breakers", "q4_parse_dry", "q4_dry_penalty_table", "q4_dry_penalty",
+    "q4_sampler_set_adaptive", "q4_sampler_get_adaptive", "q4_parse_adaptive", "q4_get_adaptive_records", "q4_adaptive_mask",
 ]
 
 _lib = None
@@ -369,6 +385,12 @@ def lib():
         L.q4_parse_dry.argtypes = [C.c_char_p, C.POINTER(DryControls)]
         L.q4_dry_penalty_table.argtypes = [C.POINTER(DryControls), vp]
         L.q4_dry_penalty.argtypes = [vp, i, C.POINTER(DryControls), vp, i, vp, vp]
+    if hasattr(L, "q4_sampler_set_adaptive"):      # (older builds under tools/ab.py do not have it)
+        L.q4_sampler_set_adaptive.argtypes = [vp, C.POINTER(AdaptiveControls)]
+        L.q4_sampler_get_adaptive.argtypes = [vp, C.POINTER(AdaptiveControls)]
+        L.q4_parse_adaptive.argtypes = [C.c_char_p, C.POINTER(AdaptiveControls)]
+        L.q4_get_adaptive_records.argtypes = [vp, i, i, vp]
+        L.q4_adaptive_mask.argtypes = [vp, i, C.POINTER(AdaptiveControls), f, vp, vp, vp, vp, vp]
     if _use_prof:
         for name, at in (("q4_set_gemv_tune", [i, i, i]), ("q4_set_gemv_early", [i, i]), ("q4_set_half_tail", [i]),
                          ("q4_set_ksplit", [i]), ("q4_set_ablate", [i]), ("q4_set_skip_mask", [i]),
@@ -547,6 +569,30 @@ def dry_breaker_ids(tokenizer, strings=DRY_BREAKER_STRINGS):
     return out
 
 
+def parse_adaptive(text):
+    """q4_parse_adaptive: "typical_p=0.9,top_n_sigma=1.5,mirostat_tau=5,mirostat_eta=0.1" -> AdaptiveControls"""
+    c = AdaptiveControls()
+    check(lib().q4_parse_adaptive(text.encode(), C.byref(c)))
+    return c
+
+
+def adaptive_record(raw):
+    """one raw record (ADAPTIVE_RECORD float32) as a dict: T_s, H, d_star, mu, T_m, lse, lse_t floats (NaN: the stage was off), kept an int"""
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    out = {k: np.float32(raw[j]) for j, k in enumerate(ADAPTIVE_RECORD_FIELDS)}
+    out["kept"] = int(raw[5:6].view(np.int32)[0])
+    return out
+
+
+def adaptive_mask(logits, n, controls=None, temperature=1.0, mu_ring=None, side=None, tokens=None, pos=None, record=None, **kw):
+    """q4_adaptive_mask over DevBufs: top-n-sigma, typical-p and Mirostat v2 write -inf over `logits` (n halves) in place. controls: an
+    AdaptiveControls, or its fields as keywords. With Mirostat: mu_ring (float32 by position), side (n + 2 float32), tokens (the ring, int32), pos (one
+    int32) and a temperature above 0. record: ADAPTIVE_RECORD float32 (adaptive_record reads them)."""
+    c = controls if controls is not None else AdaptiveControls(**kw)
+    check(lib().q4_adaptive_mask(logits.ptr, n, C.byref(c), float(temperature), mu_ring.ptr if mu_ring else None, side.ptr if side else None,
+                                 tokens.ptr if tokens else None, pos.ptr if pos else None, record.ptr if record else None))
+
+
 class Guide:
     """q4_guide: a token automaton on the device. table: uint16 [S, V], an entry a state or GUIDE_DEAD (llama_cu_awq_amd.guide builds them from
     choices or a regular expression). Immutable; may be attached to several models of the same vocabulary; close() fails while one still holds it."""
@@ -661,7 +707,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None):
+                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -722,6 +768,8 @@ class Transformer:
                 self.set_dry(**dry)
             if dry_breakers is not None:
                 self.set_dry_breakers(dry_breakers, tokenizer=tokenizer)
+            if adaptive is not None:
+                self.set_adaptive(**adaptive)
         except Exception:
             self.close()
             raise
@@ -934,6 +982,22 @@ class Transformer:
             breakers = dry_breaker_ids(tokenizer)
         ids = _breaker_array(breakers)
         check(lib().q4_sampler_set_dry_breakers(self.sampler, ids.ctypes.data, ids.shape[0]))
+
+    def set_adaptive(self, **kw):
+        """typical-p, top-n-sigma and Mirostat v2 inside the decode step (q4_sampler_set_adaptive): typical_p, top_n_sigma, mirostat_tau, mirostat_eta;
+        no keyword: off. They mask the logits of every generating step behind the sampling controls and in front of the argmax / sampler."""
+        check(lib().q4_sampler_set_adaptive(self.sampler, C.byref(AdaptiveControls(**kw)) if kw else None))
+
+    def adaptive(self):
+        c = AdaptiveControls()
+        check(lib().q4_sampler_get_adaptive(self.sampler, C.byref(c)))
+        return c.as_dict()
+
+    def adaptive_records(self, first_pos, n):
+        """the launch's records at positions first_pos .. first_pos + n - 1 as float32 [n, ADAPTIVE_RECORD] (adaptive_record reads a row); synchronises"""
+        out = np.empty((n, ADAPTIVE_RECORD), dtype=np.float32)
+        check(lib().q4_get_adaptive_records(self.h, first_pos, n, out.ctypes.data))
+        return out
 
     def set_guide(self, guide):
         """Guided decoding (q4_set_guide): a Guide, or None for off. Every generating step then masks what the automaton's state forbids; the state

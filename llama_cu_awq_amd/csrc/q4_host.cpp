@@ -603,6 +603,13 @@ int q4_main(int argc, char** argv) {
         fprintf(stderr, "Q4_DRY: cannot use '%s' (keys: multiplier, base, allowed, last_n, ngram; e.g. multiplier=0.8,base=1.75,allowed=2,last_n=1024)\n", dry_text);
         exit(EXIT_FAILURE);
     }
+    // ... and typical-p / top-n-sigma / Mirostat v2 (q4_parse_adaptive): Q4_ADAPTIVE="typical_p=0.9" or "mirostat_tau=5,mirostat_eta=0.1"
+    const char* adaptive_text = getenv("Q4_ADAPTIVE");
+    q4_adaptive_controls adaptive;
+    if (adaptive_text && *adaptive_text && q4_parse_adaptive(adaptive_text, &adaptive)) {
+        fprintf(stderr, "Q4_ADAPTIVE: cannot use '%s' (keys: typical_p, top_n_sigma, mirostat_tau, mirostat_eta; e.g. typical_p=0.9 or mirostat_tau=5,mirostat_eta=0.1)\n", adaptive_text);
+        exit(EXIT_FAILURE);
+    }
 
     Transformer transformer;
     int rc = q4_build_transformer(&transformer, a.checkpoint_path, a.perplexity);
@@ -627,6 +634,7 @@ int q4_main(int argc, char** argv) {
     die_on(build_sampler(&sampler, transformer.config.vocab_size, a.temperature, a.topp, a.rng_seed));
     if (sampling && *sampling) die_on(q4_sampler_set_controls(&sampler, &controls));
     if (dry_text && *dry_text) die_on(q4_sampler_set_dry(&sampler, &dry));
+    if (adaptive_text && *adaptive_text) die_on(q4_sampler_set_adaptive(&sampler, &adaptive));
     const char* breakers = getenv("Q4_DRY_BREAKERS");
     if (breakers && *breakers) {
         std::vector<int> ids;

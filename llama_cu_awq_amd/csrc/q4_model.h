@@ -40,6 +40,10 @@ struct Model {
     int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)
     int guide_len = 0;
     void* guide_block = nullptr;    // what the guide launch reads: {table, ring, sizes}; captured graphs hold its address
+    float* adaptive_mu = nullptr;   // q4_sampler_set_adaptive: ONE allocation made by the first step that runs the launch with this model, kept until q4_free_transformer --
+    float* adaptive_rec = nullptr;  // Mirostat's mu by position [adaptive_len = seq_len] (every byte 0xFF, a NaN: none), the records [adaptive_len][Q4_ADAPTIVE_RECORD]
+    float* adaptive_side = nullptr; // and the side buffer [vocab + 2]: the kept entries' w of the last launch, {side_pos (an int), side_lse}
+    int adaptive_len = 0;
     unsigned long long fingerprint = 0;   // of the checkpoint file (q4_build_transformer): the header without seq_len, the file's size, its first and last 64 KiB; what a snapshot is matched by
     int shift_keep = 0, shift_discard = 0;   // q4_set_context_shift: what the library's own token loops shift by at seq_len; discard 0: off
     int shifted_keep = -1;          // the smallest n_keep of the q4_shift_context calls since the last q4_reset_sequence, -1: none -- rows above it are not "computed from the ring's tokens" (q4_common_prefix)
@@ -86,6 +90,19 @@ const void* dry_block(const Sampler* sampler);
 int dry_prepare(const Sampler* sampler, int vocab, const void** block);   // Q4_ERR_ARG: a breaker id at or above the vocabulary
 int launch_dry_step(const void* block, const Config* p, RunState* s);
 void dry_forget(const Sampler* sampler);   // frees the block and the bitmap: the graphs that hold the block are gone and the stream has drained
+// q4_adaptive.hip. The typical-p / top-n-sigma / Mirostat settings kept beside a Sampler (q4_sampler_set_adaptive), the same five entry points; the
+// launch sits behind the sampling controls' and in front of the argmax / sampler. _prepare also allocates the model's rings on first use (m null: a
+// RunState the library did not build -- no rings, no records, Mirostat is Q4_ERR_ARG) and refuses Mirostat at temperature 0. NONE over the ring
+// positions of a prompt group or over the whole ring (in stream order, outside any capture; nothing without rings); the move of q4_shift_context
+bool adaptive_on(const Sampler* sampler);
+const void* adaptive_block(const Sampler* sampler);
+int adaptive_prepare(const Sampler* sampler, Model* m, const Config* p, const void** block);
+int launch_adaptive_step(const void* block, const Model* m, const Config* p, RunState* s);
+void adaptive_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
+int adaptive_clear_positions(const Model* m, int pos, int nsteps);
+int adaptive_clear_ring(const Model* m);
+int adaptive_shift(const Model* m, int vocab, int n_pos, int first, int M, int D);
+void adaptive_release(Model* m);
 // q4_guide.hip. The guide launch of a generating step, between the record launch and the sampling controls' launch; NONE over the ring positions of a
 // prompt group, or over the whole ring (both in stream order, outside any capture); what q4_free_transformer releases
 int launch_guide_step(const Model* m, const Config* p, RunState* s);

@@ -499,6 +499,7 @@ void q4_free_transformer(Transformer* t) {                                      
         Model& m = it->second;
         hipDeviceSynchronize();
         guide_release(&m);
+        adaptive_release(&m);
         for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.inv_freq_dev, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);

@@ -44,7 +44,8 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
 // bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in), bit5 = the classifier as screen + refine (cls_screen.h),
 // bit6 = the sampling controls' launch (q4_logit_process.hip; the address of the Sampler's parameter block baked in, none of its values),
 // bit7 = the guide launch (q4_guide.hip; the address of the model's guide block baked in, nothing of the guide),
-// bit8 = the DRY launch (q4_dry.hip; the address of the Sampler's parameter block baked in, none of its values). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// bit8 = the DRY launch (q4_dry.hip; the address of the Sampler's parameter block baked in, none of its values),
+// bit9 = the adaptive truncation launch (q4_adaptive.hip; the addresses of the Sampler's parameter block and of the model's rings baked in). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -54,25 +55,26 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][512];
-    bool captured[Q4_MAX_GRAPHS][512];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][1024];
+    bool captured[Q4_MAX_GRAPHS][1024];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
     const void* controls;              // the parameter block the set's graphs with the sampling controls' launch read
     const void* guide;                 // the guide block the set's graphs with the guide launch read
     const void* dry;                   // the parameter block the set's graphs with the DRY launch read
+    const void* adaptive;              // the parameter block the set's graphs with the adaptive truncation launch read
 };
 static GraphSet g_sets[GRAPH_OWNERS];
 static unsigned long long g_set_clock = 0;
 static int g_graph_captures = 0;
 // a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
 // mask: 0 drops every variant and gives the set up; 4 the sampled variants (what they have baked in is forgotten); 16 those with the record launch;
-// 64 those with the sampling controls' launch; 128 those with the guide launch; 256 those with the DRY launch
+// 64 those with the sampling controls' launch; 128 those with the guide launch; 256 those with the DRY launch; 512 those with the adaptive truncation launch
 static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 512; v++)
+        for (int v = 0; v < 1024; v++)
             if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
@@ -83,6 +85,7 @@ static void drop_graphs(GraphSet& gs, int mask) {
     if (!mask || (mask & 64)) gs.controls = nullptr;
     if (!mask || (mask & 128)) gs.guide = nullptr;
     if (!mask || (mask & 256)) gs.dry = nullptr;
+    if (!mask || (mask & 512)) gs.adaptive = nullptr;
 }
 void drop_graphs_of(const RunState* s) {
     for (GraphSet& gs : g_sets)
@@ -109,11 +112,11 @@ static GraphSet& graph_set_of(const RunState* owner, const Config* p, const Tran
 
 // A step runs its classifier as screen + refine only when nothing but the greedy token is taken from its logits: a greedy generating step of a token
 // loop (may_screen: the public per-step entry points never pass it -- their callers read RunState::logits), no fp32 copy, no log-probability records, a
-// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls, no DRY and no guide
-// (their launches rewrite whole logits).
+// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls, no DRY, no adaptive
+// truncation and no guide (their launches rewrite whole logits).
 static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits, const Sampler* sampler) {
     return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
-           !sampling_controls_on(sampler) && !dry_on(sampler) && !m->guide &&
+           !sampling_controls_on(sampler) && !dry_on(sampler) && !adaptive_on(sampler) && !m->guide &&
            cls_screen_shape(m->screen.n, m->screen.d);
 }
 
@@ -218,6 +221,12 @@ void destroy_sampler(Sampler* sampler) {
         if (g_stream) hipStreamSynchronize(g_stream);
     }
     dry_forget(sampler);
+    if (const void* block = adaptive_block(sampler)) {              // ... and with the adaptive truncation launch
+        for (GraphSet& gs : g_sets)
+            if (gs.adaptive == block) drop_graphs(gs, 512);
+        if (g_stream) hipStreamSynchronize(g_stream);
+    }
+    adaptive_forget(sampler);
     auto cr = g_coin_rings.find(sampler);
     if (cr != g_coin_rings.end()) {
         for (GraphSet& gs : g_sets)
@@ -321,6 +330,12 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     // carries the guide launch between the record launch and the controls' launch
     const Model* guided = lpm && lpm->guide ? lpm : nullptr;
     if (guided && !gen_token) { Q4_TRY(guide_clear_positions(guided, pos, nsteps)); guided = nullptr; }
+    // q4_sampler_set_adaptive: Mirostat's mu is state by position like the guide's -- a prompt group puts NONE at its positions (only while the sampler has the launch on, as the guide's clearing needs a guide); a generating step
+    // carries the launch behind the controls' launch
+    Model* const mdl = model_of(s);
+    if (mdl && mdl->adaptive_mu && !gen_token && adaptive_on(pSampler)) Q4_TRY(adaptive_clear_positions(mdl, pos, nsteps));
+    const void* adaptive = nullptr;
+    if (gen_token && adaptive_on(pSampler)) Q4_TRY(adaptive_prepare(pSampler, mdl, p, &adaptive));
     if (lpm && lpm->logprobs_k < 0) lpm = nullptr;
     // q4_sampler_set_controls / _set_logit_bias: a launch that rewrites the logits between the record launch and the argmax / sampler of a generating step
     const void* controls = nullptr;
@@ -328,16 +343,16 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     // q4_sampler_set_dry: its launch sits behind the guide's and in front of the controls'
     const void* dry = nullptr;
     if (gen_token && dry_on(pSampler)) Q4_TRY(dry_prepare(pSampler, p->vocab_size, &dry));
-    // the record of a generating step whose logits the controls, DRY or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
+    // the record of a generating step whose logits the controls, DRY, the adaptive truncation or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
     // step keeps the raw logits aside and looks its token up behind the argmax, the way a sampled step does
-    const bool lp_greedy = greedy && !controls && !guided && !dry, lp_pick = lpm && gen_token && (!greedy || controls || guided || dry);
+    const bool lp_greedy = greedy && !controls && !guided && !dry && !adaptive, lp_pick = lpm && gen_token && (!greedy || controls || guided || dry || adaptive);
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
         const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0) | (screened ? 32 : 0) |
-                            (controls ? 64 : 0) | (guided ? 128 : 0) | (dry ? 256 : 0);
+                            (controls ? 64 : 0) | (guided ? 128 : 0) | (dry ? 256 : 0) | (adaptive ? 512 : 0);
         if (guided && gs.guide != guided->guide_block) {
             drop_graphs(gs, 128);
             gs.guide = guided->guide_block;
@@ -349,6 +364,10 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
         if (controls && gs.controls != controls) {
             drop_graphs(gs, 64);
             gs.controls = controls;
+        }
+        if (adaptive && gs.adaptive != adaptive) {
+            drop_graphs(gs, 512);
+            gs.adaptive = adaptive;
         }
         CoinRing* ring = nullptr;
         if (!greedy) {     // the sampling kernel is part of the graph: its temperature, top-p, scratch and coin ring are baked in
@@ -374,6 +393,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
                 if (!rc && guided) rc = launch_guide_step(guided, p, s);                   // (behind the records: they describe the model's raw logits;
                 if (!rc && dry) rc = launch_dry_step(dry, p, s);                           //  the mask first, then DRY: top-k counts what both left)
                 if (!rc && controls) rc = launch_logit_process_step(controls, p, s);
+                if (!rc && adaptive) rc = launch_adaptive_step(adaptive, mdl, p, s);        // (typical-p and Mirostat see what top-k and min-p left)
                 if (!rc && greedy) {
                     if (feed && i + 1 < nsteps)
                         rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
@@ -409,6 +429,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     if (guided) Q4_TRY(launch_guide_step(guided, p, s));
     if (dry) Q4_TRY(launch_dry_step(dry, p, s));
     if (controls) Q4_TRY(launch_logit_process_step(controls, p, s));
+    if (adaptive) Q4_TRY(launch_adaptive_step(adaptive, mdl, p, s));
     Q4_TRY(sample_impl(pSampler, s, gen_token, true));
     return lp_pick ? launch_logprobs_pick(lpm, p, s) : Q4_OK;
 }
@@ -422,6 +443,7 @@ static int begin_sequence(RunState* s, const int* tokens, int num_tokens, int st
     if (g_rearm_after > 0 && --g_rearm_after == 0 && g_fusion == 1) { g_fusion = g_rearm_level; q4_reset_graphs(); }   // probation over
     Model* m = model_of(s);
     if (m && m->guide) Q4_TRY(guide_clear_ring(m));        // a new sequence starts at the guide's state 0
+    if (m) Q4_TRY(adaptive_clear_ring(m));                 // ... and a Mirostat span at 2 * tau
     Q4_TRY(clear_handoff_state(s, m, false));     // counters and granules; the error word [0] stays until q4_handoff_status reads it
     Q4_HIP(hipStreamSynchronize(g_stream));
     if (m && start_pos == 0) { m->rows_suspect = false; m->shifted_keep = -1; }   // every row the sequence reads is written again
@@ -498,6 +520,7 @@ int q4_shift_context(Transformer* t, int n_pos, int n_keep, int n_discard, int n
         Q4_TRY(shift_ring_rows(m->guide_state, sizeof(int), first, M, D));
         if (new_pos >= 1) Q4_HIP(hipMemcpy(m->guide_state + new_pos - 1, &last, sizeof(int), hipMemcpyHostToDevice));   // (M > 0: the moved entry already)
     }
+    Q4_TRY(adaptive_shift(m, p->vocab_size, n_pos, first, M, D));
     if (m->logprobs_k >= 0) {
         const size_t K = (size_t)m->logprobs_k;
         Q4_TRY(shift_ring_rows(m->lp_lse, sizeof(float), first, M, D));
