@@ -1,7 +1,7 @@
 // q4_adaptive.hip -- the three truncation rules that take their threshold from a statistic of the whole distribution: top-n-sigma, typical-p and
 // Mirostat v2, as ONE launch that masks the step's fp16 logits in place, behind the sampling controls' launch and in front of the argmax or the
 // sampler. Not in the reference. The rule is written down in llama2_q4.h.
-// ONE 1024-thread block, the partition of q4_logprobs.hip: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last whole chunk, one tail
+// ONE 1024-thread block, the partition of logit_block.h: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last whole chunk, one tail
 // element; up to 32 x 1024 logits stay in registers across the stages, larger vocabularies are read again from L2 in every pass. A masked entry IS the
 // half -inf from then on: a later stage sees it as an entry that takes no part.
 //   every statistic is a sum in ONE fixed order, that of q4_logprobs.hip: a thread adds its elements in ascending index in runs of 32 (four chunks),
@@ -22,18 +22,20 @@
 #include <vector>
 #include "q4_device.h"
 #include "q4_model.h"
+#include "sampler_side.h"
+#include "logit_block.h"
+#include "option_text.h"
 #pragma clang fp contract(off)
 using namespace q4;
 
 namespace {
 
-constexpr int AD_T = 1024, AD_W = 16, AD_Q = 4;        // threads, waves, register-resident 16-byte chunks per thread
+constexpr int AD_Q = 4;                                // register-resident 16-byte chunks per thread
 constexpr int AD_SLOTS = AD_Q * 8 + 1;                 // a thread's elements in the register form: 32 and the tail
 constexpr int AD_REC = Q4_ADAPTIVE_RECORD;
 constexpr float AD_LOG2E = 1.44269504088896340736f, AD_LN2 = 0.69314718055994530942f;
 
-// what the kernel reads: one small device block per Sampler (or the op-level launcher's), rewritten in stream order when the host changes a value,
-// so a captured graph never holds a value -- only the block's address
+// what the kernel reads: the stage's device block (sampler_side.h)
 struct AdaptiveParams {
     float typical_p;         // >= 1: off
     float top_n_sigma;       // 0: off
@@ -42,8 +44,6 @@ struct AdaptiveParams {
     int pad[3];
 };
 
-__device__ __forceinline__ unsigned half_of(const u32x4& q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu; }
-__device__ __forceinline__ void mask_half(u32x4& q, int e) { q[e >> 1] = (q[e >> 1] & ~(0xFFFFu << ((e & 1) * 16))) | (0xFC00u << ((e & 1) * 16)); }
 __device__ __forceinline__ bool takes_part(unsigned h) { return (h & 0x7FFFu) < 0x7C00u; }      // a finite half
 
 // the thread's view of the logits
@@ -61,7 +61,7 @@ __device__ __forceinline__ void each(const View& c, F f) {
     if constexpr (REG) {
 #pragma unroll
         for (int kq = 0; kq < AD_Q; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
 #pragma unroll
                 for (int e = 0; e < 8; e++) f(kq * 8 + e, u * 8 + e, half_of(c.pq[kq], e));
@@ -69,7 +69,7 @@ __device__ __forceinline__ void each(const View& c, F f) {
         }
     } else {
         for (int kq = 0; kq < c.nq; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
                 const u32x4 q = c.lv[u];
 #pragma unroll
@@ -86,7 +86,7 @@ __device__ __forceinline__ float thread_sum(const View& c, F f) {
     if constexpr (REG) {
 #pragma unroll
         for (int kq = 0; kq < AD_Q; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
 #pragma unroll
                 for (int e = 0; e < 8; e++) run += f(kq * 8 + e, u * 8 + e, half_of(c.pq[kq], e));
@@ -95,7 +95,7 @@ __device__ __forceinline__ float thread_sum(const View& c, F f) {
         total += run;                                          // one run of 32
     } else {
         for (int kq = 0; kq < c.nq; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
                 const u32x4 q = c.lv[u];
 #pragma unroll
@@ -114,7 +114,7 @@ __device__ __forceinline__ void mask_pass(View& c, F keep) {
     if constexpr (REG) {
 #pragma unroll
         for (int kq = 0; kq < AD_Q; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
@@ -125,7 +125,7 @@ __device__ __forceinline__ void mask_pass(View& c, F keep) {
         }
     } else {
         for (int kq = 0; kq < c.nq; kq++) {
-            const int u = c.tid + kq * AD_T;
+            const int u = c.tid + kq * LB_T;
             if (u < c.n8) {
                 const u32x4 q = c.lv[u];
                 u32x4 o = q;
@@ -145,24 +145,24 @@ __device__ __forceinline__ void mask_pass(View& c, F keep) {
 // Block-wide reductions. `use` counts the calls: two LDS rows take turns, so ONE barrier per call is enough (a row is written again only two calls
 // later, behind the barrier of the call in between, which every thread passes after its reads). Every thread gets the result.
 template <int N>
-__device__ __forceinline__ void block_sum(float (&v)[N], float (*red)[2 * AD_W], int& use) {
+__device__ __forceinline__ void block_sum(float (&v)[N], float (*red)[2 * LB_W], int& use) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* row = red[use++ & 1];
 #pragma unroll
     for (int i = 0; i < N; i++) {
         v[i] = wave_sum(v[i]);
-        if (lane == 0) row[i * AD_W + wave] = v[i];
+        if (lane == 0) row[i * LB_W + wave] = v[i];
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < N; i++) v[i] = row16_sum(row[i * AD_W + (lane & 15)]);
+    for (int i = 0; i < N; i++) v[i] = row16_sum(row[i * LB_W + (lane & 15)]);
 }
-__device__ __forceinline__ float block_sum1(float v, float (*red)[2 * AD_W], int& use) {
+__device__ __forceinline__ float block_sum1(float v, float (*red)[2 * LB_W], int& use) {
     float a[1] = {v};
     block_sum<1>(a, red, use);
     return a[0];
 }
-__device__ __forceinline__ float block_max(float v, float (*red)[2 * AD_W], int& use) {
+__device__ __forceinline__ float block_max(float v, float (*red)[2 * LB_W], int& use) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* row = red[use++ & 1];
     v = wave_max(v);
@@ -170,21 +170,9 @@ __device__ __forceinline__ float block_max(float v, float (*red)[2 * AD_W], int&
     __syncthreads();
     return row16_max(row[lane & 15]);
 }
-__device__ __forceinline__ int block_max_i(int v, float (*red)[2 * AD_W], int& use) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
-    int* row = reinterpret_cast<int*>(red[use++ & 1]);
-    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = row[0];
-#pragma unroll
-    for (int w = 1; w < AD_W; w++) s = max(s, row[w]);
-    return s;
-}
-
 // the largest value among the entries that take part, -inf: none
 template <bool REG>
-__device__ __forceinline__ float view_max(const View& c, float (*red)[2 * AD_W], int& use) {
+__device__ __forceinline__ float view_max(const View& c, float (*red)[2 * LB_W], int& use) {
     float m = -INFINITY;
     each<REG>(c, [&](int, int, unsigned h) { if (takes_part(h)) m = fmaxf(m, h2f((uint16_t)h)); });
     return block_max(m, red, use);
@@ -192,9 +180,10 @@ __device__ __forceinline__ float view_max(const View& c, float (*red)[2 * AD_W],
 
 // REG: n <= 32 x 1024. mu_ring / side / tokens / pPos null: no Mirostat. rec: AD_REC floats per record, record *pPos when rec_by_pos, else record 0.
 template <bool REG>
-__global__ void __launch_bounds__(AD_T) adaptive_kernel(q4_half* logits, int n, const AdaptiveParams* __restrict__ prm, float* mu_ring, float* side,
+__global__ void __launch_bounds__(LB_T) adaptive_kernel(q4_half* logits, int n, const AdaptiveParams* __restrict__ prm, float* mu_ring, float* side,
                                                         float* rec, int rec_by_pos, int seq_len, const int* tokens, const int* pPos) {
-    __shared__ float red[2][2 * AD_W];
+    __shared__ float red[2][2 * LB_W];
+    int (*const ired)[2 * LB_W] = reinterpret_cast<int (*)[2 * LB_W]>(red);     // the same two rows for logit_block.h's int maximum
     const int tid = threadIdx.x;
     const float typical_p = prm->typical_p, nsigma = prm->top_n_sigma, tau = prm->tau, eta = prm->eta, temp = prm->temperature;
     const bool miro = tau > 0.f && temp > 0.f && mu_ring != nullptr && side != nullptr && tokens != nullptr && pPos != nullptr;
@@ -223,11 +212,11 @@ __global__ void __launch_bounds__(AD_T) adaptive_kernel(q4_half* logits, int n, 
     }
 
     View c;
-    c.n = n; c.n8 = n >> 3; c.nq = REG ? AD_Q : (c.n8 + AD_T - 1) / AD_T; c.tail = c.n8 * 8 + tid; c.tid = tid; c.dirty = 0u;
+    c.n = n; c.n8 = n >> 3; c.nq = REG ? AD_Q : (c.n8 + LB_T - 1) / LB_T; c.tail = c.n8 * 8 + tid; c.tid = tid; c.dirty = 0u;
     c.lv = reinterpret_cast<u32x4*>(logits);
 #pragma unroll
     for (int kq = 0; kq < AD_Q; kq++) {
-        const int u = tid + kq * AD_T;
+        const int u = tid + kq * LB_T;
         c.pq[kq] = (REG && u < c.n8) ? c.lv[u] : (u32x4){0xFC00FC00u, 0xFC00FC00u, 0xFC00FC00u, 0xFC00FC00u};
     }
     c.th = c.tail < n ? (unsigned)logits[c.tail] : 0xFC00u;
@@ -286,7 +275,7 @@ __global__ void __launch_bounds__(AD_T) adaptive_kernel(q4_half* logits, int n, 
                 else k = key_of(h);
                 if (takes_part(h)) maxkey = max(maxkey, k);
             });
-            maxkey = block_max_i(maxkey, red, use);
+            maxkey = q4::block_max(maxkey, ired, use);
             int hi = maxkey;                                   // the mass of {key <= hi} reaches typical_p (or no set does: everything stays)
             if (mass_all >= typical_p) {
                 int lo = -1;                                   // ... that of {key <= lo} does not
@@ -323,7 +312,7 @@ __global__ void __launch_bounds__(AD_T) adaptive_kernel(q4_half* logits, int n, 
             if (!(mw >= T_m)) {
                 int first = -0x7FFFFFFF;
                 each<REG>(c, [&](int, int i, unsigned h) { if (takes_part(h) && h2f((uint16_t)h) == m) first = max(first, -i); });
-                arg = -block_max_i(first, red, use);
+                arg = -q4::block_max(first, ired, use);
             }
             mask_pass<REG>(c, [&](int, int i, unsigned h) { return h2f((uint16_t)h) / temp >= T_m || i == arg; });
             // the side buffer: w of what stayed, -inf elsewhere, and their log-sum-exp (the pass that sums is the pass that stores)
@@ -353,14 +342,14 @@ __global__ void __launch_bounds__(AD_T) adaptive_kernel(q4_half* logits, int n, 
     if constexpr (REG) {
 #pragma unroll
         for (int kq = 0; kq < AD_Q; kq++) {
-            const int u = tid + kq * AD_T;
+            const int u = tid + kq * LB_T;
             if (u < c.n8 && (c.dirty >> kq & 1u)) c.lv[u] = c.pq[kq];
         }
     }
     if (c.tail < n && (c.dirty >> AD_Q & 1u)) logits[c.tail] = (q4_half)c.th;
 }
 
-// ---- host side: validation, the per-Sampler records, the launchers ---------------------------------------------------------------------------------
+// ---- host side: validation, the per-Sampler records, the stage's row ---------------------------------------------------------------------------------
 const q4_adaptive_controls NEUTRAL = {1.f, 0.f, 0.f, 0.1f};
 
 bool finite_f(float v) { return v == v && fabsf(v) != INFINITY; }
@@ -374,25 +363,22 @@ void fill_params(AdaptiveParams* P, const q4_adaptive_controls* c, float tempera
     P->typical_p = c->typical_p; P->top_n_sigma = c->top_n_sigma; P->tau = c->mirostat_tau; P->eta = c->mirostat_eta; P->temperature = temperature;
 }
 
-// The Sampler struct is the reference's: the settings live beside it, keyed by its address (like Controls of q4_logit_process.hip)
-struct Adaptive {
+// what q4_sampler_set_adaptive keeps beside a Sampler (sampler_side.h)
+struct Adaptive : DeviceBlock<AdaptiveParams> {
     q4_adaptive_controls c = NEUTRAL;
-    AdaptiveParams host;               // what the next upload sends (pageable: the copy call returns when it has been staged)
-    AdaptiveParams* dev = nullptr;
-    bool dirty = true;                 // the device block is behind the host's values
     float temperature = -1.f;          // the sampler's temperature of the last upload
     bool on() const { return !adaptive_off(&c); }
 };
-std::map<const Sampler*, Adaptive>& registry() {
-    static std::map<const Sampler*, Adaptive> r;
+SamplerSides<Adaptive>& sides() {
+    static SamplerSides<Adaptive> r;
     return r;
 }
-AdaptiveParams* g_op_block = nullptr;  // q4_adaptive_mask's own block
+DeviceBlock<AdaptiveParams> g_op;      // q4_adaptive_mask's own block
 
 int launch(q4_half* logits, int n, const AdaptiveParams* dev, float* mu, float* side, float* rec, int rec_by_pos, int seq_len, const int* tokens,
            const int* pPos) {
-    if (n <= AD_T * AD_Q * 8) Q4_LAUNCH(adaptive_kernel<true>, dim3(1), dim3(AD_T), 0, logits, n, dev, mu, side, rec, rec_by_pos, seq_len, tokens, pPos);
-    else Q4_LAUNCH(adaptive_kernel<false>, dim3(1), dim3(AD_T), 0, logits, n, dev, mu, side, rec, rec_by_pos, seq_len, tokens, pPos);
+    if (n <= LB_T * AD_Q * 8) Q4_LAUNCH(adaptive_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, dev, mu, side, rec, rec_by_pos, seq_len, tokens, pPos);
+    else Q4_LAUNCH(adaptive_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, dev, mu, side, rec, rec_by_pos, seq_len, tokens, pPos);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -406,23 +392,10 @@ int rings_to_none(const Model* m, int first, int count) {
     return Q4_OK;
 }
 
-}  // namespace
-
-namespace q4 {
-
-bool adaptive_on(const Sampler* sampler) {
-    if (!sampler || registry().empty()) return false;
-    auto it = registry().find(sampler);
-    return it != registry().end() && it->second.on();
-}
-const void* adaptive_block(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    return it == registry().end() ? nullptr : it->second.dev;
-}
-// in front of a step (outside any capture): Mirostat against the sampler's temperature, the model's rings, the device block, the pending upload in
-// stream order
-int adaptive_prepare(const Sampler* sampler, Model* m, const Config* p, const void** block) {
-    Adaptive& r = registry()[sampler];
+// LogitStage::prepare: Mirostat against the sampler's temperature (m null: a RunState the library did not build -- no rings, no records, Mirostat is
+// Q4_ERR_ARG), the model's rings on first use, then the block, which carries the temperature
+int prepare(const Sampler* sampler, Model* m, const Config* p, const void** block) {
+    Adaptive& r = sides().of(sampler);
     if (r.c.mirostat_tau > 0.f && (!(sampler->temperature > 0.f) || !m)) {
         snprintf(g_last_error, sizeof(g_last_error), "Mirostat needs a sampler temperature above 0 and a Transformer the library built");
         return Q4_ERR_ARG;
@@ -437,30 +410,30 @@ int adaptive_prepare(const Sampler* sampler, Model* m, const Config* p, const vo
         m->adaptive_len = p->seq_len;
         Q4_HIP(hipMemsetAsync(ring, 0xFF, cells * sizeof(float), g_stream));       // none everywhere; side_pos -1
     }
-    if (!r.dev) {
-        Q4_HIP(hipMalloc((void**)&r.dev, sizeof(AdaptiveParams)));
-        r.dirty = true;
-    }
-    if (r.dirty || r.temperature != sampler->temperature) {
+    if (r.temperature != sampler->temperature) r.dirty = true;
+    if (r.stale()) {
         fill_params(&r.host, &r.c, sampler->temperature);
-        Q4_HIP(hipMemcpyAsync(r.dev, &r.host, sizeof(AdaptiveParams), hipMemcpyHostToDevice, g_stream));
-        r.dirty = false;
         r.temperature = sampler->temperature;
     }
+    Q4_TRY(r.upload());
     *block = r.dev;
     return Q4_OK;
 }
-int launch_adaptive_step(const void* block, const Model* m, const Config* p, RunState* s) {
+
+bool stage_on(const Sampler* sampler, const Model*) { return sides().on(sampler); }
+int launch_step(const void* block, const Model* m, const Config* p, RunState* s) {
     return launch(s->logits, p->vocab_size, (const AdaptiveParams*)block, m ? m->adaptive_mu : nullptr, m ? m->adaptive_side : nullptr,
                   m ? m->adaptive_rec : nullptr, 1, m ? m->adaptive_len : p->seq_len, &(s->shared_data->tokens[0]), s->pos);
 }
-// destroy_sampler: the caller has dropped the graphs that hold the block and drained the stream
-void adaptive_forget(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    if (it == registry().end()) return;
-    if (it->second.dev) (void)hipFree(it->second.dev);
-    registry().erase(it);
-}
+const void* stage_block(const Sampler* sampler) { return sides().block(sampler); }
+void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
+
+}  // namespace
+
+LogitStage q4::adaptive_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
+
+namespace q4 {
+
 int adaptive_clear_positions(const Model* m, int pos, int nsteps) { return m->adaptive_mu ? rings_to_none(m, pos, nsteps) : Q4_OK; }
 int adaptive_clear_ring(const Model* m) { return m->adaptive_mu ? rings_to_none(m, 0, m->adaptive_len) : Q4_OK; }
 // q4_shift_context (the stream has drained): mu and the records of [first, first + M) move down by D, entry new_pos - 1 receives old entry n_pos - 1,
@@ -497,16 +470,16 @@ extern "C" {
 
 int q4_sampler_set_adaptive(Sampler* sampler, const q4_adaptive_controls* controls) {
     if (!sampler || (controls && !adaptive_valid(controls))) return Q4_ERR_ARG;
-    if (!controls && registry().find(sampler) == registry().end()) return Q4_OK;       // off, and never on
-    Adaptive& r = registry()[sampler];
+    if (!controls && !sides().find(sampler)) return Q4_OK;     // off, and never on
+    Adaptive& r = sides().of(sampler);
     r.c = controls ? *controls : NEUTRAL;
     r.dirty = true;
     return Q4_OK;
 }
 int q4_sampler_get_adaptive(const Sampler* sampler, q4_adaptive_controls* out) {
     if (!sampler || !out) return Q4_ERR_ARG;
-    auto it = registry().find(sampler);
-    *out = it == registry().end() ? NEUTRAL : it->second.c;
+    const Adaptive* r = sides().find(sampler);
+    *out = r ? r->c : NEUTRAL;
     return Q4_OK;
 }
 
@@ -519,14 +492,8 @@ int q4_parse_adaptive(const char* text, q4_adaptive_controls* out) {
     unsigned seen = 0u;
     const char* p = text;
     while (*p) {
-        const char* eq = strchr(p, '=');
-        const char* end = strchr(p, ',');
-        if (!end) end = p + strlen(p);
-        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
-        char key[32], val[64];
-        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
-        memcpy(key, p, eq - p); key[eq - p] = 0;
-        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char key[OPTION_KEY_CAP], val[64];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
         const int which = !strcmp(key, "typical_p") ? 0 : !strcmp(key, "top_n_sigma") ? 1 : !strcmp(key, "mirostat_tau") ? 2 : !strcmp(key, "mirostat_eta") ? 3 : -1;
         if (which < 0 || (seen >> which & 1u)) return Q4_ERR_ARG;
         seen |= 1u << which;
@@ -534,8 +501,6 @@ int q4_parse_adaptive(const char* text, q4_adaptive_controls* out) {
         float* f = which == 0 ? &c.typical_p : which == 1 ? &c.top_n_sigma : which == 2 ? &c.mirostat_tau : &c.mirostat_eta;
         *f = strtof(val, &rest);
         if (*rest || rest == val) return Q4_ERR_ARG;
-        p = *end ? end + 1 : end;
-        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
     }
     if (!adaptive_valid(&c)) return Q4_ERR_ARG;
     *out = c;
@@ -555,12 +520,11 @@ int q4_adaptive_mask(q4_half* logits, int n, const q4_adaptive_controls* control
     if (!logits || n < 1 || !controls || !adaptive_valid(controls)) return Q4_ERR_ARG;
     if (controls->mirostat_tau > 0.f && (!(temperature > 0.f) || !finite_f(temperature) || !mu_ring || !side || !tokens || !pPos)) return Q4_ERR_ARG;
     if (adaptive_off(controls)) return Q4_OK;
-    if (!g_op_block) Q4_HIP(hipMalloc((void**)&g_op_block, sizeof(AdaptiveParams)));
-    AdaptiveParams P;
-    fill_params(&P, controls, temperature);
-    Q4_HIP(hipMemcpyAsync(g_op_block, &P, sizeof(P), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
+    fill_params(&g_op.host, controls, temperature);
+    g_op.dirty = true;
+    Q4_TRY(g_op.upload());
     const bool miro = controls->mirostat_tau > 0.f;
-    return launch(logits, n, g_op_block, miro ? mu_ring : nullptr, miro ? side : nullptr, record, 0, Q4_MAX_SEQ_LEN, miro ? tokens : nullptr,
+    return launch(logits, n, g_op.dev, miro ? mu_ring : nullptr, miro ? side : nullptr, record, 0, Q4_MAX_SEQ_LEN, miro ? tokens : nullptr,
                   miro ? pPos : nullptr);
 }
 

@@ -6,8 +6,8 @@
 //   3. the candidates -- window slots in front of the last whose token equals ring[p] -- are compacted in index order with one block prefix sum.
 //   4. candidate c goes to thread c mod 1024: it walks back at most 64 LDS entries (its match length M) and reads the token behind it.
 //   5. the per-token maximum over the COMPACTED list only (key = M * 4096 + 4095 - c: the largest M, then the first in index order): the one candidate
-//      of a token that no other beats rewrites that token's logit -- the ban, or one fp32 subtraction of pen[min(M, R)] finished as step 3 of
-//      q4_logit_process.hip. One writer per logit: no atomics, no arrival order, the same input gives the same bytes on every launch.
+//      of a token that no other beats rewrites that token's logit -- the ban, or one fp32 subtraction of pen[min(M, R)] finished by
+//      logit_block.h's finish. One writer per logit: no atomics, no arrival order, the same input gives the same bytes on every launch.
 // The vocabulary is never scanned: the cost does not depend on n. Worst case, a window of one repeated token: 4095 candidates, every M 64, 4095 x 4
 // comparisons per thread over broadcast 16-byte LDS reads. No ring entry or breaker id indexes anything before it has been checked against [0, n).
 #include <hip/hip_runtime.h>
@@ -19,17 +19,19 @@
 #include <vector>
 #include "q4_device.h"
 #include "q4_model.h"
+#include "sampler_side.h"
+#include "logit_block.h"
+#include "option_text.h"
 #pragma clang fp contract(off)
 using namespace q4;
 
 namespace {
 
-constexpr int DR_T = 1024, DR_W = 16, DR_E = 4;        // threads, waves, window entries per thread
+constexpr int DR_E = 4;                                // window entries per thread
 constexpr int DR_CAP = Q4_DRY_MAX_MATCH;
-static_assert(DR_T * DR_E == Q4_MAX_DRY_WINDOW, "four window entries per thread");
+static_assert(LB_T * DR_E == Q4_MAX_DRY_WINDOW, "four window entries per thread");
 
-// what the kernel reads: one small device block per Sampler (or the op-level launcher's), rewritten in stream order when the host changes a value,
-// so a captured graph never holds a value -- only the block's address
+// what the kernel reads: the stage's device block (sampler_side.h)
 struct DryParams {
     int last_n;              // 0: off
     int allowed;             // allowed_length
@@ -41,53 +43,13 @@ struct DryParams {
     float pen[DR_CAP + 1];   // q4_dry_penalty_table
 };
 
-// q4_logit_process.hip, step 3: a finite value clamped to the half range and rounded (RNE); an infinity stays; a NaN is 0x7E00
-__device__ __forceinline__ q4_half finish(float v) {
-    if (v != v) return (q4_half)0x7E00u;
-    if (fabsf(v) != INFINITY) v = fminf(fmaxf(v, -65504.0f), 65504.0f);
-    return (q4_half)f2h(v);
-}
-
-// block-wide maximum / exclusive prefix sum of one int per thread, as in q4_logit_process.hip: two LDS rows take turns, ONE barrier per call
-__device__ __forceinline__ int block_max(int v, int (*red)[DR_W], int& use) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
-    int* row = red[use++ & 1];
-    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = row[0];
-#pragma unroll
-    for (int w = 1; w < DR_W; w++) s = max(s, row[w]);
-    return s;
-}
-__device__ __forceinline__ int block_scan(int v, int (*red)[DR_W], int& use, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(x, off);
-        if (lane >= off) x += o;
-    }
-    int* row = red[use++ & 1];
-    if (lane == 63) row[wave] = x;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < DR_W; w++) {
-        const int r = row[w];
-        tot += r;
-        before += w < wave ? r : 0;
-    }
-    total = tot;
-    return before + x - v;
-}
-
-__global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const DryParams* __restrict__ prm, const int* tokens, const int* pPos) {
-    __shared__ __attribute__((aligned(16))) int s_win[DR_T * DR_E];      // the window, local index k = ring index - start
-    __shared__ __attribute__((aligned(16))) int s_tok[DR_T * DR_E];      // per candidate: the token behind it, -1: outside [0, n)
-    __shared__ __attribute__((aligned(16))) int s_key[DR_T * DR_E];      // per candidate: its slot k, then M * 4096 + 4095 - c
+// (finish and the block-wide int reductions: logit_block.h)
+__global__ void __launch_bounds__(LB_T) dry_kernel(q4_half* logits, int n, const DryParams* __restrict__ prm, const int* tokens, const int* pPos) {
+    __shared__ __attribute__((aligned(16))) int s_win[LB_T * DR_E];      // the window, local index k = ring index - start
+    __shared__ __attribute__((aligned(16))) int s_tok[LB_T * DR_E];      // per candidate: the token behind it, -1: outside [0, n)
+    __shared__ __attribute__((aligned(16))) int s_key[LB_T * DR_E];      // per candidate: its slot k, then M * 4096 + 4095 - c
     __shared__ float s_pen[DR_CAP + 1];
-    __shared__ int red[2][DR_W];
+    __shared__ int red[2][LB_W];
     const int tid = threadIdx.x;
     const int last_n = min(max(prm->last_n, 0), (int)Q4_MAX_DRY_WINDOW);
     if (last_n == 0 || tokens == nullptr || pPos == nullptr) return;   // (block-uniform, like every return below)
@@ -140,7 +102,7 @@ __global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const
     int myt[DR_E], mykey[DR_E];
 #pragma unroll
     for (int i = 0; i < DR_E; i++) {
-        const int c = tid + i * DR_T;
+        const int c = tid + i * LB_T;
         myt[i] = -1;
         mykey[i] = 0;
         if (c < C) {
@@ -150,7 +112,7 @@ __global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const
             int t = s_win[k + 1];
             if ((unsigned)t >= (unsigned)n) t = -1;
             myt[i] = t;
-            mykey[i] = M * (DR_T * DR_E) + (DR_T * DR_E - 1 - c);
+            mykey[i] = M * (LB_T * DR_E) + (LB_T * DR_E - 1 - c);
         }
         if (c < Cpad) {                                                // (slot c was read by this thread alone)
             s_tok[c] = myt[i];
@@ -162,7 +124,7 @@ __global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const
     // ---- 5. the candidate of a token that no other candidate of that token beats rewrites its logit
     bool lose[DR_E] = {false, false, false, false};
     if (tid < C) {
-        const int mine_n = min(DR_E, (C - tid + DR_T - 1) / DR_T);     // this thread's candidates
+        const int mine_n = min(DR_E, (C - tid + LB_T - 1) / LB_T);     // this thread's candidates
         for (int s = 0; s < Cpad; s += 4) {
             const int4 T = *reinterpret_cast<const int4*>(&s_tok[s]);
             const int4 K = *reinterpret_cast<const int4*>(&s_key[s]);
@@ -177,7 +139,7 @@ __global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const
     for (int i = 0; i < DR_E; i++) {
         const int t = myt[i];
         if (t < 0 || lose[i]) continue;
-        const int M = mykey[i] / (DR_T * DR_E);
+        const int M = mykey[i] / (LB_T * DR_E);
         if (ban_on && M >= ngram - 1) logits[t] = (q4_half)0xFC00u;
         else if (dry_on) {
             const int Lt = min(M, R);
@@ -186,7 +148,7 @@ __global__ void __launch_bounds__(DR_T) dry_kernel(q4_half* logits, int n, const
     }
 }
 
-// ---- host side: validation, the per-Sampler records, the launchers ---------------------------------------------------------------------------------
+// ---- host side: validation, the per-Sampler records, the stage's row ---------------------------------------------------------------------------------
 const q4_dry_controls DRY_DEFAULT = {0.f, 1.75f, 2, 1024, 0};
 
 bool finite_f(float v) { return v == v && fabsf(v) != INFINITY; }
@@ -226,18 +188,20 @@ void fill_params(DryParams* P, const q4_dry_controls* c, const unsigned* bitmap,
     penalty_table(c, P->pen);
 }
 
-// a device block and the breaker bitmap it points at
-struct DeviceSide {
-    DryParams host;                    // what the next upload sends (pageable: the copy call returns when it has been staged)
-    DryParams* dev = nullptr;
+// the device block and the breaker bitmap it points at
+struct DeviceSide : DeviceBlock<DryParams> {
     std::vector<unsigned> bitmap_host;
     unsigned* bitmap = nullptr;
     int bitmap_words = 0;              // allocated
+    void release() {
+        DeviceBlock<DryParams>::release();
+        if (bitmap) (void)hipFree(bitmap);
+        bitmap = nullptr; bitmap_words = 0;
+    }
 };
-// The block (allocated once) and the bitmap for a vocabulary of `vocab` tokens, uploaded in stream order. The bitmap grows only after the stream has
-// drained: a launch in flight may still read the old one.
+// The bitmap for a vocabulary of `vocab` tokens and the block, uploaded in stream order. The bitmap grows only after the stream has drained: a launch
+// in flight may still read the old one.
 int upload(DeviceSide& d, const q4_dry_controls* c, const std::vector<int>& breakers, int vocab) {
-    if (!d.dev) Q4_HIP(hipMalloc((void**)&d.dev, sizeof(DryParams)));
     const int words = breakers.empty() ? 0 : (vocab + 31) / 32;
     if (words > d.bitmap_words) {
         Q4_HIP(hipStreamSynchronize(g_stream));
@@ -252,47 +216,33 @@ int upload(DeviceSide& d, const q4_dry_controls* c, const std::vector<int>& brea
         Q4_HIP(hipMemcpyAsync(d.bitmap, d.bitmap_host.data(), (size_t)words * sizeof(unsigned), hipMemcpyHostToDevice, g_stream));
     }
     fill_params(&d.host, c, words ? d.bitmap : nullptr, words);
-    Q4_HIP(hipMemcpyAsync(d.dev, &d.host, sizeof(DryParams), hipMemcpyHostToDevice, g_stream));
-    return Q4_OK;
+    d.dirty = true;
+    return d.upload();
 }
 
-// The Sampler struct is the reference's: the settings live beside it, keyed by its address (like Controls of q4_logit_process.hip)
-struct Dry {
+// what q4_sampler_set_dry / _set_dry_breakers keep beside a Sampler (sampler_side.h)
+struct Dry : DeviceSide {
     q4_dry_controls c = DRY_DEFAULT;
     std::vector<int> breakers;
-    DeviceSide d;
-    bool dirty = true;                 // the device side is behind the host's values
     int vocab = -1;                    // the vocabulary the breaker ids were last checked against and the bitmap was built for
     bool on() const { return !dry_off(&c); }
 };
-std::map<const Sampler*, Dry>& registry() {
-    static std::map<const Sampler*, Dry> r;
+SamplerSides<Dry>& sides() {
+    static SamplerSides<Dry> r;
     return r;
 }
 DeviceSide g_op;                       // q4_dry_penalty's own block and bitmap
 
 int launch(q4_half* logits, int n, const DryParams* dev, const int* tokens, const int* pPos) {
-    Q4_LAUNCH(dry_kernel, dim3(1), dim3(DR_T), 0, logits, n, dev, tokens, pPos);
+    Q4_LAUNCH(dry_kernel, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
 
-}  // namespace
-
-namespace q4 {
-
-bool dry_on(const Sampler* sampler) {
-    if (!sampler || registry().empty()) return false;
-    auto it = registry().find(sampler);
-    return it != registry().end() && it->second.on();
-}
-const void* dry_block(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    return it == registry().end() ? nullptr : it->second.d.dev;
-}
-// in front of a step (outside any capture): the breaker ids against this model's vocabulary, the device block, the pending upload in stream order
-int dry_prepare(const Sampler* sampler, int vocab, const void** block) {
-    Dry& r = registry()[sampler];
+// LogitStage::prepare: the breaker ids against this model's vocabulary, then the bitmap and the block
+int prepare(const Sampler* sampler, Model*, const Config* p, const void** block) {
+    Dry& r = sides().of(sampler);
+    const int vocab = p->vocab_size;
     if (r.vocab != vocab) {
         if (!breakers_valid(r.breakers.data(), (int)r.breakers.size(), vocab)) {
             snprintf(g_last_error, sizeof(g_last_error), "DRY: a breaker id exceeds the vocabulary (%d)", vocab);
@@ -301,47 +251,42 @@ int dry_prepare(const Sampler* sampler, int vocab, const void** block) {
         r.vocab = vocab;
         r.dirty = true;
     }
-    if (r.dirty || !r.d.dev) {
-        Q4_TRY(upload(r.d, &r.c, r.breakers, vocab));
-        r.dirty = false;
-    }
-    *block = r.d.dev;
+    if (r.stale()) Q4_TRY(upload(r, &r.c, r.breakers, vocab));
+    *block = r.dev;
     return Q4_OK;
 }
-int launch_dry_step(const void* block, const Config* p, RunState* s) {
+
+bool stage_on(const Sampler* sampler, const Model*) { return sides().on(sampler); }
+int launch_step(const void* block, const Model*, const Config* p, RunState* s) {
     return launch(s->logits, p->vocab_size, (const DryParams*)block, &(s->shared_data->tokens[0]), s->pos);
 }
-// destroy_sampler: the caller has dropped the graphs that hold the block and drained the stream
-void dry_forget(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    if (it == registry().end()) return;
-    if (it->second.d.dev) (void)hipFree(it->second.d.dev);
-    if (it->second.d.bitmap) (void)hipFree(it->second.d.bitmap);
-    registry().erase(it);
-}
+const void* stage_block(const Sampler* sampler) { return sides().block(sampler); }
+void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
 
-}  // namespace q4
+}  // namespace
+
+LogitStage q4::dry_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
 
 extern "C" {
 
 int q4_sampler_set_dry(Sampler* sampler, const q4_dry_controls* controls) {
     if (!sampler || (controls && !dry_valid(controls))) return Q4_ERR_ARG;
-    if (!controls && registry().find(sampler) == registry().end()) return Q4_OK;       // off, and never on
-    Dry& r = registry()[sampler];
+    if (!controls && !sides().find(sampler)) return Q4_OK;     // off, and never on
+    Dry& r = sides().of(sampler);
     r.c = controls ? *controls : DRY_DEFAULT;
     r.dirty = true;
     return Q4_OK;
 }
 int q4_sampler_get_dry(const Sampler* sampler, q4_dry_controls* out) {
     if (!sampler || !out) return Q4_ERR_ARG;
-    auto it = registry().find(sampler);
-    *out = it == registry().end() ? DRY_DEFAULT : it->second.c;
+    const Dry* r = sides().find(sampler);
+    *out = r ? r->c : DRY_DEFAULT;
     return Q4_OK;
 }
 int q4_sampler_set_dry_breakers(Sampler* sampler, const int* ids, int n) {
     if (!sampler || !breakers_valid(ids, n, 0)) return Q4_ERR_ARG;
-    if (n == 0 && registry().find(sampler) == registry().end()) return Q4_OK;
-    Dry& r = registry()[sampler];
+    if (n == 0 && !sides().find(sampler)) return Q4_OK;
+    Dry& r = sides().of(sampler);
     r.breakers.assign(ids, ids + n);
     r.dirty = true;
     r.vocab = -1;
@@ -355,14 +300,8 @@ int q4_parse_dry(const char* text, q4_dry_controls* out) {
     q4_dry_controls c = DRY_DEFAULT;
     const char* p = text;
     while (*p) {
-        const char* eq = strchr(p, '=');
-        const char* end = strchr(p, ',');
-        if (!end) end = p + strlen(p);
-        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
-        char key[32], val[64];
-        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
-        memcpy(key, p, eq - p); key[eq - p] = 0;
-        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char key[OPTION_KEY_CAP], val[64];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
         char* rest = nullptr;
         int* iv = !strcmp(key, "allowed") ? &c.allowed_length : !strcmp(key, "last_n") ? &c.last_n : !strcmp(key, "ngram") ? &c.no_repeat_ngram_size : nullptr;
         if (iv) {
@@ -375,8 +314,6 @@ int q4_parse_dry(const char* text, q4_dry_controls* out) {
             *f = strtof(val, &rest);
             if (*rest || rest == val) return Q4_ERR_ARG;
         }
-        p = *end ? end + 1 : end;
-        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
     }
     if (!dry_valid(&c)) return Q4_ERR_ARG;
     *out = c;

@@ -4,7 +4,7 @@
 // V rounded up to 8 entries -- a row is read in 16-byte pieces --: 2 * S * V bytes, 64 KB per state at 32000 tokens, 262 MB at the 4096 states a guide may
 // have. The automaton's state lives on the device by position, in a ring state[seq_len] of int per model (Q4_GUIDE_NONE: no guided step ran here,
 // Q4_GUIDE_OFFTRACK: a token the guide forbids was consumed; sticky).
-// ONE 1024-thread block, the partition of q4_logprobs.hip and q4_logit_process.hip: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last
+// ONE 1024-thread block, the partition of logit_block.h: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last
 // whole chunk, one tail element. With p = *pPos:
 //   1. prev = p > 0 ? state[p - 1] : NONE
 //   2. s = 0 if prev == NONE; OFFTRACK if prev == OFFTRACK or prev is outside [0, S); else with t = tokens[p] (the pinned ring, read by position the way
@@ -24,6 +24,7 @@
 #include <vector>
 #include "q4_device.h"
 #include "q4_model.h"
+#include "logit_block.h"
 using namespace q4;
 
 // the handle of the C ABI: the device table and how many live models hold it
@@ -35,7 +36,7 @@ struct q4_guide {
 
 namespace {
 
-constexpr int GM_T = 1024, GM_Q = 4;                   // threads, register-resident 16-byte chunks per thread
+constexpr int GM_Q = 4;                                // register-resident 16-byte chunks per thread (the block and its partition: logit_block.h)
 
 // what the kernel reads: one small device block per model (or the op-level launcher's), rewritten in stream order when the guide changes, so a captured
 // graph holds the block's address and nothing of the guide
@@ -62,7 +63,7 @@ __device__ __forceinline__ u32x4 mask_chunk(const u32x4& q, const u32x4& r, bool
 // loads on the scalar unit's own counter (the table's entry as the aligned 32-bit word that holds it: the scalar unit has no 16-bit load).
 #define GM_GLOBAL __attribute__((address_space(1)))
 
-__global__ void __launch_bounds__(GM_T) guide_mask_kernel(q4_half* logits, int n, const GuideBlock* __restrict__ blk, const int* tokens, const int* pPos) {
+__global__ void __launch_bounds__(LB_T) guide_mask_kernel(q4_half* logits, int n, const GuideBlock* __restrict__ blk, const int* tokens, const int* pPos) {
     const int tid = threadIdx.x;
     const int n8 = n >> 3, tail = n8 * 8 + tid;
     u32x4* lv = reinterpret_cast<u32x4*>(logits);
@@ -70,7 +71,7 @@ __global__ void __launch_bounds__(GM_T) guide_mask_kernel(q4_half* logits, int n
     u32x4 pq[GM_Q];
 #pragma unroll
     for (int kq = 0; kq < GM_Q; kq++) {
-        const int u = tid + kq * GM_T;
+        const int u = tid + kq * LB_T;
         pq[kq] = u < n8 ? lv[u] : (u32x4){0u, 0u, 0u, 0u};
     }
 
@@ -100,19 +101,19 @@ __global__ void __launch_bounds__(GM_T) guide_mask_kernel(q4_half* logits, int n
     u32x4 rq[GM_Q];                                            // (requested together: one wait for the row, not one per chunk)
 #pragma unroll
     for (int kq = 0; kq < GM_Q; kq++) {
-        const int u = tid + kq * GM_T;
+        const int u = tid + kq * LB_T;
         rq[kq] = u < n8 ? rv[u] : (u32x4){0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int kq = 0; kq < GM_Q; kq++) {
-        const int u = tid + kq * GM_T;
+        const int u = tid + kq * LB_T;
         if (u < n8) {
             bool changed = false;
             const u32x4 o = mask_chunk(pq[kq], rq[kq], changed);
             if (changed) lv[u] = o;
         }
     }
-    for (int u = tid + GM_Q * GM_T; u < n8; u += GM_T) {     // more than 32 x 1024 logits: the rest, chunk by chunk
+    for (int u = tid + GM_Q * LB_T; u < n8; u += LB_T) {     // more than 32 x 1024 logits: the rest, chunk by chunk
         bool changed = false;
         const u32x4 q = lv[u], r = rv[u];
         const u32x4 o = mask_chunk(q, r, changed);
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(GM_T) guide_mask_kernel(q4_half* logits, int n
 GuideBlock* g_op_block = nullptr;      // q4_guide_mask's own block
 
 int launch(q4_half* logits, int n, const GuideBlock* dev, const int* tokens, const int* pPos) {
-    Q4_LAUNCH(guide_mask_kernel, dim3(1), dim3(GM_T), 0, logits, n, dev, tokens, pPos);
+    Q4_LAUNCH(guide_mask_kernel, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -139,9 +140,16 @@ int ring_to_none(const Model* m, int first, int count) {
 
 namespace q4 {
 
-int launch_guide_step(const Model* m, const Config* p, RunState* s) {
-    return launch(s->logits, p->vocab_size, (const GuideBlock*)m->guide_block, &(s->shared_data->tokens[0]), s->pos);
+// the stage lives with the model: q4_set_guide has allocated and written the block, nothing to prepare and nothing a Sampler owns
+static bool stage_on(const Sampler*, const Model* m) { return m && m->guide; }
+static int prepare(const Sampler*, Model* m, const Config*, const void** block) {
+    *block = m->guide_block;
+    return Q4_OK;
 }
+static int launch_step(const void* block, const Model*, const Config* p, RunState* s) {
+    return launch(s->logits, p->vocab_size, (const GuideBlock*)block, &(s->shared_data->tokens[0]), s->pos);
+}
+LogitStage guide_stage = {stage_on, prepare, launch_step, nullptr, nullptr};
 int guide_clear_positions(const Model* m, int pos, int nsteps) { return ring_to_none(m, pos, nsteps); }
 int guide_clear_ring(const Model* m) { return ring_to_none(m, 0, m->guide_len); }
 // q4_free_transformer: the graphs that hold the block are gone and the device has drained

@@ -1,6 +1,6 @@
 // q4_logit_process.hip -- the sampling controls of a completion API beside temperature and top-p: logit bias, repetition / presence / frequency penalties,
 // top-k and min-p, as ONE launch that rewrites the step's fp16 logits in place in front of the argmax or the sampler. Not in the reference.
-// ONE 1024-thread block, the partition of q4_logprobs.hip: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last whole chunk, one tail
+// ONE 1024-thread block, the partition of logit_block.h: thread t owns the 16-byte chunks t, t + 1024, ... and, past the last whole chunk, one tail
 // element; up to 32 x 1024 logits stay in registers, larger vocabularies are read again from L2 in every pass.
 //   1. bias, 2. penalties, 3. clamp and round -- on the TOUCHED entries only (at most 256 bias ids and 1024 window tokens):
 //      v = float(l); v += b_i; with c_i > 0 occurrences of i in the window: v = v > 0 ? v / r : v * r, v -= (float(c_i) * frequency + presence);
@@ -11,7 +11,7 @@
 //      not neutral. The ring is pinned host memory: thread t requests entry t first; the bias list is staged while the request is in flight. The
 //      occurrences are counted in LDS: every thread compares its entry with all the others (last_n / 4 broadcast reads of 16 bytes), the first occurrence
 //      of a token rewrites its logit, a bias id that is also in the window hands its bias to that thread through LDS.
-//   4. top-k on the 16-bit monotone key of q4_logprobs.hip (-0 equals +0, NaN ranks last), order (key descending, index ascending): T, the k-th largest
+//   4. top-k on the 16-bit monotone key of a half (logit_block.h; -0 equals +0, NaN ranks last), order (key descending, index ascending): T, the k-th largest
 //      key, by 16 steps of a binary search whose count is one block-wide sum each; with ties that straddle rank k the entries equal to T keep their place
 //      by index (one block-wide prefix sum per row of 8192 logits, until the k are full). Everything behind rank k becomes -inf.
 //   5. min-p on the PROCESSED logits at temperature 1 (independent of the sampler's temperature): with m the largest of them, entry i stays iff
@@ -25,16 +25,18 @@
 #include <map>
 #include "q4_device.h"
 #include "q4_model.h"
+#include "sampler_side.h"
+#include "logit_block.h"
+#include "option_text.h"
 #pragma clang fp contract(off)
 using namespace q4;
 
 namespace {
 
-constexpr int PL_T = 1024, PL_W = 16, PL_Q = 4;        // threads, waves, register-resident 16-byte chunks per thread
+constexpr int PL_Q = 4;                                // register-resident 16-byte chunks per thread
 constexpr unsigned PL_NO_BIAS = 0xFFFFFFFFu;           // (a NaN pattern: the setters refuse a NaN bias)
 
-// what the kernel reads: one small device block per Sampler (or the op-level launcher's), rewritten in stream order when the host changes the controls,
-// so a captured graph never holds a value of them -- only the block's address
+// what the kernel reads: the stage's device block (sampler_side.h)
 struct LogitParams {
     int top_k;
     int min_p_on;
@@ -46,19 +48,7 @@ struct LogitParams {
     float bias[Q4_MAX_LOGIT_BIAS];
 };
 
-__device__ __forceinline__ unsigned half_key(unsigned h) {      // q4_logprobs.hip: larger value <=> larger key, -0 -> +0, NaN -> 0
-    if (h == 0x8000u) h = 0u;
-    if ((h & 0x7FFFu) > 0x7C00u) return 0u;
-    return (h & 0x8000u) ? (~h & 0xFFFFu) : (h | 0x8000u);
-}
-__device__ __forceinline__ unsigned key_half(unsigned key) { return (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu); }   // (key 0 -> a NaN)
-__device__ __forceinline__ unsigned half_of(const u32x4& q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu; }
-__device__ __forceinline__ u32x4 chunk_keys(const u32x4& q) {
-    u32x4 k;
-#pragma unroll
-    for (int d = 0; d < 4; d++) k[d] = half_key(q[d] & 0xFFFFu) | (half_key(q[d] >> 16) << 16);
-    return k;
-}
+// (the key of a half, a chunk's halves, finish and the block-wide int reductions: logit_block.h)
 __device__ __forceinline__ int count_ge(const u32x4& k, unsigned mid) {
     int c = 0;
 #pragma unroll
@@ -72,66 +62,13 @@ __device__ __forceinline__ int count_eq(const u32x4& k, unsigned T) {
     return c;
 }
 
-// step 3: a finite value clamped to the half range and rounded (RNE); an infinity stays; a NaN is 0x7E00
-__device__ __forceinline__ q4_half finish(float v) {
-    if (v != v) return (q4_half)0x7E00u;
-    if (fabsf(v) != INFINITY) v = fminf(fmaxf(v, -65504.0f), 65504.0f);
-    return (q4_half)f2h(v);
-}
-
-// Block-wide sum / maximum / exclusive prefix sum of one int per thread. `use` counts the calls: two LDS rows take turns, so ONE barrier per call is
-// enough (a row is written again only two calls later, behind the barrier of the call in between, which every thread passes after its reads).
-__device__ __forceinline__ int block_sum(int v, int (*red)[PL_W], int& use) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    int* row = red[use++ & 1];
-    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < PL_W; w++) s += row[w];
-    return s;
-}
-__device__ __forceinline__ int block_max(int v, int (*red)[PL_W], int& use) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
-    int* row = red[use++ & 1];
-    if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = row[0];
-#pragma unroll
-    for (int w = 1; w < PL_W; w++) s = max(s, row[w]);
-    return s;
-}
-__device__ __forceinline__ int block_scan(int v, int (*red)[PL_W], int& use, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(x, off);
-        if (lane >= off) x += o;
-    }
-    int* row = red[use++ & 1];
-    if (lane == 63) row[wave] = x;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < PL_W; w++) {
-        const int r = row[w];
-        tot += r;
-        before += w < wave ? r : 0;
-    }
-    total = tot;
-    return before + x - v;
-}
-
 // REG: n <= 32 x 1024, the thread's chunks and their keys stay in registers. tokens / pPos null: no window.
 template <bool REG>
-__global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, int n, const LogitParams* __restrict__ prm, const int* tokens,
+__global__ void __launch_bounds__(LB_T) logit_process_kernel(q4_half* logits, int n, const LogitParams* __restrict__ prm, const int* tokens,
                                                              const int* pPos) {
-    __shared__ __attribute__((aligned(16))) int s_win[PL_T];
-    __shared__ unsigned s_wbias[PL_T];
-    __shared__ int red[2][PL_W];
+    __shared__ __attribute__((aligned(16))) int s_win[LB_T];
+    __shared__ unsigned s_wbias[LB_T];
+    __shared__ int red[2][LB_W];
     const int tid = threadIdx.x;
     const int top_k = prm->top_k, min_p_on = prm->min_p_on, n_bias = min(max(prm->n_bias, 0), (int)Q4_MAX_LOGIT_BIAS);
     const int last_n = min(max(prm->last_n, 0), (int)Q4_MAX_PENALTY_WINDOW);
@@ -188,14 +125,14 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
     if (top_k <= 0 && !min_p_on) return;                      // (block-uniform)
 
     // ---- steps 4 and 5
-    const int n8 = n >> 3, nq = REG ? PL_Q : (n8 + PL_T - 1) / PL_T;
+    const int n8 = n >> 3, nq = REG ? PL_Q : (n8 + LB_T - 1) / LB_T;
     const int tail = n8 * 8 + tid;
     u32x4* lv = reinterpret_cast<u32x4*>(logits);
     u32x4 pq[PL_Q], kk[PL_Q];
     if (REG) {
 #pragma unroll
         for (int kq = 0; kq < PL_Q; kq++) {
-            const int u = tid + kq * PL_T;
+            const int u = tid + kq * LB_T;
             pq[kq] = u < n8 ? lv[u] : (u32x4){0u, 0u, 0u, 0u};
             kk[kq] = u < n8 ? chunk_keys(pq[kq]) : (u32x4){0u, 0u, 0u, 0u};      // (key 0 is below every threshold the search tries)
         }
@@ -213,7 +150,7 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
             int c = tkey >= mid ? 1 : 0;
 #pragma unroll 4
             for (int kq = 0; kq < (REG ? PL_Q : nq); kq++) {
-                const int u = tid + kq * PL_T;
+                const int u = tid + kq * LB_T;
                 if constexpr (REG) c += count_ge(kk[kq], mid);
                 else if (u < n8) c += count_ge(chunk_keys(lv[u]), mid);
             }
@@ -231,7 +168,7 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
         int mk = (int)tkey;
 #pragma unroll 4
         for (int kq = 0; kq < (REG ? PL_Q : nq); kq++) {
-            const int u = tid + kq * PL_T;
+            const int u = tid + kq * LB_T;
             u32x4 k;
             if constexpr (REG) k = kk[kq]; else k = u < n8 ? chunk_keys(lv[u]) : (u32x4){0u, 0u, 0u, 0u};
 #pragma unroll
@@ -245,7 +182,7 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
     int kept_eq = 0;                                           // entries equal to T in the rows so far (block-uniform; counted only while ties straddle)
     for (int kq = 0; kq <= nq; kq++) {
         const bool is_tail = kq == nq;
-        const int u = tid + kq * PL_T;
+        const int u = tid + kq * LB_T;
         const bool have = is_tail ? tail < n : u < n8;
         u32x4 q = {0u, 0u, 0u, 0u}, k = {0u, 0u, 0u, 0u};
         if (is_tail) { q[0] = th; k[0] = tkey; }
@@ -272,7 +209,7 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
                 bool keep = all || key > T || (key == T && (!straddle || base++ < need));
                 if (keep && min_p_on) keep = h2f((uint16_t)h) - m >= log_min_p;
                 if (!keep && h != 0xFC00u) {
-                    o[e >> 1] = (o[e >> 1] & ~(0xFFFFu << ((e & 1) * 16))) | (0xFC00u << ((e & 1) * 16));
+                    mask_half(o, e);
                     changed = true;
                 }
             }
@@ -284,7 +221,7 @@ __global__ void __launch_bounds__(PL_T) logit_process_kernel(q4_half* logits, in
     }
 }
 
-// ---- host side: validation, the per-Sampler records, the launchers ---------------------------------------------------------------------------------
+// ---- host side: validation, the per-Sampler records, the stage's row ---------------------------------------------------------------------------------
 bool finite_f(float v) { return v == v && fabsf(v) != INFINITY; }
 
 bool controls_valid(const q4_sampling_controls* c) {
@@ -319,47 +256,32 @@ void fill_params(LogitParams* P, const q4_sampling_controls* c, const int* ids, 
 
 const q4_sampling_controls NEUTRAL = {0, 0.f, 1.f, 0.f, 0.f, 0};
 
-// The Sampler struct is the reference's: the controls live beside it, keyed by its address (like the coin rings of q4_step.hip)
-struct Controls {
+// what q4_sampler_set_controls / _set_logit_bias keep beside a Sampler (sampler_side.h)
+struct Controls : DeviceBlock<LogitParams> {
     q4_sampling_controls c = NEUTRAL;
     int n_bias = 0;
     int ids[Q4_MAX_LOGIT_BIAS];
     float bias[Q4_MAX_LOGIT_BIAS];
-    LogitParams host;                  // what the next upload sends (pageable: the copy call returns when it has been staged)
-    LogitParams* dev = nullptr;
-    bool dirty = true;                 // the device block is behind the host's values
     int checked_vocab = -1;            // the vocabulary top_k and the bias ids were last checked against
     bool on() const { return !controls_neutral(&c) || n_bias > 0; }
 };
-std::map<const Sampler*, Controls>& registry() {
-    static std::map<const Sampler*, Controls> r;
+SamplerSides<Controls>& sides() {
+    static SamplerSides<Controls> r;
     return r;
 }
-LogitParams* g_op_block = nullptr;     // q4_process_logits' own block
+DeviceBlock<LogitParams> g_op;         // q4_process_logits' own block
 
 int launch(q4_half* logits, int n, const LogitParams* dev, const int* tokens, const int* pPos) {
-    if (n <= PL_T * PL_Q * 8) Q4_LAUNCH(logit_process_kernel<true>, dim3(1), dim3(PL_T), 0, logits, n, dev, tokens, pPos);
-    else Q4_LAUNCH(logit_process_kernel<false>, dim3(1), dim3(PL_T), 0, logits, n, dev, tokens, pPos);
+    if (n <= LB_T * PL_Q * 8) Q4_LAUNCH(logit_process_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
+    else Q4_LAUNCH(logit_process_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
 
-}  // namespace
-
-namespace q4 {
-
-bool sampling_controls_on(const Sampler* sampler) {
-    if (!sampler || registry().empty()) return false;
-    auto it = registry().find(sampler);
-    return it != registry().end() && it->second.on();
-}
-const void* sampling_controls_block(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    return it == registry().end() ? nullptr : it->second.dev;
-}
-// in front of a step (outside any capture): the values against this model's vocabulary, the device block, the pending upload in stream order
-int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block) {
-    Controls& ctl = registry()[sampler];
+// LogitStage::prepare: top_k and the bias ids against this model's vocabulary, then the block
+int prepare(const Sampler* sampler, Model*, const Config* p, const void** block) {
+    Controls& ctl = sides().of(sampler);
+    const int vocab = p->vocab_size;
     if (ctl.checked_vocab != vocab) {
         if (ctl.c.top_k > vocab || !bias_valid(ctl.ids, ctl.bias, ctl.n_bias, vocab)) {
             snprintf(g_last_error, sizeof(g_last_error), "sampling controls: top_k or a logit bias id exceeds the vocabulary (%d)", vocab);
@@ -367,37 +289,29 @@ int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** bl
         }
         ctl.checked_vocab = vocab;
     }
-    if (!ctl.dev) {
-        Q4_HIP(hipMalloc((void**)&ctl.dev, sizeof(LogitParams)));
-        ctl.dirty = true;
-    }
-    if (ctl.dirty) {
-        fill_params(&ctl.host, &ctl.c, ctl.ids, ctl.bias, ctl.n_bias);
-        Q4_HIP(hipMemcpyAsync(ctl.dev, &ctl.host, sizeof(LogitParams), hipMemcpyHostToDevice, g_stream));
-        ctl.dirty = false;
-    }
+    if (ctl.stale()) fill_params(&ctl.host, &ctl.c, ctl.ids, ctl.bias, ctl.n_bias);
+    Q4_TRY(ctl.upload());
     *block = ctl.dev;
     return Q4_OK;
 }
-int launch_logit_process_step(const void* block, const Config* p, RunState* s) {
+
+bool stage_on(const Sampler* sampler, const Model*) { return sides().on(sampler); }
+int launch_step(const void* block, const Model*, const Config* p, RunState* s) {
     return launch(s->logits, p->vocab_size, (const LogitParams*)block, &(s->shared_data->tokens[0]), s->pos);
 }
-// destroy_sampler: the caller has dropped the graphs that hold the block and drained the stream
-void sampling_controls_forget(const Sampler* sampler) {
-    auto it = registry().find(sampler);
-    if (it == registry().end()) return;
-    if (it->second.dev) (void)hipFree(it->second.dev);
-    registry().erase(it);
-}
+const void* stage_block(const Sampler* sampler) { return sides().block(sampler); }
+void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
 
-}  // namespace q4
+}  // namespace
+
+LogitStage q4::controls_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
 
 extern "C" {
 
 int q4_sampler_set_controls(Sampler* sampler, const q4_sampling_controls* controls) {
     if (!sampler || (controls && !controls_valid(controls))) return Q4_ERR_ARG;
-    if (!controls && registry().find(sampler) == registry().end()) return Q4_OK;       // off, and never on
-    Controls& ctl = registry()[sampler];
+    if (!controls && !sides().find(sampler)) return Q4_OK;     // off, and never on
+    Controls& ctl = sides().of(sampler);
     const int keep_n = ctl.c.penalty_last_n;
     ctl.c = controls ? *controls : NEUTRAL;
     if (!controls) ctl.c.penalty_last_n = keep_n;
@@ -407,14 +321,14 @@ int q4_sampler_set_controls(Sampler* sampler, const q4_sampling_controls* contro
 }
 int q4_sampler_get_controls(const Sampler* sampler, q4_sampling_controls* out) {
     if (!sampler || !out) return Q4_ERR_ARG;
-    auto it = registry().find(sampler);
-    *out = it == registry().end() ? NEUTRAL : it->second.c;
+    const Controls* ctl = sides().find(sampler);
+    *out = ctl ? ctl->c : NEUTRAL;
     return Q4_OK;
 }
 int q4_sampler_set_logit_bias(Sampler* sampler, const int* ids, const float* bias, int n) {
     if (!sampler || !bias_valid(ids, bias, n, 0)) return Q4_ERR_ARG;
-    if (n == 0 && registry().find(sampler) == registry().end()) return Q4_OK;
-    Controls& ctl = registry()[sampler];
+    if (n == 0 && !sides().find(sampler)) return Q4_OK;
+    Controls& ctl = sides().of(sampler);
     ctl.n_bias = n;
     for (int i = 0; i < n; i++) { ctl.ids[i] = ids[i]; ctl.bias[i] = bias[i]; }
     ctl.dirty = true;
@@ -430,14 +344,8 @@ int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out) {
     c.penalty_last_n = 64;
     const char* p = text;
     while (*p) {
-        const char* eq = strchr(p, '=');
-        const char* end = strchr(p, ',');
-        if (!end) end = p + strlen(p);
-        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
-        char key[32], val[64];
-        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
-        memcpy(key, p, eq - p); key[eq - p] = 0;
-        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char key[OPTION_KEY_CAP], val[64];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
         char* rest = nullptr;
         if (!strcmp(key, "top_k") || !strcmp(key, "last_n")) {
             const long v = strtol(val, &rest, 10);
@@ -450,8 +358,6 @@ int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out) {
             *f = strtof(val, &rest);
             if (*rest || rest == val) return Q4_ERR_ARG;
         }
-        p = *end ? end + 1 : end;
-        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
     }
     if (!controls_valid(&c)) return Q4_ERR_ARG;
     *out = c;
@@ -462,11 +368,10 @@ int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* contro
                       const int* pPos) {
     if (!logits || n < 1 || !controls || !controls_valid(controls) || controls->top_k > n || !bias_valid(bias_ids, bias, n_bias, n)) return Q4_ERR_ARG;
     if (controls_neutral(controls) && n_bias == 0) return Q4_OK;
-    if (!g_op_block) Q4_HIP(hipMalloc((void**)&g_op_block, sizeof(LogitParams)));
-    LogitParams P;
-    fill_params(&P, controls, bias_ids, bias, n_bias);
-    Q4_HIP(hipMemcpyAsync(g_op_block, &P, sizeof(P), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
-    return launch(logits, n, g_op_block, tokens, pPos);
+    fill_params(&g_op.host, controls, bias_ids, bias, n_bias);
+    g_op.dirty = true;
+    Q4_TRY(g_op.upload());
+    return launch(logits, n, g_op.dev, tokens, pPos);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 //   lse = m + logf(sum_i expf(l_i - m)), m = max_i l_i, fp32; a log-probability is l - lse (one fp32 subtraction).
 // ONE 1024-thread block (the argmax launch beside it is one block too; the whole vocabulary is 64 KB of L2 hits):
 //   * thread t owns the 16-byte chunks t, t + 1024, ... (8 consecutive logits each) and, past the last whole chunk, one tail element -- argmax_kernel's
-//     partition. Up to 32 x 1024 logits stay in registers between the phases; larger vocabularies re-read them from L2 in every phase.
+//     partition (logit_block.h: the other single-block launches over the logits use it too). Up to 32 x 1024 logits stay in registers between the phases; larger vocabularies re-read them from L2 in every phase.
 //   * the sum has a fixed order: a thread adds runs of 32 exponentials (four chunks) in ascending index, adds the runs' totals in ascending order
 //     (one run up to 32 x 1024 logits, four at 128256), then the tail element; a 64-lane tree (wave_sum), a 16-lane tree over the wave totals.
 //     No atomics, no arrival order, never more than 32 + runs + 1 sequential adds: bit-stable from launch to launch.
@@ -17,11 +17,12 @@
 #include <math.h>
 #include "q4_device.h"
 #include "q4_model.h"
+#include "logit_block.h"
 using namespace q4;
 
 namespace {
 
-constexpr int LP_T = 1024, LP_W = 16, LP_Q = 4;        // threads, waves, register-resident 16-byte chunks per thread
+constexpr int LP_Q = 4;                                // register-resident 16-byte chunks per thread
 constexpr int LP_K = Q4_MAX_TOP_LOGPROBS;
 // LDS candidate list: k x (elements per thread) entries always fit. In registers a thread has 32 + 1 elements: 20 x 33 = 660; the looping path's list
 // fills what is left of 64 KB of static LDS (k x (8 x chunks per thread + 1) <= 6144: 311,000 logits at k = 20; the launcher refuses more)
@@ -30,12 +31,7 @@ enum { LP_TARGET = 0, LP_GREEDY = 1, LP_SAMPLED = 2 };
 
 typedef unsigned long long u64;
 
-// monotone key of a half: larger value <=> larger key. -0 -> +0 (equal under argmax_kernel's float compare), NaN -> 0 (below -inf: never wins, like there)
-__device__ __forceinline__ unsigned half_key(unsigned h) {
-    if (h == 0x8000u) h = 0u;
-    if ((h & 0x7FFFu) > 0x7C00u) return 0u;
-    return (h & 0x8000u) ? (~h & 0xFFFFu) : (h | 0x8000u);
-}
+// (half_key, the monotone key of a half, and half_of: logit_block.h)
 __device__ __forceinline__ u64 pack_p(unsigned key, unsigned idx) { return ((u64)(key + 1u) << 32) | (u64)(0xFFFFFFFFu - idx); }
 __device__ __forceinline__ unsigned p_index(u64 p) { return 0xFFFFFFFFu - (unsigned)p; }
 
@@ -49,19 +45,16 @@ __device__ __forceinline__ u64 wave_max_u64(u64 v) {
     return v;
 }
 
-// the 8 halves of a chunk, in index order
-__device__ __forceinline__ unsigned half_of(const u32x4& q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu; }
-
 // REG: n <= 32 x 1024, the thread's chunks stay in registers. mode: LP_TARGET the target token is tokens[tok_off + position] (tokens null: none),
 // LP_GREEDY token_logprob = entry 0, LP_SAMPLED the raw logits go to `side` and logprob_pick_kernel fills token_logprob behind the sampler.
 // pPos null: the stand-alone launcher (record 0); else record *pPos of rings with `cap` records -- a position outside them writes nothing.
 template <bool REG>
-__global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __restrict__ logits, int n, int top_k, int mode, const int* tokens, int tok_off,
+__global__ void __launch_bounds__(LB_T) logprob_topk_kernel(const q4_half* __restrict__ logits, int n, int top_k, int mode, const int* tokens, int tok_off,
                                                             const int* pPos, int cap, float* lse_out, float* tlp_out, int* top_ids, float* top_lps,
                                                             q4_half* __restrict__ side) {
     constexpr int LP_CAND = REG ? LP_CAND_REG : LP_CAND_LOOP;
     __shared__ u64 cand[LP_CAND];
-    __shared__ u64 wtop[LP_W * LP_K];
+    __shared__ u64 wtop[LB_W * LP_K];
     __shared__ float red[16];
     __shared__ u64 s_T;
     __shared__ unsigned s_count;
@@ -73,14 +66,14 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
     int target = -1;
     if (mode == LP_TARGET && tokens != nullptr && tid == 0 && tok_off + pos < Q4_MAX_SEQ_LEN) target = tokens[tok_off + pos];
     const int keff = top_k > 0 ? top_k : 1;                    // entry 0 is always found: the greedy token
-    const int n8 = n >> 3, nq = REG ? LP_Q : (n8 + LP_T - 1) / LP_T;
+    const int n8 = n >> 3, nq = REG ? LP_Q : (n8 + LB_T - 1) / LB_T;
     const int tail = n8 * 8 + tid;                             // this thread's tail element, if < n
     const u32x4* lv = reinterpret_cast<const u32x4*>(logits);
     u32x4 pq[LP_Q];
     if (REG) {
 #pragma unroll
         for (int kq = 0; kq < LP_Q; kq++) {
-            const int u = tid + kq * LP_T;
+            const int u = tid + kq * LB_T;
             pq[kq] = u < n8 ? lv[u] : (u32x4){0u, 0u, 0u, 0u};
         }
     }
@@ -93,7 +86,7 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
     unsigned best_idx = 0;
 #pragma unroll 4
     for (int kq = 0; kq < (REG ? LP_Q : nq); kq++) {
-        const int u = tid + kq * LP_T;
+        const int u = tid + kq * LB_T;
         if (u < n8) {
             u32x4 q;
             if constexpr (REG) q = pq[kq]; else q = lv[u];
@@ -128,20 +121,20 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
     m = row16_max(red[lane & 15]);
     // wave 0: T = the keff-th largest of the 16 x keff (0 when fewer than keff threads hold elements: every element is a candidate then)
     if (wave == 0) {
-        u64 v[(LP_W * LP_K + 63) / 64];
+        u64 v[(LB_W * LP_K + 63) / 64];
 #pragma unroll
-        for (int j = 0; j < (LP_W * LP_K + 63) / 64; j++) {
+        for (int j = 0; j < (LB_W * LP_K + 63) / 64; j++) {
             const int i = lane + 64 * j, w = i / LP_K, r = i - w * LP_K;
-            v[j] = (i < LP_W * LP_K && r < keff) ? wtop[i] : 0ull;
+            v[j] = (i < LB_W * LP_K && r < keff) ? wtop[i] : 0ull;
         }
         u64 T = 0ull;
         for (int i = 0; i < keff; i++) {
             u64 l = v[0];
 #pragma unroll
-            for (int j = 1; j < (LP_W * LP_K + 63) / 64; j++) l = v[j] > l ? v[j] : l;
+            for (int j = 1; j < (LB_W * LP_K + 63) / 64; j++) l = v[j] > l ? v[j] : l;
             T = wave_max_u64(l);
 #pragma unroll
-            for (int j = 0; j < (LP_W * LP_K + 63) / 64; j++) if (v[j] == T) v[j] = 0ull;
+            for (int j = 0; j < (LB_W * LP_K + 63) / 64; j++) if (v[j] == T) v[j] = 0ull;
         }
         if (lane == 0) s_T = T;
     }
@@ -152,7 +145,7 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
         float run = 0.f;
 #pragma unroll 4
         for (int kq = 0; kq < (REG ? LP_Q : nq); kq++) {
-            const int u = tid + kq * LP_T;
+            const int u = tid + kq * LB_T;
             if (u < n8) {
                 u32x4 q;
                 if constexpr (REG) q = pq[kq]; else q = lv[u];
@@ -176,7 +169,7 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
     if (mineP >= T) {
 #pragma unroll 4
         for (int kq = 0; kq < (REG ? LP_Q : nq); kq++) {
-            const int u = tid + kq * LP_T;
+            const int u = tid + kq * LB_T;
             if (u < n8) {
                 u32x4 q;
                 if constexpr (REG) q = pq[kq]; else q = lv[u];
@@ -199,13 +192,13 @@ __global__ void __launch_bounds__(LP_T) logprob_topk_kernel(const q4_half* __res
         }
     }
     if (mode == LP_SAMPLED && side != nullptr) {               // the sampler overwrites `logits`: keep the raw values for logprob_pick_kernel
-        for (int u = tid; u < n8; u += LP_T) reinterpret_cast<u32x4*>(side)[u] = lv[u];
+        for (int u = tid; u < n8; u += LB_T) reinterpret_cast<u32x4*>(side)[u] = lv[u];
         if (tail < n) side[tail] = (q4_half)th;
     }
     __syncthreads();
     const int count = (int)min(s_count, (unsigned)LP_CAND);
     const size_t rec = (size_t)pos;
-    for (int i = tid; i < count; i += LP_T) {
+    for (int i = tid; i < count; i += LB_T) {
         const u64 mine = cand[i];
         int r = 0;
         for (int j = 0; j < count; j++) r += cand[j] > mine ? 1 : 0;             // (every lane reads one word: an LDS broadcast)
@@ -244,10 +237,10 @@ int launch_topk(const q4_half* logits, int n, int top_k, int mode, const int* to
                 int* top_ids, float* top_lps, q4_half* side) {
     if (n < 1 || top_k < 0 || top_k > LP_K || top_k > n) return Q4_ERR_ARG;
     if (!logprobs_size_ok(n, top_k)) return Q4_ERR_UNSUPPORTED_SIZE;
-    if (n <= LP_T * LP_Q * 8)
-        Q4_LAUNCH(logprob_topk_kernel<true>, dim3(1), dim3(LP_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
+    if (n <= LB_T * LP_Q * 8)
+        Q4_LAUNCH(logprob_topk_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
     else
-        Q4_LAUNCH(logprob_topk_kernel<false>, dim3(1), dim3(LP_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
+        Q4_LAUNCH(logprob_topk_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -258,8 +251,8 @@ namespace q4 {
 
 // the candidate list holds the elements of k threads: k x (8 per chunk + the tail element)
 bool logprobs_size_ok(int n, int top_k) {
-    const long long per_thread = 8ll * (((n >> 3) + LP_T - 1) / LP_T) + 1;
-    return n <= LP_T * LP_Q * 8 || (long long)(top_k > 0 ? top_k : 1) * per_thread <= LP_CAND_LOOP;
+    const long long per_thread = 8ll * (((n >> 3) + LB_T - 1) / LB_T) + 1;
+    return n <= LB_T * LP_Q * 8 || (long long)(top_k > 0 ? top_k : 1) * per_thread <= LP_CAND_LOOP;
 }
 
 int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_token, bool greedy) {

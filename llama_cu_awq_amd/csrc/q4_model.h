@@ -1,4 +1,5 @@
-// q4_model.h -- what the library keeps beside a Transformer, and what q4_model.hip, q4_network.hip and q4_step.hip share (not part of the C ABI).
+// q4_model.h -- what the library keeps beside a Transformer, what q4_model.hip, q4_network.hip and q4_step.hip share, and the row a logit stage gives
+// the step (not part of the C ABI).
 #pragma once
 #include <map>
 #include <vector>
@@ -75,37 +76,33 @@ void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the 
 bool logprobs_size_ok(int n, int top_k);
 int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_token, bool greedy);
 int launch_logprobs_pick(const Model* m, const Config* p, RunState* s);
-// q4_logit_process.hip. The sampling controls kept beside a Sampler (q4_sampler_set_controls / _set_logit_bias): whether any is on; before a step and
-// outside any capture, the check against the vocabulary and the device block the launch reads (allocated once, rewritten in stream order when the host
-// changed a value); the launch itself, between the record launch and the argmax / sampler of a generating step
-bool sampling_controls_on(const Sampler* sampler);
-const void* sampling_controls_block(const Sampler* sampler);
-int sampling_controls_prepare(const Sampler* sampler, int vocab, const void** block);
-int launch_logit_process_step(const void* block, const Config* p, RunState* s);
-void sampling_controls_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
-// q4_dry.hip. The DRY / no-repeat-n-gram settings kept beside a Sampler (q4_sampler_set_dry / _set_dry_breakers), the same five entry points as the
-// sampling controls'; the launch sits behind the guide's and in front of the sampling controls'
-bool dry_on(const Sampler* sampler);
-const void* dry_block(const Sampler* sampler);
-int dry_prepare(const Sampler* sampler, int vocab, const void** block);   // Q4_ERR_ARG: a breaker id at or above the vocabulary
-int launch_dry_step(const void* block, const Config* p, RunState* s);
-void dry_forget(const Sampler* sampler);   // frees the block and the bitmap: the graphs that hold the block are gone and the stream has drained
-// q4_adaptive.hip. The typical-p / top-n-sigma / Mirostat settings kept beside a Sampler (q4_sampler_set_adaptive), the same five entry points; the
-// launch sits behind the sampling controls' and in front of the argmax / sampler. _prepare also allocates the model's rings on first use (m null: a
-// RunState the library did not build -- no rings, no records, Mirostat is Q4_ERR_ARG) and refuses Mirostat at temperature 0. NONE over the ring
-// positions of a prompt group or over the whole ring (in stream order, outside any capture; nothing without rings); the move of q4_shift_context
-bool adaptive_on(const Sampler* sampler);
-const void* adaptive_block(const Sampler* sampler);
-int adaptive_prepare(const Sampler* sampler, Model* m, const Config* p, const void** block);
-int launch_adaptive_step(const void* block, const Model* m, const Config* p, RunState* s);
-void adaptive_forget(const Sampler* sampler);   // frees the block: the graphs that hold it are gone and the stream has drained
+// A logit stage: ONE launch that rewrites a generating step's fp16 logits in place, between the record launch and the argmax / sampler. What it reads
+// sits in a small device block whose address -- and nothing else of the stage -- a captured graph holds. m is null for a RunState the
+// library did not build.
+struct LogitStage {
+    bool (*on)(const Sampler* sampler, const Model* m);
+    // in front of a step, outside any capture: the settings against this model, the block (allocated once, rewritten in stream order when the host
+    // changed a value), and whatever else the launch needs allocated. An error refuses the step
+    int (*prepare)(const Sampler* sampler, Model* m, const Config* p, const void** block);
+    int (*launch)(const void* block, const Model* m, const Config* p, RunState* s);
+    // per-Sampler stages: the block a Sampler owns (null: none yet; never creates one), and what destroy_sampler calls once the graphs that hold
+    // that block are gone and the stream has drained. Both null for a stage that lives with the model
+    const void* (*block)(const Sampler* sampler);
+    void (*forget)(const Sampler* sampler);
+};
+// q4_step.hip's table, in launch order: the guide's mask (q4_guide.hip; per model), DRY (q4_dry.hip), the sampling controls (q4_logit_process.hip:
+// top-k counts what both left), the adaptive truncation (q4_adaptive.hip: typical-p and Mirostat see what top-k and min-p left)
+// (Written once, where they are defined. Not const: a const object with a constant initializer is emitted for the device as well, where these host
+// functions do not exist.)
+extern LogitStage guide_stage, dry_stage, controls_stage, adaptive_stage;
+// q4_adaptive.hip. NONE over the ring positions of a prompt group or over the whole ring (in stream order, outside any capture; nothing without
+// rings); the move of q4_shift_context; what q4_free_transformer releases
 int adaptive_clear_positions(const Model* m, int pos, int nsteps);
 int adaptive_clear_ring(const Model* m);
 int adaptive_shift(const Model* m, int vocab, int n_pos, int first, int M, int D);
 void adaptive_release(Model* m);
-// q4_guide.hip. The guide launch of a generating step, between the record launch and the sampling controls' launch; NONE over the ring positions of a
-// prompt group, or over the whole ring (both in stream order, outside any capture); what q4_free_transformer releases
-int launch_guide_step(const Model* m, const Config* p, RunState* s);
+// q4_guide.hip. NONE over the ring positions of a prompt group, or over the whole ring (both in stream order, outside any capture); what
+// q4_free_transformer releases
 int guide_clear_positions(const Model* m, int pos, int nsteps);
 int guide_clear_ring(const Model* m);
 void guide_release(Model* m);

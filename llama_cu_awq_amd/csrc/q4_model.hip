@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 #include "q4_model.h"
+#include "option_text.h"
 
 namespace q4 {
 
@@ -598,14 +599,8 @@ int q4_parse_rope_scaling(const char* text, q4_rope_scaling* out) {
     const char* p = *end ? end + 1 : end;
     if (*end && !*p) return Q4_ERR_ARG;                        // a trailing comma
     while (*p) {
-        const char* eq = strchr(p, '=');
-        end = strchr(p, ',');
-        if (!end) end = p + strlen(p);
-        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
-        char key[32], val[48];
-        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
-        memcpy(key, p, eq - p); key[eq - p] = 0;
-        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char key[OPTION_KEY_CAP], val[48];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
         int k = 0;
         while (k < n_keys && strcmp(key, keys[k])) k++;
         if (k == n_keys || (seen & (1 << k))) return Q4_ERR_ARG;
@@ -621,8 +616,6 @@ int q4_parse_rope_scaling(const char* text, q4_rope_scaling* out) {
             if (*rest || !isfinite(v)) return Q4_ERR_ARG;
             (k == 0 ? r.factor : k == 1 ? r.low_freq_factor : r.high_freq_factor) = v;
         }
-        p = *end ? end + 1 : end;
-        if (*end && !*p) return Q4_ERR_ARG;
     }
     if (seen != (1 << n_keys) - 1 || !rope_scaling_ok(&r)) return Q4_ERR_ARG;
     *out = r;

@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include <vector>
 #include "q4_model.h"
+#include "option_text.h"
 
 namespace q4 {
 
@@ -40,12 +41,15 @@ static int clear_handoff_state(const RunState* s, const Model* m, bool error_too
     return Q4_OK;
 }
 
+// The logit stages of a generating step, in launch order (q4_model.h LogitStage). Stage i is variant bit STAGE_BIT0 + i.
+static const LogitStage* const STAGES[] = {&guide_stage, &dry_stage, &controls_stage, &adaptive_stage};
+enum { N_STAGES = sizeof(STAGES) / sizeof(STAGES[0]), STAGE_BIT0 = 6, N_VARIANTS = 1 << (STAGE_BIT0 + N_STAGES) };
+static inline int stage_bit(int i) { return 1 << (STAGE_BIT0 + i); }
+
 // graphs: [bin][variant]; variant bit0 = gen_token, bit1 = copyLogits, bit2 = sampled (the sampler launch, its temperature / top-p / coin ring baked in),
 // bit3 = Q4_MULTI_STEPS steps per graph, bit4 = the log-probability record launch of q4_set_logprobs (its K and ring baked in), bit5 = the classifier as screen + refine (cls_screen.h),
-// bit6 = the sampling controls' launch (q4_logit_process.hip; the address of the Sampler's parameter block baked in, none of its values),
-// bit7 = the guide launch (q4_guide.hip; the address of the model's guide block baked in, nothing of the guide),
-// bit8 = the DRY launch (q4_dry.hip; the address of the Sampler's parameter block baked in, none of its values),
-// bit9 = the adaptive truncation launch (q4_adaptive.hip; the addresses of the Sampler's parameter block and of the model's rings baked in). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
+// from bit6 on one bit per logit stage: its launch, with the address of its parameter block baked in and none of the block's values (the adaptive
+// truncation's also holds the addresses of the model's rings). A captured graph holds one model's pointers, so the sets are kept PER MODEL (its RunState): a host that alternates
 // a few models on one GPU replays each one's graphs (llama2_q4.cu:342-344 keeps one set for its one model); beyond GRAPH_OWNERS live models the least
 // recently used set is dropped and captured again on its next turn (q4_graph_captures counts: a host can see it happen). A set remembers the Config and the
 // weights it was captured with: a caller who reuses a RunState with others gets new captures, not a replay of stale pointers.
@@ -55,26 +59,23 @@ struct GraphSet {
     const Config* config;
     const TransformerWeights* weights;
     unsigned long long used;
-    hipGraphExec_t exec[Q4_MAX_GRAPHS][1024];
-    bool captured[Q4_MAX_GRAPHS][1024];
+    hipGraphExec_t exec[Q4_MAX_GRAPHS][N_VARIANTS];
+    bool captured[Q4_MAX_GRAPHS][N_VARIANTS];
     const Sampler* sampler;            // what the set's sampled graphs have baked in
     float temperature, topp;
     const float* coins;
-    const void* controls;              // the parameter block the set's graphs with the sampling controls' launch read
-    const void* guide;                 // the guide block the set's graphs with the guide launch read
-    const void* dry;                   // the parameter block the set's graphs with the DRY launch read
-    const void* adaptive;              // the parameter block the set's graphs with the adaptive truncation launch read
+    const void* block[N_STAGES];       // the parameter block the set's graphs with stage i's launch read
 };
 static GraphSet g_sets[GRAPH_OWNERS];
 static unsigned long long g_set_clock = 0;
 static int g_graph_captures = 0;
 // a graph is destroyed only after the launch stream has drained -- a replay may still be in flight (eviction and free are rare: the token loop never waits here)
-// mask: 0 drops every variant and gives the set up; 4 the sampled variants (what they have baked in is forgotten); 16 those with the record launch;
-// 64 those with the sampling controls' launch; 128 those with the guide launch; 256 those with the DRY launch; 512 those with the adaptive truncation launch
+// mask: 0 drops every variant and gives the set up; else the variants with any of the mask's bits -- 4 the sampled ones (what they have baked in is
+// forgotten), 16 those with the record launch, stage_bit(i) those with stage i's launch (its block is forgotten)
 static void drop_graphs(GraphSet& gs, int mask) {
     bool drained = false;
     for (int i = 0; i < Q4_MAX_GRAPHS; i++)
-        for (int v = 0; v < 1024; v++)
+        for (int v = 0; v < N_VARIANTS; v++)
             if (gs.captured[i][v] && (!mask || (v & mask))) {
                 if (!drained) { (void)hipStreamSynchronize(g_stream); drained = true; }
                 hipGraphExecDestroy(gs.exec[i][v]);
@@ -82,10 +83,8 @@ static void drop_graphs(GraphSet& gs, int mask) {
             }
     if (!mask) gs.owner = nullptr;
     if (!mask || (mask & 4)) { gs.sampler = nullptr; gs.coins = nullptr; }
-    if (!mask || (mask & 64)) gs.controls = nullptr;
-    if (!mask || (mask & 128)) gs.guide = nullptr;
-    if (!mask || (mask & 256)) gs.dry = nullptr;
-    if (!mask || (mask & 512)) gs.adaptive = nullptr;
+    for (int i = 0; i < N_STAGES; i++)
+        if (!mask || (mask & stage_bit(i))) gs.block[i] = nullptr;
 }
 void drop_graphs_of(const RunState* s) {
     for (GraphSet& gs : g_sets)
@@ -112,12 +111,16 @@ static GraphSet& graph_set_of(const RunState* owner, const Config* p, const Tran
 
 // A step runs its classifier as screen + refine only when nothing but the greedy token is taken from its logits: a greedy generating step of a token
 // loop (may_screen: the public per-step entry points never pass it -- their callers read RunState::logits), no fp32 copy, no log-probability records, a
-// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on, no sampling controls, no DRY, no adaptive
-// truncation and no guide (their launches rewrite whole logits).
+// model with a screening copy whose shape the launch stream still admits, the fused sequence, the switch on and no logit stage (their launches rewrite
+// whole logits).
+static bool any_stage_on(const Sampler* sampler, const Model* m) {
+    for (const LogitStage* st : STAGES)
+        if (st->on(sampler, m)) return true;
+    return false;
+}
 static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits, const Sampler* sampler) {
     return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
-           !sampling_controls_on(sampler) && !dry_on(sampler) && !adaptive_on(sampler) && !m->guide &&
-           cls_screen_shape(m->screen.n, m->screen.d);
+           !any_stage_on(sampler, m) && cls_screen_shape(m->screen.n, m->screen.d);
 }
 
 }  // namespace q4
@@ -209,24 +212,15 @@ static int coin_ring_for(const Sampler* sampler, int positions, CoinRing** out) 
     return Q4_OK;
 }
 void destroy_sampler(Sampler* sampler) {
-    if (const void* block = sampling_controls_block(sampler)) {     // graphs with the sampling controls' launch hold the block's address
-        for (GraphSet& gs : g_sets)
-            if (gs.controls == block) drop_graphs(gs, 64);
-        if (g_stream) hipStreamSynchronize(g_stream);
+    for (int i = 0; i < N_STAGES; i++) {
+        if (!STAGES[i]->forget) continue;
+        if (const void* block = STAGES[i]->block(sampler)) {        // graphs with the stage's launch hold the block's address
+            for (GraphSet& gs : g_sets)
+                if (gs.block[i] == block) drop_graphs(gs, stage_bit(i));
+            if (g_stream) hipStreamSynchronize(g_stream);
+        }
+        STAGES[i]->forget(sampler);
     }
-    sampling_controls_forget(sampler);
-    if (const void* block = dry_block(sampler)) {                   // ... and so do graphs with the DRY launch
-        for (GraphSet& gs : g_sets)
-            if (gs.dry == block) drop_graphs(gs, 256);
-        if (g_stream) hipStreamSynchronize(g_stream);
-    }
-    dry_forget(sampler);
-    if (const void* block = adaptive_block(sampler)) {              // ... and with the adaptive truncation launch
-        for (GraphSet& gs : g_sets)
-            if (gs.adaptive == block) drop_graphs(gs, 512);
-        if (g_stream) hipStreamSynchronize(g_stream);
-    }
-    adaptive_forget(sampler);
     auto cr = g_coin_rings.find(sampler);
     if (cr != g_coin_rings.end()) {
         for (GraphSet& gs : g_sets)
@@ -280,6 +274,33 @@ static int sample_impl(Sampler* sampler, RunState* s, int gen_token, bool launch
 }
 int q4_sample(Sampler* sampler, RunState* s, int gen_token) { return sample_impl(sampler, s, gen_token, true); }
 
+// What a step runs behind its network: the fp32 copy of the logits, the record launch, the logit stages that are on (block[i] non-null), the argmax or
+// the sampler, the record's look-up of the chosen token. ONE list for both paths. captured: inside a capture -- a sampled step's coin comes from
+// the ring `coins` by position (the caller draws it), and a step that feeds the next (feed_next) leaves the token's embedding row in s->x. Eager:
+// sample_impl draws the step's coin itself.
+struct StepTail {
+    int gen_token, copyLogits;
+    bool greedy, lp_greedy, lp_pick;
+    const Model* lpm;                  // null: no record launch
+    const Model* model;
+    Sampler* sampler;
+    const void* block[N_STAGES];
+};
+static int step_tail(const StepTail& t, const Config* p, RunState* s, const TransformerWeights* w, bool captured, const float* coins, bool feed_next) {
+    if (t.copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
+    if (t.lpm) Q4_TRY(launch_logprobs_step(t.lpm, p, s, t.gen_token, t.lp_greedy));   // (before the sampler: it advances the position and overwrites the logits;
+    for (int i = 0; i < N_STAGES; i++)                                                //  in front of the stages: the records describe the model's raw logits)
+        if (t.block[i]) Q4_TRY(STAGES[i]->launch(t.block[i], t.model, p, s));
+    if (!captured) Q4_TRY(sample_impl(t.sampler, s, t.gen_token, true));
+    else if (!t.greedy)                // sampler.h:51-81 inside the graph
+        Q4_TRY(q4_sample_topp_device(t.sampler, s, 0.f, coins, feed_next ? s->x : nullptr, w->token_embedding_table, p->dim));
+    else if (feed_next)
+        Q4_TRY(launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, s->x, w->token_embedding_table, p->dim));
+    else
+        Q4_TRY(q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, t.gen_token));
+    return t.lp_pick ? launch_logprobs_pick(t.lpm, p, s) : Q4_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // run_transformer, llama2_q4.cu:346-395
 __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
@@ -324,51 +345,34 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
     const int graphIndex = graph_bin(seq_len, p, &seq_len_bin);
     if (nsteps != 1 && (nsteps != g_multi_steps || g_use_graphs != 1)) return Q4_ERR_ARG;
     if (pos < 0 || pos + nsteps > p->seq_len) return Q4_ERR_ARG;
-    const Model* lpm = model_of(s);                                                // q4_set_logprobs: a record launch between the classifier and the sampler
-    const bool screened = step_screens(lpm, may_screen != 0, gen_token, greedy, copyLogits, pSampler);
-    // q4_set_guide: a prompt group puts NONE at its positions (in stream order, outside the graph, where the coin ring's copy sits); a generating step
-    // carries the guide launch between the record launch and the controls' launch
-    const Model* guided = lpm && lpm->guide ? lpm : nullptr;
-    if (guided && !gen_token) { Q4_TRY(guide_clear_positions(guided, pos, nsteps)); guided = nullptr; }
-    // q4_sampler_set_adaptive: Mirostat's mu is state by position like the guide's -- a prompt group puts NONE at its positions (only while the sampler has the launch on, as the guide's clearing needs a guide); a generating step
-    // carries the launch behind the controls' launch
     Model* const mdl = model_of(s);
-    if (mdl && mdl->adaptive_mu && !gen_token && adaptive_on(pSampler)) Q4_TRY(adaptive_clear_positions(mdl, pos, nsteps));
-    const void* adaptive = nullptr;
-    if (gen_token && adaptive_on(pSampler)) Q4_TRY(adaptive_prepare(pSampler, mdl, p, &adaptive));
-    if (lpm && lpm->logprobs_k < 0) lpm = nullptr;
-    // q4_sampler_set_controls / _set_logit_bias: a launch that rewrites the logits between the record launch and the argmax / sampler of a generating step
-    const void* controls = nullptr;
-    if (gen_token && sampling_controls_on(pSampler)) Q4_TRY(sampling_controls_prepare(pSampler, p->vocab_size, &controls));
-    // q4_sampler_set_dry: its launch sits behind the guide's and in front of the controls'
-    const void* dry = nullptr;
-    if (gen_token && dry_on(pSampler)) Q4_TRY(dry_prepare(pSampler, p->vocab_size, &dry));
-    // the record of a generating step whose logits the controls, DRY, the adaptive truncation or the guide rewrite: the chosen token need not be the raw logits' largest, so a greedy
-    // step keeps the raw logits aside and looks its token up behind the argmax, the way a sampled step does
-    const bool lp_greedy = greedy && !controls && !guided && !dry && !adaptive, lp_pick = lpm && gen_token && (!greedy || controls || guided || dry || adaptive);
+    const bool screened = step_screens(mdl, may_screen != 0, gen_token, greedy, copyLogits, pSampler);
+    // State by position -- the guide's automaton, Mirostat's mu -- is put to NONE at a prompt group's positions (in stream order, outside the graph, where
+    // the coin ring's copy sits): the guide's while the model has a guide, the adaptive truncation's while the sampler has the launch on
+    if (!gen_token && guide_stage.on(pSampler, mdl)) Q4_TRY(guide_clear_positions(mdl, pos, nsteps));
+    if (!gen_token && mdl && mdl->adaptive_mu && adaptive_stage.on(pSampler, mdl)) Q4_TRY(adaptive_clear_positions(mdl, pos, nsteps));
+    // q4_set_logprobs: a record launch between the classifier and the sampler. Of a generating step whose logits a stage rewrites the chosen token need
+    // not be the raw logits' largest, so a greedy step keeps the raw logits aside and looks its token up behind the argmax, the way a sampled step does
+    StepTail tail = {gen_token, copyLogits, greedy, greedy, false, mdl && mdl->logprobs_k >= 0 ? mdl : nullptr, mdl, pSampler, {}};
+    int stage_bits = 0;
+    for (int i = 0; i < N_STAGES && gen_token; i++)
+        if (STAGES[i]->on(pSampler, mdl)) {
+            Q4_TRY(STAGES[i]->prepare(pSampler, mdl, p, &tail.block[i]));
+            stage_bits |= stage_bit(i);
+            tail.lp_greedy = false;
+        }
+    tail.lp_pick = tail.lpm && gen_token && !tail.lp_greedy;
 
     if (g_use_graphs == 1) {
         GraphSet& gs = graph_set_of(s, p, w);
         // Unlike the reference, the greedy sampler kernel and the fp32 logits copy are part of the captured
         // graph (one launch per token instead of up to three); the variant index keeps them apart.
-        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (lpm ? 16 : 0) | (screened ? 32 : 0) |
-                            (controls ? 64 : 0) | (guided ? 128 : 0) | (dry ? 256 : 0) | (adaptive ? 512 : 0);
-        if (guided && gs.guide != guided->guide_block) {
-            drop_graphs(gs, 128);
-            gs.guide = guided->guide_block;
-        }
-        if (dry && gs.dry != dry) {
-            drop_graphs(gs, 256);
-            gs.dry = dry;
-        }
-        if (controls && gs.controls != controls) {
-            drop_graphs(gs, 64);
-            gs.controls = controls;
-        }
-        if (adaptive && gs.adaptive != adaptive) {
-            drop_graphs(gs, 512);
-            gs.adaptive = adaptive;
-        }
+        const int variant = (gen_token ? 1 : 0) | (copyLogits ? 2 : 0) | (greedy ? 0 : 4) | (nsteps > 1 ? 8 : 0) | (tail.lpm ? 16 : 0) | (screened ? 32 : 0) | stage_bits;
+        for (int i = 0; i < N_STAGES; i++)
+            if (tail.block[i] && gs.block[i] != tail.block[i]) {     // another block: the graphs with this stage's launch hold a stale address
+                drop_graphs(gs, stage_bit(i));
+                gs.block[i] = tail.block[i];
+            }
         CoinRing* ring = nullptr;
         if (!greedy) {     // the sampling kernel is part of the graph: its temperature, top-p, scratch and coin ring are baked in
             Q4_TRY(coin_ring_for(pSampler, p->seq_len, &ring));
@@ -388,23 +392,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
             const bool feed = gen_token && nsteps > 1 && g_fusion >= 1;
             for (int i = 0; i < nsteps && !rc; i++) {
                 rc = run_network(s->pos, p, s, w, seq_len_bin, feed && i > 0, screened);
-                if (!rc && copyLogits) rc = q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos);
-                if (!rc && lpm) rc = launch_logprobs_step(lpm, p, s, gen_token, lp_greedy);   // (before the sampler: it advances the position and overwrites the logits)
-                if (!rc && guided) rc = launch_guide_step(guided, p, s);                   // (behind the records: they describe the model's raw logits;
-                if (!rc && dry) rc = launch_dry_step(dry, p, s);                           //  the mask first, then DRY: top-k counts what both left)
-                if (!rc && controls) rc = launch_logit_process_step(controls, p, s);
-                if (!rc && adaptive) rc = launch_adaptive_step(adaptive, mdl, p, s);        // (typical-p and Mirostat see what top-k and min-p left)
-                if (!rc && greedy) {
-                    if (feed && i + 1 < nsteps)
-                        rc = launch_argmax_feed(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos,
-                                                s->x, w->token_embedding_table, p->dim);
-                    else
-                        rc = q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, gen_token);
-                    if (!rc && lp_pick) rc = launch_logprobs_pick(lpm, p, s);
-                } else if (!rc) {   // sampler.h:51-81 inside the graph: the coin comes from the ring, by position
-                    rc = q4_sample_topp_device(pSampler, s, 0.f, ring->dev, feed && i + 1 < nsteps ? s->x : nullptr, w->token_embedding_table, p->dim);
-                    if (!rc && lpm) rc = launch_logprobs_pick(lpm, p, s);
-                }
+                if (!rc) rc = step_tail(tail, p, s, w, true, ring ? ring->dev : nullptr, feed && i + 1 < nsteps);
             }
             hipError_t e = hipStreamEndCapture(g_stream, &graph);
             if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
@@ -424,14 +412,7 @@ __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int p
         return Q4_OK;
     }
     Q4_TRY(run_network(s->pos, p, s, w, g_use_graphs == 2 ? seq_len_bin : seq_len, false, screened));   // :374
-    if (copyLogits) Q4_TRY(q4_copy_logits_at_pos(s->logits_array, s->logits, p->vocab_size, s->pos));   // :377-382
-    if (lpm) Q4_TRY(launch_logprobs_step(lpm, p, s, gen_token, lp_greedy));
-    if (guided) Q4_TRY(launch_guide_step(guided, p, s));
-    if (dry) Q4_TRY(launch_dry_step(dry, p, s));
-    if (controls) Q4_TRY(launch_logit_process_step(controls, p, s));
-    if (adaptive) Q4_TRY(launch_adaptive_step(adaptive, mdl, p, s));
-    Q4_TRY(sample_impl(pSampler, s, gen_token, true));
-    return lp_pick ? launch_logprobs_pick(lpm, p, s) : Q4_OK;
+    return step_tail(tail, p, s, w, false, nullptr, false);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -555,21 +536,13 @@ int q4_parse_context_shift(const char* text, int* n_keep, int* n_discard) {
     long keep = 0, discard = 0;
     const char* p = text;
     while (*p) {
-        const char* eq = strchr(p, '=');
-        const char* end = strchr(p, ',');
-        if (!end) end = p + strlen(p);
-        if (!eq || eq > end || eq == p || eq + 1 == end) return Q4_ERR_ARG;
-        char key[32], val[32];
-        if ((size_t)(eq - p) >= sizeof(key) || (size_t)(end - eq - 1) >= sizeof(val)) return Q4_ERR_ARG;
-        memcpy(key, p, eq - p); key[eq - p] = 0;
-        memcpy(val, eq + 1, end - eq - 1); val[end - eq - 1] = 0;
+        char key[OPTION_KEY_CAP], val[32];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
         long* dst = !strcmp(key, "keep") ? &keep : !strcmp(key, "discard") ? &discard : nullptr;
         if (!dst || val[0] < '0' || val[0] > '9') return Q4_ERR_ARG;          // (no sign, no leading blank)
         char* rest = nullptr;
         *dst = strtol(val, &rest, 10);
         if (*rest || *dst > Q4_MAX_SEQ_LEN) return Q4_ERR_ARG;
-        p = *end ? end + 1 : end;
-        if (*end && !*p) return Q4_ERR_ARG;                    // a trailing comma
     }
     if (discard < 1) return Q4_ERR_ARG;                        // off is the absence of a setting, not a text
     *n_keep = (int)keep;

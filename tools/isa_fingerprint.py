@@ -53,6 +53,7 @@ for m in re.finditer(r"\.amdhsa_kernel (_Z\w+)(.*?)\.end_amdhsa_kernel", asm, re
 dem = subprocess.run(["c++filt"], input="\n".join(out.keys()), capture_output=True, text=True).stdout.splitlines()
 res = {}
 for k, d in zip(out.keys(), dem):
+    d = d.replace("(anonymous namespace)::", "")     # (its parenthesis is no argument list: without this every such kernel of a file got one name)
     d = re.sub(r"\(.*$", "", d)          # the template name without the argument list
     res[d] = out[k]
 json.dump(res, sys.stdout, indent=1, sort_keys=True)
