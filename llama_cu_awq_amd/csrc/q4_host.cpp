@@ -1,6 +1,6 @@
 // q4_host.cpp -- host-only side of llama2_q4: the llama2.c BPE tokenizer (tokenizer.h), the generate / chat /
 // perplexity drivers (llama2_q4.cu:436-601, perplexity.h:57-139) and the CLI (llama2_q4.cu:604-720).
-// No device code here; everything reaches the GPU through the C ABI in llama2_q4.h.
+// No device code here; everything reaches the GPU through the C ABI in llama2_q4.h, but for q4_step.hip's token loop and the step it queues (q4_loop.h).
 #include <ctype.h>
 #include <math.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "llama2_q4.h"
+#include "q4_loop.h"
 
 static const int bos_token = 1;   // tokenizer.h:8
 static const int eos_token = 2;   // tokenizer.h:9
@@ -149,19 +150,9 @@ int q4_tokenizer_encode(struct Tokenizer* t, const char* text, int bos, int eos,
 }
 
 // ---------------------------------------------------------------------------------------------------
-static long time_in_ms() {                                                         // llama2_q4.cu:400-405
-    struct timespec time;
-    timespec_get(&time, TIME_UTC);
-    return time.tv_sec * 1000 + time.tv_nsec / 1000000;
-}
-
 static void die_on(int rc) {
     if (rc) { printf("\n%s\n", q4_status_string(rc)); exit(EXIT_FAILURE); }        // the reference's printf + exit
 }
-
-// q4_step.hip, not exported: q4_run_transformer_steps for a token loop that does not read the group's logits (the greedy screen, cls_screen.h)
-extern "C" __attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
-                                                                                    int copyLogits, Sampler* pSampler, int may_screen);
 
 // Q4_PROMPT_CACHE=FILE (generate mode): a serialised snapshot of an earlier run's prompt positions. Everything about it goes to stderr; a file that is
 // missing, fails q4_snapshot_check or belongs to another model is reported and ignored.
@@ -205,6 +196,21 @@ static void prompt_cache_save(const char* path, const Transformer* t, int n_pos)
     if (!ok) { fprintf(stderr, "Q4_PROMPT_CACHE: cannot write %s\n", path); remove(tmp.c_str()); }
 }
 
+// What generate() does with the tokens of the loop: every one is decoded behind its predecessor and printed (llama2_q4.cu:473-476)
+struct Printer { struct Tokenizer* tokenizer; const int* prompt_tokens; int vocab_size; };
+static void print_token(void* ctx, int, int prev, int next) {
+    const Printer* p = (const Printer*)ctx;
+    if (next >= p->vocab_size) next = 0;                                               // :474
+    safe_printf(q4_tokenizer_decode(p->tokenizer, prev, next));
+}
+// ... and with an attempt: the second follows a bounded in-launch wait that ran out, the text above is invalid and the library has dropped to fusion
+// level 1 (no in-launch waits) -- say so. Each prints what the skipped steps' iterations would, from the prompt's tokens.
+static void print_attempt(void* ctx, int attempt, int start) {
+    const Printer* p = (const Printer*)ctx;
+    if (attempt > 0) printf("\n\n[%s -- generating again]\n", q4_last_error());
+    for (int i = 1; i < start; i++) safe_printf(q4_tokenizer_decode(p->tokenizer, p->prompt_tokens[i - 1], p->prompt_tokens[i]));
+}
+
 static double generate_cached(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sampler, const char* prompt, int steps,
                               int* timed_tokens_out, double* seconds_out, const char* cache_path);
 // generate(), llama2_q4.cu:436-492
@@ -226,7 +232,6 @@ static double generate_cached(Transformer* transformer, struct Tokenizer* tokeni
         fprintf(stderr, "something is wrong, expected at least 1 prompt token\n");
         exit(EXIT_FAILURE);
     }
-    RunState* state = &transformer->state;
     // the prompt cache: restore, then skip the positions the snapshot's tokens share with the prompt -- none of them past an EOS, where the loop stops
     int start_pos = 0, covered = 0;
     if (cache_path) {
@@ -238,83 +243,23 @@ static double generate_cached(Transformer* transformer, struct Tokenizer* tokeni
             while (covered < info.n_pos && covered < num_prompt_tokens && had[covered] == prompt_tokens[covered]) covered++;
             start_pos = covered < num_prompt_tokens - 1 ? covered : num_prompt_tokens - 1;
             if (start_pos > steps) start_pos = 0;
-            for (int i = 1; i < start_pos; i++)
-                if (prompt_tokens[i] == eos_token || prompt_tokens[i] >= transformer->config.vocab_size) start_pos = 0;
+            for (int i = 1; i < start_pos; i++)                                        // (their pieces are printed: no token the loop would clamp)
+                if (prompt_tokens[i] >= transformer->config.vocab_size) start_pos = 0;
             die_on(q4_snapshot_delete(snap));                                          // (synchronises: the rows are in place)
         }
     }
-    const unsigned long long rng0 = sampler->rng_state;
-    int timed_tokens = 0;
-    double time = 0.0;
-    int ran_from = 0;
-    // q4_set_context_shift: at seq_len the rows slide instead of the loop ending; `pos` counts steps, the device runs step pos at position pos - off
-    int shift_keep = 0, shift_discard = 0, off = 0;
-    (void)q4_get_context_shift(transformer, &shift_keep, &shift_discard);
-    const int seq_len = transformer->config.seq_len;
-    for (int attempt = 0;; attempt++) {
-        long start = time_in_ms();
-        int next;
-        int token = prompt_tokens[0];
-        int pos = attempt == 0 ? start_pos : 0;                                        // the retry after a time-out trusts no row
-        ran_from = pos;
-        off = 0;
-        if (pos == 0) die_on(q4_reset_sequence(state, prompt_tokens, num_prompt_tokens));   // :461-463
-        else die_on(q4_resume_sequence(state, prompt_tokens, num_prompt_tokens, pos));
-        for (int i = 1; i < pos; i++) {                                                // what the skipped steps' iterations print
-            safe_printf(q4_tokenizer_decode(tokenizer, token, prompt_tokens[i]));
-            token = prompt_tokens[i];
-        }
-        for (int i = 0; i < pos; i++) (void)random_f32(&sampler->rng_state);           // ... and their coins (one per step, sampler.h:45)
-        int queued = pos, group_start = pos;
-        unsigned long long group_rng = sampler->rng_state;
-        bool stopped = false;
-        while (pos < steps) {
-            // step `pos` is queued behind step pos-1 before the host waits for step pos-1's token (reference: sync, then
-            // launch, :468-470) -- same device order, the GPU never idles between tokens; greedy steps inside one bin go out
-            // Q4_MULTI_STEPS at a time
-            if (pos >= queued) {
-                if (shift_discard > 0 && pos - off == seq_len) {                       // (synchronises: everything queued has finished)
-                    die_on(q4_shift_context(transformer, seq_len, shift_keep, shift_discard, seq_len + 1));
-                    off += shift_discard;
-                }
-                const int k = q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &transformer->config, sampler);
-                group_start = pos;
-                group_rng = sampler->rng_state;
-                // (every group but the one with the generation's last step may screen its classifier: nobody reads those logits)
-                die_on(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + k < steps));
-                queued = pos + k;
-            }
-            die_on(q4_wait_pos(state, pos - off));                                     // :468
-            if (pos > 0) {
-                next = q4_shared_token(state, pos - off);                              // output token of the previous iteration
-                if (next >= transformer->config.vocab_size) next = 0;                  // :474
-                const char* piece = q4_tokenizer_decode(tokenizer, token, next);
-                safe_printf(piece);
-                if (next == eos_token) { stopped = true; break; }
-                token = next;
-            }
-            pos++;
-        }
-        printf("\n");
-        long end = time_in_ms();
-        if (stopped) {   // one coin per executed step as in the reference (sampler.h:45): undo the draws of the group's surplus steps
-            sampler->rng_state = group_rng;
-            for (int i = group_start; i <= pos; i++) (void)random_f32(&sampler->rng_state);
-        }
-        time = (end - start) / 1000.0;
-        timed_tokens = pos - 1 - ran_from;                                             // (the steps this run executed)
-        if (q4_handoff_status(state) == Q4_OK) break;
-        // a bounded in-launch wait ran out: the text above is invalid. The library has cleared its hand-off state and dropped
-        // to fusion level 1 (no in-launch waits): say so and generate again, once
-        if (attempt > 0) die_on(Q4_ERR_HIP);
-        if (off > 0) die_on(Q4_ERR_HIP);                                               // (a shifted sequence is not generated again)
-        printf("\n[%s -- generating again]\n", q4_last_error());
-        sampler->rng_state = rng0;
-    }
+    // the token loop (q4_loop.h) over the printer above; q4_set_context_shift: at seq_len the rows slide instead of the loop ending
+    Printer printer = {tokenizer, prompt_tokens, transformer->config.vocab_size};
+    TokenLoop loop = {print_token, print_attempt, &printer};
+    const int rc = q4_token_loop(transformer, sampler, prompt_tokens, num_prompt_tokens, steps, start_pos, &loop);
+    printf("\n");
+    die_on(rc);
+    const int timed_tokens = loop.pos - 1 - loop.start, off = loop.off;                // (the steps this run executed)
+    const double time = loop.seconds;
     printf("\nachieved tok/s: %f. Tokens: %d, seconds: %g\n", timed_tokens / time, timed_tokens, time);   // :489
     if (cache_path && off == 0) {      // keep the prompt's positions for the next run, unless the file already covers them
         die_on(q4_stream_synchronize());
-        const int done = q4_shared_pos(state), n_save = done < num_prompt_tokens ? done : num_prompt_tokens;
+        const int done = q4_shared_pos(&transformer->state), n_save = done < num_prompt_tokens ? done : num_prompt_tokens;
         if (n_save >= 1 && covered < n_save) prompt_cache_save(cache_path, transformer, n_save);
     }
     free(prompt_tokens);
@@ -383,7 +328,7 @@ void q4_chat(Transformer* transformer, struct Tokenizer* tokenizer, Sampler* sam
         }
         const int at = q4_shared_pos(state);
         // (q4_run_transformer's step; a greedy generating step may screen its classifier: only its token is read. Not the last one.)
-        die_on(run_transformer_steps_screenable(at, 1, user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, pos + 1 < steps));
+        die_on(run_transformer_steps_screenable(at, 1, user_idx >= num_prompt_tokens - 1, &transformer->config, state, &transformer->weights, 0, sampler, group_may_screen(pos, 1, steps)));
         user_idx++;
         if (user_idx > 0) {
             next = q4_shared_token(state, at);                                     // :584

@@ -1,5 +1,5 @@
 // q4_step.hip -- one decode step and the loops over it: per-model graph sets and q4_run_transformer*, the sampler's host side, the hand-off
-// state between sequences, generate and perplexity on token ids.
+// state between sequences, the one generate loop (q4_token_loop, q4_loop.h: q4_generate_ids and q4_host.cpp's q4_generate), perplexity and scoring on token ids.
 // Mirrors llama2_q4.cu:342-395 (run_transformer), :436-492 (generate), sampler.h, perplexity.h:57-97.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include <vector>
 #include "q4_model.h"
+#include "q4_loop.h"
 #include "option_text.h"
 
 namespace q4 {
@@ -303,8 +304,6 @@ static int step_tail(const StepTail& t, const Config* p, RunState* s, const Tran
 
 // ---------------------------------------------------------------------------------------------------
 // run_transformer, llama2_q4.cu:346-395
-__attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
-                                                                         int copyLogits, Sampler* pSampler, int may_screen);
 int q4_run_transformer(int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
                        Sampler* pSampler) {
     return q4_run_transformer_at(s->shared_data->pos, gen_token, p, s, w, copyLogits, pSampler);   // :354
@@ -336,9 +335,9 @@ int q4_run_transformer_steps(int pos, int nsteps, int gen_token, const Config* p
                              int copyLogits, Sampler* pSampler) {
     return run_transformer_steps_screenable(pos, nsteps, gen_token, p, s, w, copyLogits, pSampler, 0);
 }
-// ... for the token loops of this library (here and in q4_host.cpp; not exported): may_screen says that nobody reads the group's logits
-__attribute__((visibility("hidden"))) int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w,
-                                                                         int copyLogits, Sampler* pSampler, int may_screen) {
+// ... for the token loops of this library (q4_token_loop below, q4_chat; q4_loop.h): may_screen says that nobody reads the group's logits
+int run_transformer_steps_screenable(int pos, int nsteps, int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
+                                     Sampler* pSampler, int may_screen) {
     const int seq_len = pos + nsteps;                                              // :354 (of the group's last step)
     const bool greedy = sampler_is_greedy(pSampler, gen_token);
     int seq_len_bin;
@@ -570,15 +569,13 @@ int q4_steps_that_fit(int pos, int num_prompt_tokens, int steps, const Config* p
     int b0, b1;
     if (graph_bin(pos + 1, p, &b0) != graph_bin(pos + k, p, &b1)) return 1;
     // A model that screens its greedy steps: the last step a generation queues goes out alone, so that it can run the full classifier and leave
-    // RunState::logits whole (group_may_screen below). The Config of a Transformer leads to its record; any other Config finds none and changes nothing.
+    // RunState::logits whole (group_may_screen, q4_loop.h). The Config of a Transformer leads to its record; any other Config finds none and changes nothing.
     if (pos + k == steps && gen0 && sampler && sampler->temperature == 0.0f) {
         const RunState* rs = reinterpret_cast<const RunState*>(reinterpret_cast<const char*>(p) - offsetof(Transformer, config) + offsetof(Transformer, state));
         if (step_screens(model_of(rs), true, 1, true, 0, sampler)) return 1;
     }
     return k;
 }
-// what a token loop passes as may_screen for the group of k steps it queues at pos: every step but the generation's last
-static int group_may_screen(int pos, int k, int steps) { return pos + k < steps ? 1 : 0; }
 // The in-launch hand-offs of fusion levels 3 and 4 (attention -> o-proj, layer_attn.h; the FFN pair launch, gemv_ffn_pair.h) spin for a bounded time; a spin that ran out
 // sets the model's error word: everything computed since is invalid. Synchronises the stream and reports it ONCE: the word,
 // the counters and the granules are cleared (the epoch keeps counting: tags never repeat), and the library drops to fusion
@@ -626,67 +623,63 @@ int q4_wait_pos(const RunState* s, int pos) {
 }
 int q4_shared_token(const RunState* s, int index) { return s->shared_data->tokens[index]; }
 
-
-// generate() llama2_q4.cu:436-492 on token ids (no tokenizer, no printing): same loop order -- synchronise,
-// launch step `pos`, then look at the token produced by the PREVIOUS step; same throughput rule (pos-1)/elapsed.
-double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps,
-                       int* out_tokens, int* timed_tokens_out, double* seconds_out) {
-    return q4_generate_ids_from(t, sampler, prompt_tokens, num_prompt_tokens, steps, 0, out_tokens, timed_tokens_out, seconds_out);
+// After a pass over a sequence: q4_handoff_status into *rc, and what every loop of this file does with a timed-out in-launch wait. The library has
+// dropped to fusion level 1 and cleared its state, so the first time-out of a pass that can be repeated (redoable) puts the sampler back to rng0 and
+// asks for the pass once more; any other is the error.
+static bool redo_after_timeout(const RunState* s, Sampler* sampler, unsigned long long rng0, bool redoable, int* rc) {
+    *rc = q4_handoff_status(s);
+    if (!*rc || !redoable) return false;
+    sampler->rng_state = rng0;
+    return true;
 }
-// ... starting at start_pos, over K / V rows [0, start_pos) that are already in place (q4_resume_sequence's contract). The loop draws one coin per step
-// whether or not the step samples, so the skipped steps' coins are drawn and discarded first: with the same seed a resumed sampled generation produces
-// the full one's tokens, and a reused Sampler stands where the full run leaves it.
-double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos,
-                            int* out_tokens, int* timed_tokens_out, double* seconds_out) {
-    if (!t || !sampler || !prompt_tokens || num_prompt_tokens < 1) return -1.0;
-    // q4_set_context_shift: the loop shifts at seq_len instead of stopping there, so steps may pass it. `pos` below counts steps (it indexes the history);
-    // the device runs step `pos` at position pos - off, off being the positions discarded so far
+
+// generate() llama2_q4.cu:436-492, the one token loop behind q4_generate and q4_generate_ids_from (q4_loop.h): same loop order -- synchronise, launch
+// step `pos`, then look at the token produced by the PREVIOUS step; same throughput rule (pos-1)/elapsed. It starts at start_pos over K / V rows
+// [0, start_pos) that are already in place (q4_resume_sequence's contract) and draws one coin per step whether or not the step samples, so the skipped
+// steps' coins are drawn and discarded first: with the same seed a resumed sampled generation produces the full one's tokens, and a reused Sampler
+// stands where the full run leaves it. q4_set_context_shift: the loop shifts at seq_len instead of stopping there, so steps may pass it; `pos` counts
+// steps, and the device runs step `pos` at position pos - off, off being the positions discarded so far.
+int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos, TokenLoop* loop) {
     const Model* sm = model_of(&t->state);
     const int seq_len = t->config.seq_len, shift_keep = sm ? sm->shift_keep : 0, shift_discard = sm ? sm->shift_discard : 0;
-    if (steps <= 0) steps = seq_len;
-    else if (steps > (shift_discard > 0 ? Q4_MAX_SEQ_LEN - 1 : seq_len)) steps = shift_discard > 0 ? Q4_MAX_SEQ_LEN - 1 : seq_len;   // :690
-    if (start_pos < 0 || start_pos > num_prompt_tokens - 1 || start_pos > t->config.seq_len) {
-        snprintf(g_last_error, sizeof(g_last_error), "q4_generate_ids_from: start_pos %d outside [0, %d] (%s)", start_pos, num_prompt_tokens - 1, q4_status_string(Q4_ERR_ARG));
-        return -1.0;
-    }
     // the full loop stops at the first EOS it meets in the ring behind index 0, a prompt's included: a prefix that holds one is not skipped
     for (int i = 1; i < start_pos; i++)
         if (prompt_tokens[i] == 2) start_pos = 0;
     const unsigned long long rng0 = sampler->rng_state;
-    std::vector<int> history;                                // of a run that shifts: every token by step, the evicted ones too
     for (int attempt = 0;; attempt++) {
         struct timespec t0, t1;
         clock_gettime(CLOCK_MONOTONIC, &t0);
         const int start = attempt == 0 ? start_pos : 0;      // the retry after a time-out trusts no row
         int pos = start, queued = start, group_start = start, off = 0;
-        if (start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start)) return -1.0;
+        Q4_TRY(start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start));
+        if (loop->on_attempt) loop->on_attempt(loop->ctx, attempt, start);
         for (int i = 0; i < start; i++) (void)random_f32(&sampler->rng_state);
         unsigned long long group_rng = sampler->rng_state;   // sampler state in front of the group of steps queued last
+        int prev = prompt_tokens[start > 0 ? start - 1 : 0];
         bool stopped = false;
         while (pos < steps) {
             // the reference synchronises and then launches step `pos` (:468-470); here the launch goes out first, queued
             // behind step pos-1, and the host then waits for step pos-1's token -- same device order, no idle gap per token.
-            // Greedy steps inside one bin go out Q4_MULTI_STEPS at a time (one graph replay); a stop at EOS leaves at most
+            // Steps inside one bin go out Q4_MULTI_STEPS at a time (one graph replay); a stop at EOS leaves at most
             // Q4_MULTI_STEPS - 1 surplus steps behind, which the next q4_reset_sequence discards.
             if (pos >= queued) {
-                if (shift_discard > 0 && pos - off == seq_len) {     // the wall: everything queued has to finish (q4_shift_context synchronises), then the rows slide
-                    if (hipStreamSynchronize(g_stream) != hipSuccess) { (void)hipGetLastError(); return -1.0; }
-                    if (history.empty()) history.resize((size_t)steps + 1);
-                    for (int i = off ? shift_keep : 0; i <= seq_len && off + i <= steps; i++) history[off + i] = t->state.shared_data->tokens[i];
-                    if (q4_shift_context(t, seq_len, shift_keep, shift_discard, seq_len + 1)) return -1.0;
+                if (shift_discard > 0 && pos - off == seq_len) {     // the wall: q4_shift_context synchronises (everything queued has finished), then the rows slide
+                    Q4_TRY(q4_shift_context(t, seq_len, shift_keep, shift_discard, seq_len + 1));
                     off += shift_discard;
                 }
                 const int k = q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                if (run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off))) return -1.0;
+                Q4_TRY(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off)));
                 queued = pos + k;
             }
-            if (q4_wait_pos(&t->state, pos - off)) return -1.0;                        // :468
+            Q4_TRY(q4_wait_pos(&t->state, pos - off));                                 // :468
             if (pos > 0) {
-                int next = t->state.shared_data->tokens[pos - off];                    // :473
+                int next = t->state.shared_data->tokens[pos - off];                    // :473, output token of the previous iteration
+                if (loop->on_token) loop->on_token(loop->ctx, pos, prev, next);
                 if (next >= t->config.vocab_size) next = 0;                            // :474
                 if (next == 2) { stopped = true; break; }                              // eos_token, :477
+                prev = next;
             }
             pos++;
         }
@@ -697,25 +690,42 @@ double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_
             sampler->rng_state = group_rng;
             for (int i = group_start; i <= pos; i++) (void)random_f32(&sampler->rng_state);
         }
-        const double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
-        const int timed_tokens = pos - 1 - start;                                      // :488, over the steps this call ran
-        if (q4_handoff_status(&t->state)) {     // a timed-out in-launch wait: the library is at fusion level 1 now, state cleared
-            if (attempt == 0 && off == 0) { sampler->rng_state = rng0; continue; }     // redo the whole sequence once (shifted rows cannot be redone)
-            return -1.0;
-        }
-        if (out_tokens) {
-            const int n = (pos < steps ? pos : steps) + 1;
-            if (off) {
-                for (int i = shift_keep; i <= seq_len && off + i < n; i++) history[off + i] = t->state.shared_data->tokens[i];
-                for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = history[i];
-            } else {
-                for (int i = 0; i < n && i < Q4_MAX_SEQ_LEN; i++) out_tokens[i] = t->state.shared_data->tokens[i];
-            }
-        }
-        if (timed_tokens_out) *timed_tokens_out = timed_tokens;
-        if (seconds_out) *seconds_out = secs;
-        return secs > 0 ? timed_tokens / secs : 0.0;
+        loop->pos = pos;
+        loop->start = start;
+        loop->off = off;
+        loop->seconds = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
+        int rc;
+        if (!redo_after_timeout(&t->state, sampler, rng0, attempt == 0 && off == 0, &rc)) return rc;   // (shifted rows cannot be redone)
     }
+}
+
+// ... on token ids (no tokenizer, no printing): out_tokens receives the ring by step, the evicted tokens of a run that shifts too
+static void record_token(void* out_tokens, int step, int, int token) { ((int*)out_tokens)[step] = token; }
+double q4_generate_ids(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps,
+                       int* out_tokens, int* timed_tokens_out, double* seconds_out) {
+    return q4_generate_ids_from(t, sampler, prompt_tokens, num_prompt_tokens, steps, 0, out_tokens, timed_tokens_out, seconds_out);
+}
+double q4_generate_ids_from(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos,
+                            int* out_tokens, int* timed_tokens_out, double* seconds_out) {
+    if (!t || !sampler || !prompt_tokens || num_prompt_tokens < 1) return -1.0;
+    const Model* sm = model_of(&t->state);
+    const int limit = sm && sm->shift_discard > 0 ? Q4_MAX_SEQ_LEN - 1 : t->config.seq_len;   // (a model that shifts generates past seq_len)
+    if (steps <= 0) steps = t->config.seq_len;
+    else if (steps > limit) steps = limit;                                             // :690
+    if (start_pos < 0 || start_pos > num_prompt_tokens - 1 || start_pos > t->config.seq_len) {
+        snprintf(g_last_error, sizeof(g_last_error), "q4_generate_ids_from: start_pos %d outside [0, %d] (%s)", start_pos, num_prompt_tokens - 1, q4_status_string(Q4_ERR_ARG));
+        return -1.0;
+    }
+    TokenLoop loop = {out_tokens ? record_token : nullptr, nullptr, out_tokens};
+    if (q4_token_loop(t, sampler, prompt_tokens, num_prompt_tokens, steps, start_pos, &loop)) return -1.0;
+    if (out_tokens) {      // up to the step it started from the ring is the prompt; a run that ends at `steps` has not looked at its last token
+        for (int i = 0; i <= loop.start && i <= steps; i++) out_tokens[i] = prompt_tokens[i];
+        if (loop.pos == steps) out_tokens[steps] = t->state.shared_data->tokens[steps - loop.off];
+    }
+    const int timed_tokens = loop.pos - 1 - loop.start;                                // :488, over the steps this call ran
+    if (timed_tokens_out) *timed_tokens_out = timed_tokens;
+    if (seconds_out) *seconds_out = loop.seconds;
+    return loop.seconds > 0 ? timed_tokens / loop.seconds : 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -750,6 +760,7 @@ float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with
     if (!state->logits_array || num_tokens < 1) return -1.0f;
     if (num_tokens >= config->seq_len) num_tokens = config->seq_len - 1;           // :68-72
     const unsigned long long rng0 = sampler->rng_state;
+    int rc;
     for (int attempt = 0;; attempt++) {
         if (q4_reset_sequence(state, tokens_with_bos, num_tokens + 1)) return -1.0f;   // :76-78
         // the input tokens are all known: the steps are queued back to back (the device advances its own position) and the
@@ -757,11 +768,9 @@ float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with
         for (int pos = 0; pos < num_tokens; pos++)
             if (q4_run_transformer_at(pos, 0, config, state, &t->weights, 1, sampler)) return -1.0f;   // :80
         if (hipDeviceSynchronize() != hipSuccess) return -1.0f;                        // :81
-        if (!q4_handoff_status(state)) break;
-        // a timed-out in-launch wait: the library has dropped to fusion level 1 and cleared its state; redo the pass once
-        if (attempt > 0) return -1.0f;
-        sampler->rng_state = rng0;
+        if (!redo_after_timeout(state, sampler, rng0, attempt == 0, &rc)) break;
     }
+    if (rc) return -1.0f;
     float* logits_arr = (float*)malloc((size_t)num_tokens * config->vocab_size * sizeof(float));
     if (q4_get_logits_array(t, num_tokens, logits_arr)) { free(logits_arr); return -1.0f; }   // :88-89
     float pplx = compute_perplexity(tokens_with_bos + 1, logits_arr, num_tokens, config->vocab_size);   // :91
@@ -824,8 +833,8 @@ int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, i
     const int before = m->logprobs_k;
     if (before < 0) Q4_TRY(q4_set_logprobs(t, 0));
     const unsigned long long rng0 = sampler->rng_state;
-    int rc = Q4_OK;
-    for (int attempt = 0; !rc; attempt++) {
+    int rc;
+    for (int attempt = 0;; attempt++) {
         rc = q4_reset_sequence(state, tokens_with_bos, num_tokens + 1);
         // every input token is known: the steps go out like generate()'s prompt steps (a target is the NEXT ring entry), up to Q4_MULTI_STEPS per replay
         for (int pos = 0; pos < num_tokens && !rc;) {
@@ -834,10 +843,7 @@ int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, i
             pos += k;
         }
         if (!rc && hipStreamSynchronize(g_stream) != hipSuccess) rc = Q4_ERR_HIP;
-        if (rc || !q4_handoff_status(state)) break;
-        // a timed-out in-launch wait: the library has dropped to fusion level 1 and cleared its state; redo the pass once
-        if (attempt > 0) rc = Q4_ERR_HIP;
-        sampler->rng_state = rng0;
+        if (rc || !redo_after_timeout(state, sampler, rng0, attempt == 0, &rc)) break;
     }
     if (!rc) rc = q4_get_logprobs(t, 0, num_tokens, logprobs_out, nullptr, nullptr);
     if (before < 0) { const int rc2 = q4_set_logprobs(t, -1); if (!rc) rc = rc2; }
