@@ -11,7 +11,7 @@
 //   * inclusive prefix sum IN FP16 (sampler.h:72-78) in a fixed cub-shaped order -- thread-sequential over 1/1024th of
 //     the vocabulary, Hillis-Steele across the 64 lanes, sequential across the 16 waves, every add rounded to fp16 --
 //     and the first index whose prefix reaches the threshold (:566-577). cub's order is unspecified; the oracle
-//     restates this one.
+//     restates this one. An entry of probability 0 is never that index (scan_search_phase has the reason).
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "q4_device.h"
@@ -269,7 +269,10 @@ __device__ void radix_pass_lds(const unsigned (&kv)[SMP_E], int n, int S, int E,
 // `limit` on are not searched, and no hit means "not among the candidates".
 // INREG: the thread's E <= 32 entries arrive in registers (pk; the caller fetched them with all loads in flight at once), key is not called
 // (the two walks are chains of dependent fp16 additions: with a load in every link thread 0 alone spent 2.7 us of LDS latency on its 2 x 32 entries).
-// Returns the first index whose prefix reaches the threshold (the minimum over the block: a wave minimum, then sixteen words in LDS -- `wmin` --; an LDS
+// An entry of probability 0 -- a -inf logit: a banned or masked token; a logit that underflows -- is never the sample: the fp16 scan is not monotone across its partition
+// (a thread's exclusive prefix comes from the lane scan, its predecessor's last inclusive prefix from that thread's own running sum, and the two may round apart),
+// so the first prefix >= threshold can belong to an entry that added nothing; a monotone scan never stops there, and neither does this search (the oracle restates it).
+// Returns the first index of a probability above 0 whose prefix reaches the threshold (the minimum over the block: a wave minimum, then sixteen words in LDS -- `wmin` --; an LDS
 // atomicMin on a generic pointer inside this shape sent hipcc / ROCm 7.2 into "Illegal instruction detected: V_CMP_NE_U32 0, $src_shared_base"), or INT_MAX.
 template <bool INREG, typename KeyAt>
 __device__ __forceinline__ int scan_search_phase(KeyAt key, const float (&pk)[SMP_E], int n, float threshold, float* wtot, int* wmin, int limit = 0x7fffffff) {
@@ -302,12 +305,13 @@ __device__ __forceinline__ int scan_search_phase(KeyAt key, const float (&pk)[SM
         for (int j = 0; j < SMP_E; j++)
             if (lo + j < hi) {
                 r = round_h(r + pk[j]);
-                if (found == 0x7fffffff && round_h(excl + r) >= threshold) found = lo + j;
+                if (found == 0x7fffffff && pk[j] != 0.f && round_h(excl + r) >= threshold) found = lo + j;
             }
     } else {
         for (int i = lo; i < hi; i++) {
-            r = round_h(r + h2f(key(i, i - lo)));
-            if (round_h(excl + r) >= threshold) { found = i; break; }
+            const float p = h2f(key(i, i - lo));
+            r = round_h(r + p);
+            if (p != 0.f && round_h(excl + r) >= threshold) { found = i; break; }
         }
     }
 #pragma unroll
@@ -319,6 +323,23 @@ __device__ __forceinline__ int scan_search_phase(KeyAt key, const float (&pk)[SM
     for (int w = 1; w < SMP_W; w++) h = wmin[w] < h ? wmin[w] : h;
     __syncthreads();                                          // (wtot / wmin may be written again by the caller's next phase)
     return h;
+}
+
+// No prefix reached the threshold (the fp16 total stays below it): the search falls back to the order's last entry with a probability above 0 -- n - 1
+// (gpu_kernels.h:560) unless that entry is a masked one. `last`: the largest such index among the entries this thread looked at (i = tid, tid + 1024, ..), -1: none.
+// Block-uniform call and result. (The callers walk their keys themselves: a key functor over the LDS sort buffer sent hipcc / ROCm 7.2 into "Illegal
+// instruction detected: Operand has incorrect register class".)
+__device__ __forceinline__ int block_last_nonzero(int last, int n, int* wmin) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(last, off); last = o > last ? o : last; }
+    if (lane == 0) wmin[wave] = last;
+    __syncthreads();
+    int h = wmin[0];
+#pragma unroll
+    for (int w = 1; w < SMP_W; w++) h = wmin[w] > h ? wmin[w] : h;
+    __syncthreads();
+    return h < 0 ? n - 1 : h;
 }
 
 // Vocabularies of up to 32 x 1024 entries, a multiple of 8: the softmax's elementwise work (a division, an exponential) and its
@@ -453,7 +474,12 @@ __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int
         } else {
             { float pk[SMP_E] = {}; hit = scan_search_phase<false>([&](int i, int) { return keys[i]; }, pk, n, threshold, red, wmin); }
         }
-        if (tid == 0) token = hit == 0x7fffffff ? n - 1 : hit;                   // indices[t] == t
+        if (hit == 0x7fffffff) {                                                 // (block-uniform)
+            int last = -1;
+            for (int i = tid; i < n; i += SMP_T) if (keys[i] != 0) last = i;
+            hit = block_last_nonzero(last, n, wmin);
+        }
+        if (tid == 0) token = hit;                                               // indices[t] == t
     } else if (onchip) {                                                         // sampler.h:60-69
         bool done = false;
         // ---- the nucleus first. The search stops at the first sorted entry whose prefix reaches the threshold, and a prefix is a function of the entries
@@ -661,8 +687,13 @@ __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int
 #pragma unroll
                   for (int j = 0; j < SMP_E; j++) pk[j] = h2f((uint16_t)(buf[j * SMP_T + tid] >> 16));     // (a thread's E consecutive entries: stride 1024, conflict-free)
                   hit = scan_search_phase<true>([](int, int) { return (uint16_t)0; }, pk, n, threshold, red, wmin); }
+        if (hit == 0x7fffffff) {                                                 // (block-uniform)
+            int last = -1;
+            for (int i = tid; i < n; i += SMP_T) { const int t = i / E; if ((buf[(i - t * E) * SMP_T + t] >> 16) != 0u) last = i; }
+            hit = block_last_nonzero(last, n, wmin);
+        }
         if (tid == 0) {
-            const int mi = hit == 0x7fffffff ? n - 1 : hit;                      // gpu_kernels.h:560,574
+            const int mi = hit;                                                  // gpu_kernels.h:560,574
             const int t = mi / E;
             token = (int)(buf[(mi - t * E) * SMP_T + t] & 0xffffu);
         }
@@ -673,7 +704,12 @@ __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int
         radix_pass(k0, v0, k1, v1, n, 8, cnt, wtot);
         const uint16_t* keys = k1;
         { float pk[SMP_E] = {}; hit = scan_search_phase<false>([&](int i, int) { return keys[i]; }, pk, n, threshold, red, wmin); }
-        if (tid == 0) token = v1[hit == 0x7fffffff ? n - 1 : hit];
+        if (hit == 0x7fffffff) {                                                 // (block-uniform)
+            int last = -1;
+            for (int i = tid; i < n; i += SMP_T) if (keys[i] != 0) last = i;
+            hit = block_last_nonzero(last, n, wmin);
+        }
+        if (tid == 0) token = v1[hit];
     }
     SMP_STAMP(6);
     if (x_next != nullptr) {                                 // (uniform: a kernel argument)

@@ -463,7 +463,7 @@ static float pairwise_sum(const float *v, int n) {
  * descending sort of fp16 probabilities (cub radix sort is stable: equal keys keep
  * ascending index order), fp16 inclusive prefix sum (order of cub DeviceScan is
  * unspecified; restated in the fixed thread/lane/wave order documented below),
- * first index whose prefix >= threshold (else n-1). Returns the token id. */
+ * first index of probability > 0 whose prefix >= threshold (else the last such index). Returns the token id. */
 static int cmp_desc_stable(const void *a, const void *b) {
     const uint32_t *pa = (const uint32_t *)a, *pb = (const uint32_t *)b;
     /* key = fp16 bits of a non-negative probability: monotonic as unsigned */
@@ -492,7 +492,7 @@ int orc_sample_topp(f16 *logits, int n, float temperature, float topp, float coi
     /* fp16 inclusive prefix sum in the HIP kernel's fixed, cub-shaped order (cub::DeviceScan's own order is
      * unspecified): 1024 "threads" each sum their E consecutive entries sequentially, a Hillis-Steele scan runs over the
      * 64 lanes of each of the 16 "waves", the wave totals are added sequentially; every add rounds to fp16 (sampler.h:72-78
-     * scans `half`). Then the first index whose prefix >= threshold, else n-1 (gpu_kernels.h:560-577). */
+     * scans `half`). Then the first index whose prefix >= threshold (gpu_kernels.h:560-577), see below. */
     int E = (n + 1023) / 1024;
     float tot[1024], v[1024], wt[16];
     for (int t = 0; t < 1024; t++) {
@@ -507,16 +507,25 @@ int orc_sample_topp(f16 *logits, int n, float temperature, float topp, float coi
         memcpy(v, nv, sizeof(v));
     }
     for (int w = 0; w < 16; w++) wt[w] = v[w * 64 + 63];
-    int min_index = n - 1;
-    for (int t = 0; t < 1024 && min_index == n - 1; t++) {
+    /* An entry of probability 0 (a -inf logit: a banned or masked token; a logit that underflows) is never the sample. The fp16 scan is not
+     * monotone across its partition -- a thread's exclusive prefix comes from the lane scan, its predecessor's last inclusive prefix from that
+     * thread's own running sum, and the two may round apart -- so the first stored prefix >= threshold can belong to an entry that added nothing;
+     * a monotone scan never stops there, and neither does this search. No hit (the fp16 total stays below the threshold): the last entry of the
+     * order with a probability above 0, n-1 if there is none (gpu_kernels.h:560). */
+    int min_index = -1;
+    for (int t = 0; t < 1024 && min_index < 0; t++) {
         float base = 0.f;
         for (int w = 0; w < t / 64; w++) base = h2f(f2h(base + wt[w]));
         float excl = (t % 64) > 0 ? h2f(f2h(base + v[t - 1])) : base;
         float r = 0.f;
         for (int i = t * E; i < n && i < t * E + E; i++) {
             r = h2f(f2h(r + h2f((f16)kv[2 * i])));
-            if (h2f(f2h(excl + r)) >= threshold) { min_index = i; break; }
+            if ((f16)kv[2 * i] != 0 && h2f(f2h(excl + r)) >= threshold) { min_index = i; break; }
         }
+    }
+    if (min_index < 0) {
+        min_index = n - 1;
+        for (int i = n - 1; i >= 0; i--) if ((f16)kv[2 * i] != 0) { min_index = i; break; }
     }
     (void)tot;
     int tok = (int)kv[2 * min_index + 1];

@@ -11,6 +11,7 @@ import pytest
 
 import logprobs_ref
 import sampling_controls_ref as ref
+import teacher_forced
 from conftest import GOLDEN, ROOT
 from llama_cu_awq_amd import synth
 from test_logprobs_gpu import _distributions
@@ -212,35 +213,11 @@ def _stepwise(q4, t, prompt, steps):
 
 
 def _raw_logits(q4, path, tokens):
-    """the sequence teacher-forced through a model WITHOUT controls, one graph replay per step: the raw fp16 logits of every position"""
-    t = q4.Transformer(path)
-    t.reset(tokens)
-    out = []
-    for pos in range(len(tokens) - 1):
-        t.run_transformer_at(pos, 0)
-        out.append(t.logits())
-    t.close()
-    return np.stack(out)
+    return teacher_forced.raw_logits(q4, path, tokens)
 
 
 def _predict(q4, orc, raw, tokens, n_prompt, controls, bias, mode, first_coin=0):
-    """what every generating step must have chosen: the reference over the raw logits and the ring window, then the argmax (lowest index) or the
-    restated sampler with the seed's coin stream (one coin per step, prompt steps included)"""
-    L = q4.lib()
-    state = C.c_ulonglong(SEED)
-    for _ in range(first_coin):
-        L.random_f32(C.byref(state))
-    out = np.array(tokens, dtype=np.int32).copy()
-    for p in range(len(tokens) - 1):
-        coin = L.random_f32(C.byref(state))
-        if p < n_prompt - 1:
-            continue
-        x = ref.process(raw[p], tokens=tokens, pos=p, logit_bias=bias, **controls)
-        if mode == "greedy":
-            out[p + 1] = int(np.argmax(x.astype(np.float32)))
-        else:
-            out[p + 1] = orc.lib().orc_sample_topp(orc.f16_bits(x.copy()), x.shape[0], SAMPLED[0], SAMPLED[1], coin)
-    return out
+    return teacher_forced.predict(q4, orc, raw, tokens, n_prompt, controls, bias, mode, SEED, SAMPLED, first_coin)
 
 
 @pytest.fixture(scope="module")
