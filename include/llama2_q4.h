@@ -362,6 +362,18 @@ int q4_get_greedy_screen(void);
 /* Candidate rows of the model's screened steps so far (synchronises the stream): of the last one, the largest, their sum, and the number of screened steps.
  * Any pointer may be NULL. All zero for a model without a screening copy; Q4_ERR_ARG for a Transformer the library did not build. */
 int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* total, long long* steps);
+
+/* Prompt ingest (csrc/prompt_pass.h): the library's token loop (q4_generate, q4_generate_ids, q4_generate_ids_from) runs up to max_tokens
+ * consecutive prompt-only positions -- those in front of num_prompt_tokens - 1, the step that generates -- as ONE pass over the weights: every launch reads
+ * its weights once and multiplies all the positions' activations. The K / V rows, the generated tokens and the final logits are the per-token steps', bit
+ * for bit; a pass runs no classifier, so RunState::logits is not written by the positions it covers. Taken only where the result is the same and nothing
+ * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits), fusion level
+ * >= 3, an fp16 K / V cache, positions below 256, log-probability records off, no guide, no adaptive truncation, no context-shift offset, an unmasked
+ * stream; everything else -- and q4_run_transformer*, q4_score_ids, q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
+ * clamped to 8, the default. q4_prompt_passes: passes run since the library was loaded. */
+void q4_set_prompt_ingest(int max_tokens);
+int q4_get_prompt_ingest(void);
+int q4_prompt_passes(void);
 /* Op-level form of a screened step for tests and tools: x [n], w [d][n] and rms_w [n] (may be NULL: x is taken as it is) are device pointers to halves; a
  * screening copy of w is built and freed inside the call. Host outputs, any may be NULL: the greedy token, A and B [d] floats (approximate logit and radius,
  * B = +inf where no claim is made), the refined logits [d] halves (exact on candidate rows, -inf elsewhere), the number of candidate rows. Shapes the

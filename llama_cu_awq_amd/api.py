@@ -198,6 +198,7 @@ SYMBOLS = [
     "q4_rope_rotation_freqs",
     "q4_sampler_set_dry", "q4_sampler_get_dry", "q4_sampler_set_dry_breakers", "q4_parse_dry", "q4_dry_penalty_table", "q4_dry_penalty",
     "q4_sampler_set_adaptive", "q4_sampler_get_adaptive", "q4_parse_adaptive", "q4_get_adaptive_records", "q4_adaptive_mask",
+    "q4_set_prompt_ingest", "q4_get_prompt_ingest", "q4_prompt_passes",
 ]
 
 _lib = None
@@ -333,6 +334,9 @@ def lib():
         L.q4_set_greedy_screen.restype = None
         L.q4_screen_candidates.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         L.q4_greedy_screen_op.argtypes = [vp, vp, i, i, vp, C.POINTER(i), vp, vp, vp, C.POINTER(i)]
+    if hasattr(L, "q4_set_prompt_ingest"):         # (older builds under tools/ab.py do not have it)
+        L.q4_set_prompt_ingest.argtypes = [i]
+        L.q4_set_prompt_ingest.restype = None
     if hasattr(L, "q4_sampler_set_controls"):      # (older builds under tools/ab.py do not have it)
         L.q4_sampler_set_controls.argtypes = [vp, C.POINTER(SamplingControls)]
         L.q4_sampler_get_controls.argtypes = [vp, C.POINTER(SamplingControls)]
@@ -689,6 +693,20 @@ def greedy_screen_op(x, w, n, d, rms_w=None):
 
 def set_greedy_screen(on):
     lib().q4_set_greedy_screen(int(on))
+
+
+def set_prompt_ingest(max_tokens):
+    """q4_set_prompt_ingest: positions per prompt pass of the token loop, 0 off (csrc/prompt_pass.h)."""
+    lib().q4_set_prompt_ingest(int(max_tokens))
+
+
+def get_prompt_ingest():
+    return lib().q4_get_prompt_ingest()
+
+
+def prompt_passes():
+    """Prompt passes run since the library was loaded (q4_prompt_passes)."""
+    return lib().q4_prompt_passes()
 
 
 def synchronize():

@@ -1,0 +1,18 @@
+// prompt_pass.h -- a prompt pass: up to PROMPT_PASS_MAX consecutive prompt-only positions run layer by layer with ONE read of every weight
+// (prompt_pass.hip). What q4_step.hip's token loop and q4_model.hip see of it.
+#pragma once
+#include "q4_model.h"
+
+namespace q4 {
+
+constexpr int PROMPT_PASS_MAX = 8;      // tokens per weight read (T)
+
+// The geometry part of the admission (q4_step.hip decides the rest): Llama-2-7B's shape -- dim 4096, multi-head, 128-wide heads, a hidden size the
+// three-phase FFN launch admits (its down projection is the two-part K split in three k-slots), a rotation table, an fp16 cache, an unmasked stream.
+bool prompt_pass_covers(const Config* p, const Model* m);
+// Positions *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all below bin 256's end, all prompt-only) on the launch stream: K / V rows of every layer, then
+// RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No classifier, no sampler.
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n);
+void prompt_pass_release(const RunState* s);   // q4_free_transformer: the pass's scratch vectors of this model
+
+}  // namespace q4

@@ -1,0 +1,450 @@
+// prompt_pass.hip -- a prompt pass (prompt_pass.h): n consecutive prompt-only positions run layer by layer, every launch reading its
+// weights ONCE into registers and looping over the n tokens' activations. Five launches per layer -- rmsnorm + q/k/v + RoPE + K/V write, attention (one
+// block per (token, head, V slice)), o-proj + residual, rmsnorm + gate/up + SiLU, down projection + residual -- between an embedding launch and one that
+// leaves RunState::x and the position words as the per-token steps would. No launch waits for another block: every dependency is a launch boundary.
+//
+// The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
+// parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
+// the epilogue -- not by which kernel, block shape or neighbour columns compute it (gemv_q4.h; the strips, the sixteen-wave o-proj role and the three-phase
+// FFN launch rest on the same fact). The body below is gemv_q4_body's steps with a token loop around steps 3 - 5, the tokens staged in groups; the attention blocks call attention_body
+// with the template arguments of attention_oproj16_kernel<5 | 6>.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <math.h>
+#include <map>
+#include "layer_attn.h"
+#include "prompt_pass.h"
+
+namespace q4 {
+
+constexpr int PP_WAVES = 16;           // waves per block: four per SIMD hide each other's issue latency (a wave alone issues a VALU instruction every ~5 cycles)
+constexpr int PP_QKV_WAVES = 12;       // q/k/v: 3 x 1024 column groups = 256 blocks of twelve waves, one per CU (sixteen-wave blocks: 192, a quarter of the CUs idle)
+
+// One wave owns COLS columns (KS = 2: one of the two k-parts of them); W / ZW / SC stay in registers while the tokens pass. Token t reads x + t * K and
+// writes out + t * N (q/k/v: q + t * N, cache rows p0 + t), p0 = *pPos -- the device position, which no launch of the pass but the last one moves.
+template <int SLOTS, int KS, bool NORM, int G>
+constexpr size_t prompt_gemv_lds() {      // G tokens' permuted x and x-only sums, their norm partials, the K split's exchange slots
+    using L = LdsLayout<SLOTS, KS>;
+    return (size_t)G * (L::XS + L::SX + (NORM ? (size_t)L::NUNITS * 4 : 0)) + 1024 + 16;
+}
+template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW>
+__global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, const int ntok) {
+    constexpr int NMAT = ModeTraits<MODE>::NMAT;
+    static_assert(G >= 1 && G <= 8, "exchange slots");
+    static_assert(KS == 1 || (KS == 2 && MODE == MODE_PLAIN && !NORM), "K split: plain GEMV");
+    static_assert(COLS >= 1 && COLS <= 4 && (MODE != MODE_QKV || COLS == 4), "one reduce4_q4 row per column; q/k/v: two RoPE pairs per wave");
+    using Lds = LdsLayout<SLOTS, KS>;
+    constexpr int TS = Lds::ROWS;
+    constexpr int NUNITS = Lds::NUNITS;
+    constexpr int NI = (NUNITS + NW * 64 - 1) / (NW * 64);   // staging steps of the block
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32x4* xs = reinterpret_cast<u32x4*>(smem);                                   // [G][TS][4][64] permuted x
+    float* sx = reinterpret_cast<float*>(smem + G * Lds::XS);                     // [G][TS][64]
+    float* part = reinterpret_cast<float*>(smem + G * (Lds::XS + Lds::SX));       // [G][NUNITS] norm partials, or [G][NW][4] k-part totals
+
+    const unsigned tid = threadIdx.x;
+    const unsigned lane = tid & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int nw = NW;
+    // q/k/v: the three matrices' column groups are dealt as one range (N / 4 groups each), so the grid divides by any block width
+    const int gidx = blockIdx.x * (nw / KS) + wave / KS;
+    const int gpm = MODE == MODE_QKV ? a.N / COLS : 1;       // column groups per matrix
+    const int mat0 = MODE == MODE_QKV ? __builtin_amdgcn_readfirstlane(gidx / gpm) : 0;
+    const int wg = MODE == MODE_QKV ? gidx - mat0 * gpm : gidx;
+    const int khalf = wave % KS;
+    const unsigned ubase = KS > 1 ? (unsigned)(khalf * a.ku) : 0u;
+    const unsigned uend = KS > 1 ? (ubase + (unsigned)a.ku < (unsigned)a.pw4 ? ubase + (unsigned)a.ku : (unsigned)a.pw4) : (unsigned)a.pw4;
+    const unsigned nchunks = (unsigned)a.K >> 3;
+    const int N = a.N;
+
+    int col[COLS];
+    if (MODE == MODE_QKV) {
+        constexpr int P = COLS / 2;
+        const int hp = a.head_size >> 1;
+#pragma unroll
+        for (int pi = 0; pi < P; pi++) {
+            const int p = wg * P + pi;
+            const int head = p / hp, i = p - head * hp;
+            col[pi] = head * a.head_size + i;
+            col[P + pi] = col[pi] + hp;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < COLS; c++) col[c] = wg * COLS + c;
+    }
+    int colc[COLS];
+#pragma unroll
+    for (int c = 0; c < COLS; c++) colc[c] = col[c] < N ? col[c] : N - 1;
+
+    int p0 = 0;
+    if (MODE == MODE_QKV) p0 = *a.pPos;
+
+    // ---- the first activations, the norm weights, then every weight / zero / scale of the wave (gemv_q4_body's loads: clamped, bounded descriptors).
+    // A normalising kernel (K = 4096: one chunk per thread) holds a whole group's chunks; the others hold one token's and fetch the next while they stage.
+    u32x4 xg[NORM ? G : 1][NI], wraw[NI];
+    auto load_x = [&](int t, u32x4 (&xr)[NI]) {
+        const int tc = t < ntok ? t : ntok - 1;             // past the pass's last token: the last one again (a load nobody stages)
+        const u32x4* xt = reinterpret_cast<const u32x4*>(a.x + (size_t)tc * a.K);
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const unsigned u = tid + i * (NW * 64);
+            xr[i] = xt[u < nchunks ? u : nchunks - 1];
+        }
+    };
+    if (NORM) {
+#pragma unroll
+        for (int g = 0; g < G; g++) load_x(g, xg[NORM ? g : 0]);
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const unsigned u = tid + i * (NW * 64);
+            wraw[i] = reinterpret_cast<const u32x4*>(a.rms_w)[u < nchunks ? u : nchunks - 1];
+        }
+    } else {
+        load_x(0, xg[0]);
+    }
+    u32x4 W[NMAT][SLOTS][COLS];
+    unsigned ZW[NMAT][SLOTS][COLS];
+    uint16_t SC[NMAT][SLOTS][COLS];
+    __amdgpu_buffer_rsrc_t rw[NMAT], rz[NMAT], rs[NMAT];
+#pragma unroll
+    for (int m = 0; m < NMAT; m++) {
+        const GemvMat& M = a.m[mat0 + m];
+        rw[m] = __builtin_amdgcn_make_buffer_rsrc((void*)M.w, 0, N * a.pw4 * 16, 0x00020000);
+        rz[m] = __builtin_amdgcn_make_buffer_rsrc((void*)M.z, 0, N * a.pzh * 4, 0x00020000);
+        rs[m] = __builtin_amdgcn_make_buffer_rsrc((void*)M.s, 0, N * a.sh * 2, 0x00020000);
+    }
+#pragma unroll
+    for (int s = 0; s < SLOTS; s++) {
+        const unsigned j = ubase + s * 64 + lane;
+        const unsigned jj = j < uend ? j : uend - 1;        // tail lanes re-read the part's last unit
+#pragma unroll
+        for (int m = 0; m < NMAT; m++)
+#pragma unroll
+            for (int c = 0; c < COLS; c++) {
+                ZW[m][s][c] = __builtin_amdgcn_raw_buffer_load_b32(rz[m], (jj >> 5) * 4, colc[c] * a.pzh * 4, Q4_ZS_AUX);
+                SC[m][s][c] = __builtin_amdgcn_raw_buffer_load_b16(rs[m], (jj >> 2) * 2, colc[c] * a.sh * 2, Q4_ZS_AUX);
+                W[m][s][c] = __builtin_amdgcn_raw_buffer_load_b128(rw[m], jj * 16, colc[c] * a.pw4 * 16, Q4_W_AUX);
+            }
+    }
+
+    const int row = lane >> 4;
+    const bool writer = (lane & 15u) == 0;
+    int qkv_n = 0, qkv_i = 0;                                // q/k/v: this row's output column and its pair's index inside the head
+    if (MODE == MODE_QKV) {
+        const int hp = a.head_size >> 1;
+        const int p = wg * 2 + (row & 1);
+        const int head = p / hp;
+        qkv_i = p - head * hp;
+        qkv_n = head * a.head_size + qkv_i + ((row & 2) ? hp : 0);
+    }
+
+    // Tokens go through in groups of G: the group's vectors are staged side by side in LDS behind ONE pair of barriers (a token's own chain of load, norm,
+    // stage and barriers costs more than its dot products), then each is consumed against the registers. Every token's arithmetic is its own.
+    for (int t0 = 0; t0 < ntok; t0 += G) {
+        const int ng = ntok - t0 < G ? ntok - t0 : G;
+        if (t0 > 0) __syncthreads();                         // the previous group's readers of xs / sx / part are done
+        // ---- 3. stage the group's x (gemv_q4_body's stage_tail per token)
+        const unsigned sgn = q4_stage_sign_bits(tid);
+        if constexpr (NORM) {
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                if (g < ng) {
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        const unsigned u = tid + i * (NW * 64);
+                        if (u < NUNITS) part[g * NUNITS + u] = u < nchunks ? sumsq8(xg[g][i], 0.f) : 0.f;
+                    }
+                }
+            __syncthreads();
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                if (g < ng) {
+                    const float ss = q4_signed_scale(rms_scale_from_partials<NUNITS>(part + g * NUNITS, NUNITS, a.K), sgn);
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        const unsigned u = tid + i * (NW * 64);
+                        u32x4 v = rms_apply8(xg[g][i], wraw[i], ss);
+                        if (u >= nchunks) v = (u32x4){0u, 0u, 0u, 0u};
+                        q4_stage_chunk(xs + g * NUNITS, sx + g * (TS * 64), u, v, NUNITS);
+                    }
+                }
+        } else {
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                if (g < ng) {
+                    u32x4 xn[NI];
+                    load_x(t0 + g + 1, xn);                  // the next token's x travels while this one is staged
+#pragma unroll
+                    for (int i = 0; i < NI; i++) {
+                        const unsigned u = tid + i * (NW * 64);
+                        u32x4 v = q4_signed_x(xg[0][i], sgn);
+                        if (u >= nchunks) v = (u32x4){0u, 0u, 0u, 0u};
+                        q4_stage_chunk(xs + g * NUNITS, sx + g * (TS * 64), u, v, NUNITS);
+                    }
+#pragma unroll
+                    for (int i = 0; i < NI; i++) xg[0][i] = xn[i];
+                }
+        }
+        __syncthreads();
+        if constexpr (NORM) {
+            if (t0 + G < ntok) {                             // the next group's x travels while this one multiplies
+#pragma unroll
+                for (int g = 0; g < G; g++) load_x(t0 + G + g, xg[NORM ? g : 0]);
+            }
+        }
+
+        // what the group's epilogues read from memory, requested in front of its dot products (read in the epilogue, each is a dependent round trip per
+        // token): the residual of the lane's output (this lane is its only writer), the rotation of its pair
+        const int n_out = MODE == MODE_QKV ? qkv_n : wg * COLS + row;
+        const bool out_lane = writer && (MODE == MODE_QKV || row < COLS) && (KS == 1 || khalf == 0) && n_out < N;
+        uint16_t resid[G];
+        float2 rot[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            resid[g] = 0;
+            rot[g] = float2{1.f, 0.f};
+            if (g < ng) {
+                if (MODE == MODE_PLAIN && a.accum && out_lane) resid[g] = a.out[0][(size_t)(t0 + g) * N + n_out];
+                if (MODE == MODE_QKV && mat0 < 2) rot[g] = a.rope_table[(size_t)(p0 + t0 + g) * (a.head_size >> 1) + qkv_i];
+            }
+        }
+
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g >= ng) break;
+            const int t = t0 + g;
+            const u32x4* xst = xs + g * NUNITS;
+            const float* sxt = sx + g * (TS * 64);
+            // the nibble masks are taken again for every token (q4_dot_unit): kept across the token loop they are four registers per weight register
+#pragma unroll
+            for (int m = 0; m < NMAT; m++)
+#pragma unroll
+                for (int s = 0; s < SLOTS; s++)
+#pragma unroll
+                    for (int c = 0; c < COLS; c++) asm volatile("" : "+v"(W[m][s][c]));
+            // ---- 4. consume in slot order
+            float colsum[NMAT][4];
+#pragma unroll
+            for (int m = 0; m < NMAT; m++)
+#pragma unroll
+                for (int c = 0; c < 4; c++) colsum[m][c] = 0.f;
+#pragma unroll
+            for (int s = 0; s < SLOTS; s++) {
+                unsigned j = ubase + s * 64 + lane;
+                unsigned jx = j;
+                if (KS > 1) {                                // past the part's end: the all-zero row
+                    jx = j < uend ? j : (unsigned)((TS - 1) * 64);
+                    j = j < uend ? j : uend - 1;
+                }
+                u32x4 X[4];
+                const unsigned xrow = KS > 1 ? ((jx >> 6) << 8) + (jx & 63u) : (unsigned)((s * 4) << 6) + lane;
+#pragma unroll
+                for (int d = 0; d < 4; d++) X[d] = xst[xrow + (d << 6)];
+                const float corr = sxt[KS > 1 ? jx : (unsigned)(s * 64) + lane];
+                const unsigned zsh = ((j >> 2) & 7u) * 4u;
+#pragma unroll
+                for (int m = 0; m < NMAT; m++)
+#pragma unroll
+                    for (int c = 0; c < COLS; c++) {
+                        const float tt = q4_dot_unit(W[m][s][c], X, ZW[m][s][c], zsh, corr);
+                        colsum[m][c] = __builtin_fmaf(h2f(SC[m][s][c]), tt, colsum[m][c]);
+                    }
+            }
+
+            // ---- 5. reduction (row r: the wave's column r; rows past COLS reduce zeros) + epilogue
+            if constexpr (MODE == MODE_PLAIN) {
+                float tot = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
+                if (KS > 1) {                                // fixed order: k-parts from the lowest up (a slot of its own per token of the group)
+                    float* ex = part + g * (NW * 4);
+                    if (writer) ex[wave * 4 + row] = tot;
+                    __syncthreads();
+                    if (khalf == 0) tot += ex[(wave + 1) * 4 + row];
+                }
+                if (out_lane) {
+                    float r = tot;
+                    if (a.accum) r += h2f(resid[g]);
+                    a.out[0][(size_t)t * N + n_out] = f2h(r);
+                }
+            } else if constexpr (MODE == MODE_FFN) {         // gate in gg and up in uu
+                const float gg = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
+                const float uu = reduce4_q4(colsum[NMAT - 1][0], colsum[NMAT - 1][1], colsum[NMAT - 1][2], colsum[NMAT - 1][3]) * 1048576.f;
+                float val = gg;
+                val *= 1.0f / (1.0f + expf(-val));           // gpu_kernels.h:271
+                val *= uu;                                   // :272
+                if (out_lane) a.out[0][(size_t)t * N + n_out] = f2h(val);
+            } else {                                         // MODE_QKV: rows = pair0 first, pair1 first, pair0 second, pair1 second
+                const int pos = p0 + t;
+                q4_half* out = mat0 == 0 ? a.out[0] + (size_t)t * N : a.out[mat0] + (size_t)a.loff + (size_t)pos * N;
+                const float mine = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
+                float r = mine;
+                if (mat0 < 2) {
+                    const float other = round_h(__shfl_xor(mine, 32));
+                    const float me = round_h(mine);
+                    const float fcr = rot[g].x, fci = rot[g].y;
+                    r = (row & 2) ? (other * fci + me * fcr) : (me * fcr - other * fci);    // gpu_kernels.h:345-346
+                }
+                if (out_lane) out[n_out] = f2h(r);
+            }
+        }
+    }
+}
+
+// Attention of the pass: block b of token t is unit b of attention_oproj16_kernel's attention role at position p0 + t -- the rows up to it were written by
+// the launch in front. The role's granules go to a sink of the pass's own with tag 0 (no launch's tag); what counts is the plain copy in xb[t].
+__global__ void __launch_bounds__(LA16_WAVES * 64) prompt_attention_kernel(const AttArgs a0, const int* pos_arr, u32x2v* sink, const unsigned sink_stride,
+                                                                           const unsigned nheads, const unsigned natt, const int dim) {
+    const unsigned t = blockIdx.x / natt, b = blockIdx.x % natt;
+    AttArgs a = a0;
+    a.pPos = pos_arr + t;
+    a.q = a0.q + (size_t)t * dim;
+    a.output = a0.output + (size_t)t * dim;
+    Handoff ho = {};
+    ho.pub = sink + (size_t)t * sink_stride;
+    const int pos = __builtin_amdgcn_readfirstlane(pos_arr[t]);
+    if (pos < 128) {
+        a.lds_scores = 128;
+        attention_body<16, 2, LA16_WAVES, 2, false, 4, 0, 8>(a, (int)(b % nheads), ho, (int)(b / nheads));
+    } else {
+        a.lds_scores = 256;
+        attention_body<16, 4, LA16_WAVES, 2, false, 4, 128, 8>(a, (int)(b % nheads), ho, (int)(b / nheads));
+    }
+}
+
+// the n tokens' embedding rows, and the positions of the pass for its attention blocks
+__global__ void prompt_embed_kernel(q4_half* xs, const q4_half* table, int dim, const int* tokens, const int* pPos, int* pos_arr) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    const int pos = *pPos + t;
+    if (u == 0) pos_arr[t] = pos;
+    if (u >= (dim >> 3)) return;
+    const int token = tokens[pos];
+    reinterpret_cast<u32x4*>(xs + (size_t)t * dim)[u] = reinterpret_cast<const u32x4*>(table + (size_t)token * dim)[u];
+}
+
+// what n per-token prompt steps leave: the last token's residual stream in RunState::x, both position words advanced by n (argmax_kernel's order)
+__global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q4_half* x_last, int dim, volatile int* pPos, int* pPosGpu, int n) {
+    for (int u = threadIdx.x; u < (dim >> 3); u += blockDim.x) reinterpret_cast<u32x4*>(x)[u] = reinterpret_cast<const u32x4*>(x_last)[u];
+    if (threadIdx.x == 0) {
+        const int pos = *pPosGpu + n;
+        __threadfence_system();
+        *pPos = pos;
+        *pPosGpu = pos;
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------
+struct PassBuf { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; u32x2v* sink; size_t sink_stride; };
+static std::map<const RunState*, PassBuf>& pass_bufs() { static std::map<const RunState*, PassBuf> b; return b; }
+
+void prompt_pass_release(const RunState* s) {
+    auto it = pass_bufs().find(s);
+    if (it == pass_bufs().end()) return;
+    if (it->second.slab) (void)hipFree(it->second.slab);
+    pass_bufs().erase(it);
+}
+
+static int pass_buf_of(const RunState* s, int dim, int hidden, PassBuf** out) {
+    auto it = pass_bufs().find(s);
+    if (it == pass_bufs().end()) {
+        const size_t T = PROMPT_PASS_MAX;
+        const size_t sink_words = line_area_words((size_t)dim / 2);      // 32-bit words of one token's granule area
+        const size_t vec = T * (size_t)dim * sizeof(q4_half), hb = T * (size_t)hidden * sizeof(q4_half);
+        const size_t bytes = 3 * vec + hb + 256 + T * sink_words * 4;
+        PassBuf b = {};
+        if (hipMalloc(&b.slab, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+        Q4_HIP(hipMemsetAsync(b.slab, 0, bytes, g_stream));
+        char* c = (char*)b.slab;
+        b.x = (q4_half*)c; c += vec;
+        b.q = (q4_half*)c; c += vec;
+        b.xb = (q4_half*)c; c += vec;
+        b.hb = (q4_half*)c; c += hb;
+        b.pos = (int*)c; c += 256;
+        b.sink = (u32x2v*)c;
+        b.sink_stride = sink_words / 2;
+        it = pass_bufs().insert({s, b}).first;
+    }
+    *out = &it->second;
+    return Q4_OK;
+}
+
+static void fill_mat(GemvMat& m, const QWeight* w) { m.w = w->weight; m.z = w->zeros; m.s = w->scales; }
+static void fill_geom(GemvArgs& a, int K, int N) {
+    const QGeom g = make_geom(K, N);
+    a.K = K; a.N = N; a.pw4 = g.pw4; a.pzh = g.pzh; a.sh = g.sh; a.nslots = g.nslots;
+    a.loff = -1;
+}
+
+bool prompt_pass_covers(const Config* p, const Model* m) {
+    if (!p || !m || !m->rope_table || !m->sync || m->kv_format != Q4_KV_FP16) return false;
+    const int dim = p->dim, hidden = p->hidden_dim;
+    if (dim != 4096 || p->n_heads != p->n_kv_heads || p->n_heads * 128 != dim || (hidden & 31)) return false;
+    if (!ffn_pair_covers(dim, hidden)) return false;
+    const QGeom g = make_geom(hidden, dim);
+    const int ku = (divUp(g.pw4, 2) + 3) & ~3;
+    if (divUp(ku, 64) != 3 || ku - 128 <= 32 || ku * 2 < g.pw4) return false;        // the two-part K split in three k-slots, no shared half slot
+    return stream_cu_count() == cu_count();
+}
+
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
+    if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
+    const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
+    PassBuf* b = nullptr;
+    Q4_TRY(pass_buf_of(s, dim, hidden, &b));
+    constexpr int TB = PP_WAVES * 64;
+    constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
+    static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024, "no LDS opt-in");
+    Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
+              (const int*)s->pos, b->pos);
+    Q4_LAUNCH_CHECK();
+    const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
+    const unsigned natt = (unsigned)p->n_heads * 4u;
+    for (int l = 0; l < p->n_layers; l++) {
+        const PerLayerWeight* L = &w->layers[l];
+        const long long loff = (long long)l * p->seq_len * dim;
+        {   // rmsnorm + q/k/v + RoPE + K/V rows
+            GemvArgs a = {};
+            fill_geom(a, dim, dim);
+            fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
+            a.out[0] = b->q; a.out[1] = s->key_cache; a.out[2] = s->value_cache;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff;
+            a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
+            Q4_LAUNCH_CHECK();
+        }
+        {   // attention
+            const AttArgs a = {b->xb, b->q, s->key_cache + loff, s->value_cache + loff, head_size, 1, dim, b->pos, alpha, 256, nullptr};
+            Q4_LAUNCH(prompt_attention_kernel, dim3((unsigned)n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, b->sink, (unsigned)b->sink_stride,
+                      (unsigned)p->n_heads, natt, dim);
+            Q4_LAUNCH_CHECK();
+        }
+        {   // o-proj + residual
+            GemvArgs a = {};
+            fill_geom(a, dim, dim);
+            fill_mat(a.m[0], &L->wq_o);
+            a.out[0] = b->x; a.x = b->xb; a.accum = 1;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 2, 1, false, 1, 4, PP_WAVES>), dim3(dim / PP_WAVES), dim3(TB), SMEM_O, a, n);
+            Q4_LAUNCH_CHECK();
+        }
+        {   // rmsnorm + gate/up + SiLU
+            GemvArgs a = {};
+            fill_geom(a, dim, hidden);
+            fill_mat(a.m[0], &L->wq_gate); fill_mat(a.m[1], &L->wq_up);
+            a.out[0] = b->hb; a.x = b->x; a.rms_w = L->rms_ffn_weight;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
+            Q4_LAUNCH_CHECK();
+        }
+        {   // down projection + residual: two k-parts, part 0 then part 1
+            GemvArgs a = {};
+            fill_geom(a, hidden, dim);
+            fill_mat(a.m[0], &L->wq_down);
+            a.ku = (divUp(a.pw4, 2) + 3) & ~3;
+            a.out[0] = b->x; a.x = b->hb; a.accum = 1;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 2, 2, PP_WAVES>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN, a, n);
+            Q4_LAUNCH_CHECK();
+        }
+    }
+    Q4_LAUNCH(prompt_finish_kernel, dim3(1), dim3(1024), 0, s->x, (const q4_half*)(b->x + (size_t)(n - 1) * dim), dim, &(s->shared_data->pos), s->pos, n);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+
+}  // namespace q4

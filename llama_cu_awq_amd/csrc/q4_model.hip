@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 #include "q4_model.h"
+#include "prompt_pass.h"
 #include "option_text.h"
 
 namespace q4 {
@@ -501,6 +502,7 @@ void q4_free_transformer(Transformer* t) {                                      
         hipDeviceSynchronize();
         guide_release(&m);
         adaptive_release(&m);
+        prompt_pass_release(&t->state);
         for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.inv_freq_dev, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);

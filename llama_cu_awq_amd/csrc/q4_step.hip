@@ -11,6 +11,7 @@
 #include <vector>
 #include "q4_model.h"
 #include "q4_loop.h"
+#include "prompt_pass.h"
 #include "option_text.h"
 
 namespace q4 {
@@ -124,6 +125,31 @@ static bool step_screens(const Model* m, bool may_screen, int gen_token, bool gr
            !any_stage_on(sampler, m) && cls_screen_shape(m->screen.n, m->screen.d);
 }
 
+// A prompt pass (prompt_pass.h) in place of the per-token prompt steps from `pos`: how many positions it takes, 0 for none. Only a token
+// loop asks (the per-step entry points, scoring and perplexity keep their steps), and only where the pass computes what the steps would and nothing reads
+// what it leaves out: the switch on; the fusion level in force >= 3 with the V-slice attention form (5 / 6) for every bin the pass touches -- so never the
+// level-1 redo after a time-out --; the geometry prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps` and
+// below 256; no log-probability records (they describe prompt steps' logits); neither the guide nor the adaptive truncation on (their state by position is
+// put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.)
+static int g_prompt_ingest = PROMPT_PASS_MAX;
+static int g_prompt_passes = 0;
+static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int num_prompt_tokens, int steps, int off) {
+    if (g_prompt_ingest < 2 || g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0) return 0;
+    const Config* p = &t->config;
+    int n = num_prompt_tokens - 1 - pos;
+    if (n > g_prompt_ingest) n = g_prompt_ingest;
+    if (n > steps - pos) n = steps - pos;
+    if (n > 256 - pos) n = 256 - pos;
+    if (n > p->seq_len - pos) n = p->seq_len - pos;
+    if (n < 2 || guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m) || !prompt_pass_covers(p, m)) return 0;
+    const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
+    for (int bin = pos + 1 <= 128 ? 128 : 256; bin <= (pos + n <= 128 ? 128 : 256); bin *= 2) {
+        const int form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, bin, t->state.att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
+        if (form != 5 && form != 6) return 0;
+    }
+    return n;
+}
+
 }  // namespace q4
 
 using namespace q4;
@@ -150,6 +176,11 @@ void q4_set_greedy_screen(int on) {
     q4_reset_graphs();
 }
 int q4_get_greedy_screen(void) { return g_greedy_screen; }
+
+// Prompt passes of the token loop (prompt_pass.h): the most positions one pass takes; 0 (and 1) off. No captured graph contains a pass: nothing to drop.
+void q4_set_prompt_ingest(int max_tokens) { g_prompt_ingest = max_tokens < 2 ? 0 : max_tokens > PROMPT_PASS_MAX ? PROMPT_PASS_MAX : max_tokens; }
+int q4_get_prompt_ingest(void) { return g_prompt_ingest; }
+int q4_prompt_passes(void) { return g_prompt_passes; }
 int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* total, long long* steps) {
     const Model* m = t ? model_of(&t->state) : nullptr;
     if (!m) return Q4_ERR_ARG;
@@ -667,10 +698,17 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                     Q4_TRY(q4_shift_context(t, seq_len, shift_keep, shift_discard, seq_len + 1));
                     off += shift_discard;
                 }
-                const int k = q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
+                const int np = prompt_pass_tokens(t, sm, sampler, pos - off, num_prompt_tokens - off, steps - off, off);
+                const int k = np ? np : q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                Q4_TRY(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off)));
+                if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them
+                    for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
+                    Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, np));
+                    g_prompt_passes++;
+                } else {
+                    Q4_TRY(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off)));
+                }
                 queued = pos + k;
             }
             Q4_TRY(q4_wait_pos(&t->state, pos - off));                                 // :468
