@@ -40,7 +40,8 @@ typedef enum {
     Q4_ERR_ALLOC = 2,              /* "malloc failed..." llama2_q4.cu:53-58,62-65,129-133 */
     Q4_ERR_IO = 3,                 /* "Couldn't open file" / "Invalid header size" / "error reading weights" :158,412,414 */
     Q4_ERR_HIP = 4,                /* a HIP runtime call failed (the reference never checks) */
-    Q4_ERR_ARG = 5
+    Q4_ERR_ARG = 5,
+    Q4_NOT_ADMITTED = 6            /* q4_verify_tokens only: nothing ran; run steps instead */
 } q4_status;
 
 const char* q4_status_string(int status);
@@ -380,6 +381,56 @@ int q4_prompt_passes(void);
  * classifier's strips do not cover: Q4_ERR_UNSUPPORTED_SIZE. */
 int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const q4_half* rms_w, int* token, float* A, float* B, q4_half* refined,
                         int* candidates);
+
+/* ---- speculative greedy decoding (csrc/spec_verify.h). Not in the reference. Off by default. ----
+ * A verify pass runs the token at the current position p and D drafted tokens (1 <= D <= Q4_SPEC_MAX_DRAFT) as the positions p .. p + D of ONE pass over the
+ * weights, classifier included, and accepts the m leading drafts that equal the greedy token of the row in front of them. Every row's logits are the per-token
+ * step's, bit for bit, so a pass emits exactly the m + 1 tokens that m + 1 greedy steps emit and leaves what they leave: ring[p + 1 .. p + m + 1], the
+ * position p + m + 1, RunState::logits and RunState::x of step p + m, the K / V rows. K / V rows p + m + 1 .. p + D hold rows computed from rejected drafts:
+ * they lie at or above the position (q4_common_prefix, q4_resume_sequence and snapshots never trust such rows) and are written again by whatever runs there next.
+ * A pass is admitted where a prompt pass is (q4_set_prompt_ingest above: geometry, fusion level >= 3, fp16 cache, unmasked stream, no context-shift offset,
+ * log-probability records off, no guide) and, in a token loop, only for a greedy sampler (temperature 0) with no logit stage on (sampling controls, logit
+ * bias, DRY, adaptive truncation), with p + D < 256, inside `steps` and seq_len. Cost (7B, measured: DESIGN.md 3.8): a pass pays where drafts are usually
+ * right and loses where they are not. */
+#define Q4_SPEC_MAX_DRAFT 7
+#define Q4_SPEC_MAX_NGRAM 8
+/* The primitive, at the current position (synchronises before and after): out_tokens receives the *n_accepted + 1 tokens the pass emitted (room for
+ * n_draft + 1), the first *n_accepted of them equal to draft[]. Q4_ERR_ARG before any launch: a null pointer, n_draft outside 1 .. Q4_SPEC_MAX_DRAFT, an id
+ * outside [0, vocab), a Transformer the library did not build. Q4_NOT_ADMITTED, nothing done: the model, the settings or the position do not admit a pass
+ * (q4_verify_covers). The caller owns the sequence (q4_reset_sequence, then steps or passes); greedy, whatever a Sampler says. */
+int q4_verify_tokens(Transformer* t, const int* draft, int n_draft, int* out_tokens, int* n_accepted);
+int q4_verify_covers(const Transformer* t, int pos, int n_draft);      /* 1: q4_verify_tokens at position pos with n_draft drafts would run; else 0 */
+/* The library's token loops (q4_generate, q4_generate_ids, q4_generate_ids_from): at a generating position whose pass is admitted the loop asks the model's
+ * drafter for up to max_draft tokens behind the ring and, when it gets any, runs one verify pass instead of steps; else it queues steps as before and asks
+ * again behind them. Tokens, K / V rows, final logits and the Sampler's random stream are those of the loop without it. max_draft 0: off (the default,
+ * ngram_* ignored); else 1 <= max_draft <= Q4_SPEC_MAX_DRAFT and 1 <= ngram_min <= ngram_max <= Q4_SPEC_MAX_NGRAM (the built-in drafter's), or Q4_ERR_ARG. */
+int q4_set_speculative(Transformer* t, int max_draft, int ngram_max, int ngram_min);
+int q4_get_speculative(const Transformer* t, int* max_draft, int* ngram_max, int* ngram_min);
+/* "draft=4,ngram=3,min=2": any subset of the keys in any order; a key left out takes draft=4, ngram=3, min=2 (min: the value of ngram where that is 1; DESIGN.md 3.8
+ * has the measurements behind them); "draft=0" is off. Q4_ERR_ARG and the outputs
+ * untouched: an unknown key, a malformed number, a trailing comma, values q4_set_speculative refuses. */
+int q4_parse_speculative(const char* text, int* max_draft, int* ngram_max, int* ngram_min);
+/* A drafter: tokens[0 .. n_tokens) is the ring up to the current position's token; it writes up to max_draft ids to draft_out and returns how many (<= 0:
+ * none; ids outside the vocabulary end the draft in front of them). Called on the host from inside the token loop. NULL: the built-in drafter. */
+typedef int (*q4_drafter_fn)(void* ctx, const int* tokens, int n_tokens, int max_draft, int* draft_out);
+int q4_set_drafter(Transformer* t, q4_drafter_fn fn, void* ctx);
+/* The built-in (prompt-lookup) drafter, host only: for g = ngram_max down to ngram_min (g < n_tokens), the most recent EARLIER occurrence of the last g
+ * tokens -- tokens[j .. j + g) == tokens[n_tokens - g .. n_tokens) with j < n_tokens - g, the largest such j -- and what followed it: tokens[j + g ..), up to
+ * max_draft of them and no further than the ring's end. The first g with a match decides. Returns the number of ids written, 0 for no match or bad
+ * arguments. */
+int q4_spec_draft(const int* tokens, int n_tokens, int max_draft, int ngram_max, int ngram_min, int* draft_out);
+/* Verify passes run with this model, the drafts they carried and the drafts accepted, since the model was built. Any pointer may be NULL. */
+int q4_spec_stats(const Transformer* t, long long* passes, long long* drafted, long long* accepted);
+/* Op-level forms of the pass's two launches for tests and tools, on the q4 stream; device pointers unless said otherwise.
+ * q4_verify_classifier: logits [n_rows][vocab] = wcls . rmsnorm(x[r], rms_w), x [n_rows][dim], 1 <= n_rows <= 8; every row holds the bits q4_rmsnorm +
+ * q4_matmul_f16 give for that row alone. dim 4096 and a vocabulary that is a multiple of 8, else Q4_ERR_UNSUPPORTED_SIZE.
+ * q4_verify_accept: logits rows of `size` halves, `ld` halves apart (ld a multiple of 8, >= size), row r the logits at position *pos_dev + r, r <= n_draft;
+ * draft: host array. Takes each row's greedy token by q4_argmax's rule, m = the leading rows r < n_draft whose token equals draft[r], and writes
+ * ring[p + 1 .. p + m + 1], logits_out [size] = row m, x_out [dim] = row m of x [n_draft + 1][dim] (x may be NULL: no copy), then *pos_host and *pos_dev =
+ * p + m + 1. report (9 ints, may be NULL): the rows' tokens (-1 past row n_draft) and m. */
+int q4_verify_classifier(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n_rows);
+int q4_verify_accept(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
+                     int* ring, int* pos_host, int* pos_dev, int* report);
 
 /* build_sampler / destroy_sampler sampler.h:15-29; random_u32 / random_f32 :31-40; sample :43-82 */
 int build_sampler(Sampler* sampler, int vocab_size, float temperature, float topp, unsigned long long rng_seed);

@@ -172,6 +172,12 @@ class AdaptiveControls(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+NOT_ADMITTED = 6                # q4_verify_tokens: nothing ran
+SPEC_MAX_DRAFT = 7
+# q4_drafter_fn: (ctx, tokens, n_tokens, max_draft, draft_out) -> number of ids written
+DRAFTER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int))
+
+
 # every symbol include/llama2_q4.h declares (tests/test_abi.py checks the .so exports all of them)
 SYMBOLS = [
     "q4_status_string", "q4_last_error", "q4_set_device", "q4_stream_create", "q4_stream_create_masked", "q4_stream_destroy", "q4_set_stream",
@@ -199,6 +205,8 @@ SYMBOLS = [
     "q4_sampler_set_dry", "q4_sampler_get_dry", "q4_sampler_set_dry_breakers", "q4_parse_dry", "q4_dry_penalty_table", "q4_dry_penalty",
     "q4_sampler_set_adaptive", "q4_sampler_get_adaptive", "q4_parse_adaptive", "q4_get_adaptive_records", "q4_adaptive_mask",
     "q4_set_prompt_ingest", "q4_get_prompt_ingest", "q4_prompt_passes",
+    "q4_verify_tokens", "q4_verify_covers", "q4_set_speculative", "q4_get_speculative", "q4_parse_speculative", "q4_set_drafter", "q4_spec_draft",
+    "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept",
 ]
 
 _lib = None
@@ -337,6 +345,18 @@ def lib():
     if hasattr(L, "q4_set_prompt_ingest"):         # (older builds under tools/ab.py do not have it)
         L.q4_set_prompt_ingest.argtypes = [i]
         L.q4_set_prompt_ingest.restype = None
+    if hasattr(L, "q4_verify_tokens"):             # (older builds under tools/ab.py do not have it)
+        ll = C.c_longlong
+        L.q4_verify_tokens.argtypes = [vp, vp, i, vp, C.POINTER(i)]
+        L.q4_verify_covers.argtypes = [vp, i, i]
+        L.q4_set_speculative.argtypes = [vp, i, i, i]
+        L.q4_get_speculative.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+        L.q4_parse_speculative.argtypes = [C.c_char_p, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+        L.q4_set_drafter.argtypes = [vp, DRAFTER_FN, vp]
+        L.q4_spec_draft.argtypes = [vp, i, i, i, i, vp]
+        L.q4_spec_stats.argtypes = [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]
+        L.q4_verify_classifier.argtypes = [vp, vp, vp, vp, i, i, i]
+        L.q4_verify_accept.argtypes = [vp, i, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "q4_sampler_set_controls"):      # (older builds under tools/ab.py do not have it)
         L.q4_sampler_set_controls.argtypes = [vp, C.POINTER(SamplingControls)]
         L.q4_sampler_get_controls.argtypes = [vp, C.POINTER(SamplingControls)]
@@ -680,6 +700,18 @@ class Snapshot:
             pass
 
 
+def verify_classifier(logits, x, rms_w, wcls, dim, vocab, n_rows):
+    """q4_verify_classifier over DevBufs: logits [n_rows, vocab] = wcls . rmsnorm(x[r], rms_w), the verify pass's classifier launch."""
+    check(lib().q4_verify_classifier(logits.ptr, x.ptr, rms_w.ptr, wcls.ptr, dim, vocab, n_rows))
+
+
+def verify_accept(logits, ld, size, draft, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report=None):
+    """q4_verify_accept over DevBufs (draft: host ids): the verify pass's accept launch."""
+    d = np.ascontiguousarray(draft, dtype=np.int32)
+    check(lib().q4_verify_accept(logits.ptr, ld, size, d.ctypes.data, d.shape[0], x.ptr if x else None, dim, logits_out.ptr, x_out.ptr if x_out else None,
+                                 ring.ptr, pos_host.ptr, pos_dev.ptr, report.ptr if report else None))
+
+
 def greedy_screen_op(x, w, n, d, rms_w=None):
     """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
     tok, cand = C.c_int(), C.c_int()
@@ -709,6 +741,22 @@ def prompt_passes():
     return lib().q4_prompt_passes()
 
 
+def spec_draft(tokens, max_draft, ngram_max, ngram_min):
+    """q4_spec_draft, the built-in prompt-lookup drafter (host only): the ids that followed the most recent earlier occurrence of the ring's last g tokens,
+    g from ngram_max down to ngram_min; [] for no match."""
+    t = np.ascontiguousarray(tokens, dtype=np.int32)
+    out = np.zeros(max(int(max_draft), 1), dtype=np.int32)
+    n = lib().q4_spec_draft(t.ctypes.data, t.shape[0], int(max_draft), int(ngram_max), int(ngram_min), out.ctypes.data)
+    return [int(x) for x in out[:n]]
+
+
+def parse_speculative(text):
+    """q4_parse_speculative: "draft=4,ngram=3,min=2" -> dict(draft, ngram, min)"""
+    d, g, m = C.c_int(), C.c_int(), C.c_int()
+    check(lib().q4_parse_speculative(text.encode(), C.byref(d), C.byref(g), C.byref(m)))
+    return {"draft": d.value, "ngram": g.value, "min": m.value}
+
+
 def synchronize():
     check(lib().q4_stream_synchronize())
 
@@ -725,7 +773,7 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None):
+                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -788,6 +836,8 @@ class Transformer:
                 self.set_dry_breakers(dry_breakers, tokenizer=tokenizer)
             if adaptive is not None:
                 self.set_adaptive(**adaptive)
+            if speculative is not None:
+                self.set_speculative(**speculative)
         except Exception:
             self.close()
             raise
@@ -966,6 +1016,58 @@ class Transformer:
         total, steps = C.c_longlong(), C.c_longlong()
         check(lib().q4_screen_candidates(self.h, C.byref(last), C.byref(mx), C.byref(total), C.byref(steps)))
         return last.value, mx.value, total.value, steps.value
+
+    def set_speculative(self, draft=4, ngram=3, min=2):
+        """q4_set_speculative: the token loops verify up to `draft` drafted tokens per pass over the weights (0: off); ngram / min: the longest and the
+        shortest n-gram the built-in prompt-lookup drafter matches. Greedy runs only; the tokens are those of the run without it."""
+        check(lib().q4_set_speculative(self.h, int(draft), int(ngram), int(min)))
+
+    def speculative(self):
+        d, g, m = C.c_int(), C.c_int(), C.c_int()
+        check(lib().q4_get_speculative(self.h, C.byref(d), C.byref(g), C.byref(m)))
+        return {"draft": d.value, "ngram": g.value, "min": m.value}
+
+    def set_drafter(self, fn):
+        """q4_set_drafter: fn(tokens, max_draft) -> ids, tokens the ring up to the current position's token as an int32 array (valid during the call only);
+        None: the built-in drafter. Called from inside generate_ids; an exception inside it counts as no draft."""
+        if fn is None:
+            check(lib().q4_set_drafter(self.h, DRAFTER_FN(), None))
+            self._drafter = None
+            return
+
+        def call(ctx, tokens, n_tokens, max_draft, out):
+            try:
+                ids = list(fn(np.ctypeslib.as_array(tokens, shape=(n_tokens,)), max_draft))[:max_draft]
+            except Exception:
+                return 0
+            for k, v in enumerate(ids):
+                out[k] = int(v)
+            return len(ids)
+
+        cb = DRAFTER_FN(call)
+        check(lib().q4_set_drafter(self.h, cb, None))
+        self._drafter = cb              # (keeps the callback alive while the model holds it)
+
+    def verify(self, draft):
+        """q4_verify_tokens at the current position: (emitted tokens, n_accepted) -- the n_accepted leading drafts the model confirms and the token
+        behind them --, or None where a pass is not admitted and nothing ran (run steps instead)."""
+        d = np.ascontiguousarray(draft, dtype=np.int32)
+        out = np.zeros(d.shape[0] + 1, dtype=np.int32)
+        acc = C.c_int()
+        rc = lib().q4_verify_tokens(self.h, d.ctypes.data, d.shape[0], out.ctypes.data, C.byref(acc))
+        if rc == NOT_ADMITTED:
+            return None
+        check(rc)
+        return out[: acc.value + 1].copy(), acc.value
+
+    def verify_covers(self, pos, n_draft):
+        return bool(lib().q4_verify_covers(self.h, int(pos), int(n_draft)))
+
+    def spec_stats(self):
+        """(passes, drafted, accepted) of the model's verify passes (q4_spec_stats)"""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(lib().q4_spec_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def set_sampling(self, **kw):
         """Sampling controls inside the decode step (q4_sampler_set_controls): top_k, min_p, repeat_penalty, presence_penalty, frequency_penalty,

@@ -14,5 +14,11 @@ bool prompt_pass_covers(const Config* p, const Model* m);
 // RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No classifier, no sampler.
 int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n);
 void prompt_pass_release(const RunState* s);   // q4_free_transformer: the pass's scratch vectors of this model
+// What the verify pass (spec_verify.h) shares with the prompt pass: the model's scratch rows -- x [PROMPT_PASS_MAX][dim] residual streams, pos
+// [PROMPT_PASS_MAX] their positions (allocated on first use) -- and the layer loop over rows 0 .. n - 1 of them: the five launches per layer of
+// run_prompt_pass, which reads the device position and moves nothing. The caller fills x and pos in front and takes the final residual streams from x.
+struct PassRows { q4_half* x; int* pos; };
+int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out);
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n);
 
 }  // namespace q4

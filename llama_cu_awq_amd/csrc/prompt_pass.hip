@@ -384,7 +384,17 @@ bool prompt_pass_covers(const Config* p, const Model* m) {
     return stream_cu_count() == cu_count();
 }
 
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
+int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out) {
+    PassBuf* b = nullptr;
+    Q4_TRY(pass_buf_of(s, p->dim, p->hidden_dim, &b));
+    out->x = b->x;
+    out->pos = b->pos;
+    return Q4_OK;
+}
+
+// The layer loop of a pass, shared by the prompt pass below and the verify pass (spec_verify.hip): rows 0 .. n - 1 of the model's scratch rows hold the
+// positions' residual streams going in (and pos[t] their positions), and their final residual streams coming out.
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
     PassBuf* b = nullptr;
@@ -392,9 +402,6 @@ int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, c
     constexpr int TB = PP_WAVES * 64;
     constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
     static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024, "no LDS opt-in");
-    Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
-              (const int*)s->pos, b->pos);
-    Q4_LAUNCH_CHECK();
     const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
     const unsigned natt = (unsigned)p->n_heads * 4u;
     for (int l = 0; l < p->n_layers; l++) {
@@ -442,6 +449,18 @@ int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, c
             Q4_LAUNCH_CHECK();
         }
     }
+    return Q4_OK;
+}
+
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
+    if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
+    const int dim = p->dim;
+    PassBuf* b = nullptr;
+    Q4_TRY(pass_buf_of(s, dim, p->hidden_dim, &b));
+    Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
+              (const int*)s->pos, b->pos);
+    Q4_LAUNCH_CHECK();
+    Q4_TRY(prompt_pass_layers(p, s, w, m, n));
     Q4_LAUNCH(prompt_finish_kernel, dim3(1), dim3(1024), 0, s->x, (const q4_half*)(b->x + (size_t)(n - 1) * dim), dim, &(s->shared_data->pos), s->pos, n);
     Q4_LAUNCH_CHECK();
     return Q4_OK;

@@ -569,6 +569,15 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and speculative greedy decoding (q4_parse_speculative): Q4_SPECULATIVE="draft=4,ngram=3,min=2"; runs that are not greedy keep their steps
+    const char* spec = getenv("Q4_SPECULATIVE");
+    if (spec && *spec) {
+        int draft = 0, ngram = 0, ngram_min = 0;
+        if (q4_parse_speculative(spec, &draft, &ngram, &ngram_min) || q4_set_speculative(&transformer, draft, ngram, ngram_min)) {
+            fprintf(stderr, "Q4_SPECULATIVE: cannot use '%s' (keys: draft, ngram, min; draft 0 .. %d, 1 <= min <= ngram <= %d; e.g. draft=4,ngram=3,min=2)\n", spec, Q4_SPEC_MAX_DRAFT, Q4_SPEC_MAX_NGRAM);
+            exit(EXIT_FAILURE);
+        }
+    }
     int steps = a.steps;
     if (steps <= 0 || (!shifting && steps > transformer.config.seq_len)) steps = transformer.config.seq_len;   // :690
     if (shifting && steps > Q4_MAX_SEQ_LEN - 1) steps = Q4_MAX_SEQ_LEN - 1;

@@ -10,6 +10,7 @@
 #include <vector>
 #include "q4_model.h"
 #include "prompt_pass.h"
+#include "spec_verify.h"
 #include "option_text.h"
 
 namespace q4 {
@@ -369,6 +370,7 @@ const char* q4_status_string(int status) {
         case Q4_ERR_IO: return "error reading weights";                            // :158
         case Q4_ERR_HIP: return "HIP runtime error";
         case Q4_ERR_ARG: return "invalid argument";
+        case Q4_NOT_ADMITTED: return "not admitted";
     }
     return "unknown";
 }
@@ -503,6 +505,7 @@ void q4_free_transformer(Transformer* t) {                                      
         guide_release(&m);
         adaptive_release(&m);
         prompt_pass_release(&t->state);
+        verify_release(&t->state);
         for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.inv_freq_dev, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);

@@ -12,6 +12,7 @@
 #include "q4_model.h"
 #include "q4_loop.h"
 #include "prompt_pass.h"
+#include "spec_verify.h"
 #include "option_text.h"
 
 namespace q4 {
@@ -150,6 +151,37 @@ static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sample
     return n;
 }
 
+
+// A verify pass (spec_verify.h) at position `pos` with n_draft drafts, positions pos .. pos + n_draft: what a prompt pass requires -- the
+// fusion level in force >= 3 with the V-slice attention form (5 / 6) in every bin touched, prompt_pass_covers' geometry (fp16 cache, unmasked stream), no
+// log-probability records, no guide, no context-shift offset, every position below 256 and inside seq_len -- plus a classifier shape the pass's launch
+// takes. A token loop adds (sampler non-null): temperature 0, no logit stage on, every position inside `steps`. With all of that off a greedy generating
+// step leaves, by position: its K / V rows, ring[pos + 1], the two position words; and, not by position: RunState::logits, RunState::x (un-normalised
+// behind the strips classifier; what the pass writes), the scratch vectors xb / hb / q / att (rewritten by every step before it reads them), the hand-off
+// epoch (never rewound; a pass does not advance it, as a prompt pass does not), the screen's tallies (q4_screen_candidates counts screened steps: a pass
+// screens nothing). Guide states, Mirostat's mu, record rings, the coin ring and logits_array are written only by what the admission excludes.
+static bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off) {
+    if (g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0 || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
+    const Config* p = &t->config;
+    if (pos + n_draft >= 256 || pos + n_draft >= p->seq_len || pos + n_draft >= steps) return false;
+    if (sampler && (sampler->temperature != 0.0f || any_stage_on(sampler, m))) return false;
+    if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return false;
+    const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
+    for (int bin = pos + 1 <= 128 ? 128 : 256; bin <= (pos + n_draft + 1 <= 128 ? 128 : 256); bin *= 2) {
+        const int form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, bin, t->state.att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
+        if (form != 5 && form != 6) return false;
+    }
+    return true;
+}
+// The drafter's answer for ring[0 .. n_tokens), at most max_draft ids, cut in front of the first id outside the vocabulary
+static int ask_drafter(const Model* m, const int* ring, int n_tokens, int max_draft, int vocab, int* draft) {
+    int n = m->drafter ? m->drafter(m->drafter_ctx, ring, n_tokens, max_draft, draft) : q4_spec_draft(ring, n_tokens, max_draft, m->spec_ngram_max, m->spec_ngram_min, draft);
+    if (n > max_draft) n = max_draft;
+    for (int i = 0; i < n; i++)
+        if (draft[i] < 0 || draft[i] >= vocab) { n = i; break; }
+    return n < 0 ? 0 : n;
+}
+
 }  // namespace q4
 
 using namespace q4;
@@ -181,6 +213,99 @@ int q4_get_greedy_screen(void) { return g_greedy_screen; }
 void q4_set_prompt_ingest(int max_tokens) { g_prompt_ingest = max_tokens < 2 ? 0 : max_tokens > PROMPT_PASS_MAX ? PROMPT_PASS_MAX : max_tokens; }
 int q4_get_prompt_ingest(void) { return g_prompt_ingest; }
 int q4_prompt_passes(void) { return g_prompt_passes; }
+
+// ---- speculative greedy decoding: the settings, the built-in drafter, the primitive (spec_verify.h) ----
+int q4_spec_draft(const int* tokens, int n_tokens, int max_draft, int ngram_max, int ngram_min, int* draft_out) {
+    if (!tokens || !draft_out || n_tokens < 2 || max_draft < 1 || ngram_min < 1 || ngram_max < ngram_min) return 0;
+    for (int g = ngram_max < n_tokens - 1 ? ngram_max : n_tokens - 1; g >= ngram_min; g--) {
+        const int* tail = tokens + n_tokens - g;
+        for (int j = n_tokens - g - 1; j >= 0; j--) {
+            if (memcmp(tokens + j, tail, (size_t)g * sizeof(int)) != 0) continue;
+            int n = n_tokens - (j + g);
+            if (n > max_draft) n = max_draft;
+            memcpy(draft_out, tokens + j + g, (size_t)n * sizeof(int));
+            return n;
+        }
+    }
+    return 0;
+}
+static bool speculative_ok(int max_draft, int ngram_max, int ngram_min) {
+    return max_draft == 0 || (max_draft >= 1 && max_draft <= Q4_SPEC_MAX_DRAFT && ngram_min >= 1 && ngram_min <= ngram_max && ngram_max <= Q4_SPEC_MAX_NGRAM);
+}
+int q4_set_speculative(Transformer* t, int max_draft, int ngram_max, int ngram_min) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !speculative_ok(max_draft, ngram_max, ngram_min)) return Q4_ERR_ARG;
+    m->spec_draft = max_draft;
+    m->spec_ngram_max = max_draft ? ngram_max : 0;
+    m->spec_ngram_min = max_draft ? ngram_min : 0;
+    return Q4_OK;
+}
+int q4_get_speculative(const Transformer* t, int* max_draft, int* ngram_max, int* ngram_min) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    if (max_draft) *max_draft = m->spec_draft;
+    if (ngram_max) *ngram_max = m->spec_ngram_max;
+    if (ngram_min) *ngram_min = m->spec_ngram_min;
+    return Q4_OK;
+}
+int q4_parse_speculative(const char* text, int* max_draft, int* ngram_max, int* ngram_min) {
+    if (!text || !max_draft || !ngram_max || !ngram_min) return Q4_ERR_ARG;
+    long v[3] = {4, 3, -1};               // (min left out: 2, or the longest n-gram where that is shorter)
+    const char* p = text;
+    while (*p) {
+        char key[OPTION_KEY_CAP], val[32];
+        if (!next_option(&p, key, val, sizeof(val))) return Q4_ERR_ARG;
+        long* dst = !strcmp(key, "draft") ? &v[0] : !strcmp(key, "ngram") ? &v[1] : !strcmp(key, "min") ? &v[2] : nullptr;
+        if (!dst || val[0] < '0' || val[0] > '9') return Q4_ERR_ARG;          // (no sign, no leading blank)
+        char* rest = nullptr;
+        *dst = strtol(val, &rest, 10);
+        if (*rest || *dst > 1000) return Q4_ERR_ARG;
+    }
+    if (v[2] < 0) v[2] = v[1] < 2 ? v[1] : 2;
+    if (!speculative_ok((int)v[0], (int)v[1], (int)v[2])) return Q4_ERR_ARG;
+    *max_draft = (int)v[0];
+    *ngram_max = (int)v[1];
+    *ngram_min = (int)v[2];
+    return Q4_OK;
+}
+int q4_set_drafter(Transformer* t, q4_drafter_fn fn, void* ctx) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->drafter = fn;
+    m->drafter_ctx = fn ? ctx : nullptr;
+    return Q4_OK;
+}
+int q4_spec_stats(const Transformer* t, long long* passes, long long* drafted, long long* accepted) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    if (passes) *passes = m->spec_passes;
+    if (drafted) *drafted = m->spec_drafted;
+    if (accepted) *accepted = m->spec_accepted;
+    return Q4_OK;
+}
+int q4_verify_covers(const Transformer* t, int pos, int n_draft) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && verify_covers(t, m, nullptr, pos, n_draft, t->config.seq_len, 0) ? 1 : 0;
+}
+int q4_verify_tokens(Transformer* t, const int* draft, int n_draft, int* out_tokens, int* n_accepted) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !draft || !out_tokens || !n_accepted || n_draft < 1 || n_draft > Q4_SPEC_MAX_DRAFT) return Q4_ERR_ARG;
+    for (int i = 0; i < n_draft; i++)
+        if (draft[i] < 0 || draft[i] >= t->config.vocab_size) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const int pos = t->state.shared_data->pos;
+    if (m->rows_suspect || !verify_covers(t, m, nullptr, pos, n_draft, t->config.seq_len, 0)) return Q4_NOT_ADMITTED;
+    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, draft, n_draft));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const int acc = t->state.shared_data->pos - (pos + 1);
+    if (acc < 0 || acc > n_draft) return Q4_ERR_HIP;
+    m->spec_passes++;
+    m->spec_drafted += n_draft;
+    m->spec_accepted += acc;
+    for (int i = 0; i <= acc; i++) out_tokens[i] = t->state.shared_data->tokens[pos + 1 + i];
+    *n_accepted = acc;
+    return Q4_OK;
+}
 int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* total, long long* steps) {
     const Model* m = t ? model_of(&t->state) : nullptr;
     if (!m) return Q4_ERR_ARG;
@@ -671,7 +796,7 @@ static bool redo_after_timeout(const RunState* s, Sampler* sampler, unsigned lon
 // stands where the full run leaves it. q4_set_context_shift: the loop shifts at seq_len instead of stopping there, so steps may pass it; `pos` counts
 // steps, and the device runs step `pos` at position pos - off, off being the positions discarded so far.
 int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, int num_prompt_tokens, int steps, int start_pos, TokenLoop* loop) {
-    const Model* sm = model_of(&t->state);
+    Model* const sm = model_of(&t->state);
     const int seq_len = t->config.seq_len, shift_keep = sm ? sm->shift_keep : 0, shift_discard = sm ? sm->shift_discard : 0;
     // the full loop stops at the first EOS it meets in the ring behind index 0, a prompt's included: a prefix that holds one is not skipped
     for (int i = 1; i < start_pos; i++)
@@ -682,6 +807,7 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
         clock_gettime(CLOCK_MONOTONIC, &t0);
         const int start = attempt == 0 ? start_pos : 0;      // the retry after a time-out trusts no row
         int pos = start, queued = start, group_start = start, off = 0;
+        int verify_pos = -1, verify_drafts = 0;              // a verify pass queued at verify_pos whose outcome the host has not read yet
         Q4_TRY(start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start));
         if (loop->on_attempt) loop->on_attempt(loop->ctx, attempt, start);
         for (int i = 0; i < start; i++) (void)random_f32(&sampler->rng_state);
@@ -689,6 +815,17 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
         int prev = prompt_tokens[start > 0 ? start - 1 : 0];
         bool stopped = false;
         while (pos < steps) {
+            if (verify_pos >= 0 && pos == verify_pos + 1) {      // the pass's advance says how many drafts it accepted: one coin per position it ran, as the steps draw them
+                Q4_TRY(q4_wait_pos(&t->state, pos));
+                const int m = t->state.shared_data->pos - pos;
+                if (m < 0 || m > verify_drafts) return Q4_ERR_HIP;
+                for (int i = 0; i <= m; i++) (void)random_f32(&sampler->rng_state);
+                sm->spec_passes++;
+                sm->spec_drafted += verify_drafts;
+                sm->spec_accepted += m;
+                queued = pos + m;
+                verify_pos = -1;
+            }
             // the reference synchronises and then launches step `pos` (:468-470); here the launch goes out first, queued
             // behind step pos-1, and the host then waits for step pos-1's token -- same device order, no idle gap per token.
             // Steps inside one bin go out Q4_MULTI_STEPS at a time (one graph replay); a stop at EOS leaves at most
@@ -699,10 +836,25 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                     off += shift_discard;
                 }
                 const int np = prompt_pass_tokens(t, sm, sampler, pos - off, num_prompt_tokens - off, steps - off, off);
-                const int k = np ? np : q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
+                // Speculation (q4_set_speculative; spec_verify.h): at a generating position whose verify pass is admitted the host waits for the ring's
+                // entry `pos` -- everything queued so far -- and asks the drafter. The entry itself is looked at below, like any other: an EOS there stops the
+                // loop, and the pass queued behind it is surplus, as surplus steps are. No draft: the steps below, and the question again behind them.
+                int nd = 0, draft[VERIFY_MAX_DRAFT];
+                if (!np && sm && sm->spec_draft > 0 && pos >= num_prompt_tokens - 1 && verify_covers(t, sm, sampler, pos, 1, steps, off)) {
+                    Q4_TRY(q4_wait_pos(&t->state, pos));
+                    int room = sm->spec_draft;
+                    while (room > 1 && !verify_covers(t, sm, sampler, pos, room, steps, off)) room--;
+                    if (pos == 0 || t->state.shared_data->tokens[pos] != 2)      // (behind an EOS the loop stops: no pass)
+                        nd = ask_drafter(sm, (const int*)t->state.shared_data->tokens, pos + 1, room, t->config.vocab_size, draft);
+                }
+                const int k = np ? np : nd ? 1 : q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
                 group_start = pos;
                 group_rng = sampler->rng_state;
-                if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them
+                if (nd) {      // positions pos .. pos + m run, m the accepted drafts: known once the pass has published its position
+                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, draft, nd));
+                    verify_pos = pos;
+                    verify_drafts = nd;
+                } else if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them
                     for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
                     Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, np));
                     g_prompt_passes++;

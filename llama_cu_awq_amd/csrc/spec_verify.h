@@ -1,0 +1,35 @@
+// spec_verify.h -- a verify pass of speculative greedy decoding (spec_verify.hip): the token at the current position p plus D drafted
+// tokens (1 <= D <= VERIFY_MAX_DRAFT) run as the n = D + 1 positions p .. p + D of ONE pass over the weights -- the prompt pass's layer launches
+// (prompt_pass.h), then the final norm and the classifier for all n residual rows on one read of wcls, then one launch that takes each row's greedy
+// token, counts the m leading drafts the rows confirm and leaves what m + 1 greedy steps would have left. Every row's logits are, bit for bit, the logits
+// the per-token step computes at that position, so the tokens a pass emits are the tokens plain greedy decoding emits.
+//
+// What a pass leaves: ring[p + 1 .. p + m + 1] (the confirmed drafts and the token behind them), both position words = p + m + 1, RunState::logits = row
+// m's logits, RunState::x = row m's residual stream, and the K / V rows p .. p + D of every layer. Rows p + m + 1 .. p + D were computed from drafts that
+// were NOT confirmed: they lie at or above the device position, which is where q4_common_prefix, q4_resume_sequence and snapshots stop trusting rows, and
+// the next step or pass at those positions writes them again. Drafts travel by value in a kernel argument: an unconfirmed token never enters the ring or
+// pinned memory. Every dependency is a launch boundary: the pass waits on nothing in-launch and touches neither the model's hand-off words nor its
+// granules (the attention launch writes the prompt pass's own sink).
+#pragma once
+#include "prompt_pass.h"
+
+namespace q4 {
+
+constexpr int VERIFY_MAX_DRAFT = PROMPT_PASS_MAX - 1;
+
+struct VerifyDrafts { int n; int tok[VERIFY_MAX_DRAFT]; };
+
+// Geometry the classifier launch of a pass takes: dim 4096 (eight 1 KiB pieces per vocabulary row) and a vocabulary that is a multiple of 8 -- both forms
+// classifier_with_final_norm can take for such a model (strips, or rmsnorm_kernel + gemv_f16_kernel) round the same sums in the same order.
+bool verify_cls_covers(int dim, int vocab);
+// logits [n][vocab] = wcls . rmsnorm(x[t], rms_w) for rows t < n <= PROMPT_PASS_MAX, x [n][dim]; on the launch stream
+int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n);
+// The accept launch. logits: rows of `size` halves `ld` apart (ld a multiple of 8: rows stay 16-byte aligned), row t the logits at position *pPosGpu + t;
+// x: rows of dim halves. report (device, 9 ints, may be null): the rows' greedy tokens and, in [8], m.
+int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
+                         int* ring, volatile int* pPos, int* pPosGpu, int* report);
+// The whole pass at the device position; the caller (q4_step.hip's verify_covers) has admitted it. On the launch stream; nothing is waited for.
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, const int* draft, int n_draft);
+void verify_release(const RunState* s);   // q4_free_transformer: the pass's logits rows of this model
+
+}  // namespace q4

@@ -69,6 +69,8 @@ GEOMETRIES = {
     "ffn_pair7b": (4096, 11008, 2, 32, 32, 512, 300, 10000.0),
     "ffn_pair_ragged": (4096, 10496, 2, 32, 32, 512, 300, 10000.0),
     "ffn_pair_wide": (4096, 11264, 2, 32, 32, 512, 300, 10000.0),
+    # a verify pass (csrc/spec_verify.h) whose classifier has the strips form with a ragged row split (16600 rows over 256 CUs): Llama-2-7B's layer, once
+    "spec_cls_ragged": (4096, 11008, 1, 32, 32, 16600, 300, 10000.0),
 }
 
 
