@@ -369,12 +369,21 @@ int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* t
  * its weights once and multiplies all the positions' activations. The K / V rows, the generated tokens and the final logits are the per-token steps', bit
  * for bit; a pass runs no classifier, so RunState::logits is not written by the positions it covers. Taken only where the result is the same and nothing
  * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits), fusion level
- * >= 3, an fp16 K / V cache, positions below 256, log-probability records off, no guide, no adaptive truncation, no context-shift offset, an unmasked
+ * >= 3, an fp16 K / V cache, positions below the bound of q4_set_pass_context (256 unless raised), log-probability records off, no guide, no adaptive truncation, no context-shift offset, an unmasked
  * stream; everything else -- and q4_run_transformer*, q4_score_ids, q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
  * clamped to 8, the default. q4_prompt_passes: passes run since the library was loaded. */
 void q4_set_prompt_ingest(int max_tokens);
 int q4_get_prompt_ingest(void);
 int q4_prompt_passes(void);
+/* The exclusive upper bound on the positions a prompt pass or a verify pass (below) may touch. Process-wide, like q4_set_prompt_ingest; for a model the
+ * bound in force is min(positions, seq_len). The default, 256, is also the least: arguments <= 256 give 256, and passes then stay in the bins where
+ * the step's attention is the V-slice form, exactly as before the setting existed. A larger value lets passes follow the step into the split-context
+ * bins (512, 1024, 2048, ...): there a pass's attention is one launch that reads each chunk of K / V rows once for all its tokens plus one that merges
+ * every token's flash-decode records the way the step does -- the same bits, no in-launch wait. A pass never reaches across the end of a bin (256, 512,
+ * 1024, ...), and is taken only where the step's attention form at every position it touches is one the pass reproduces (a model whose scratch does not
+ * hold the records, or a residency guard that says no, keeps its steps). */
+void q4_set_pass_context(int positions);
+int q4_get_pass_context(void);
 /* Op-level form of a screened step for tests and tools: x [n], w [d][n] and rms_w [n] (may be NULL: x is taken as it is) are device pointers to halves; a
  * screening copy of w is built and freed inside the call. Host outputs, any may be NULL: the greedy token, A and B [d] floats (approximate logit and radius,
  * B = +inf where no claim is made), the refined logits [d] halves (exact on candidate rows, -inf elsewhere), the number of candidate rows. Shapes the
@@ -390,7 +399,8 @@ int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const 
  * they lie at or above the position (q4_common_prefix, q4_resume_sequence and snapshots never trust such rows) and are written again by whatever runs there next.
  * A pass is admitted where a prompt pass is (q4_set_prompt_ingest above: geometry, fusion level >= 3, fp16 cache, unmasked stream, no context-shift offset,
  * log-probability records off, no guide) and, in a token loop, only for a greedy sampler (temperature 0) with no logit stage on (sampling controls, logit
- * bias, DRY, adaptive truncation), with p + D < 256, inside `steps` and seq_len. Cost (7B, measured: DESIGN.md 3.8): a pass pays where drafts are usually
+ * bias, DRY, adaptive truncation), with p .. p + D inside one bin (ends at 256, 512, 1024, ...), below the bound of q4_set_pass_context
+ * (256 unless raised), inside `steps` and seq_len. Cost (7B, measured: DESIGN.md 3.8): a pass pays where drafts are usually
  * right and loses where they are not. */
 #define Q4_SPEC_MAX_DRAFT 7
 #define Q4_SPEC_MAX_NGRAM 8

@@ -204,7 +204,7 @@ SYMBOLS = [
     "q4_rope_rotation_freqs",
     "q4_sampler_set_dry", "q4_sampler_get_dry", "q4_sampler_set_dry_breakers", "q4_parse_dry", "q4_dry_penalty_table", "q4_dry_penalty",
     "q4_sampler_set_adaptive", "q4_sampler_get_adaptive", "q4_parse_adaptive", "q4_get_adaptive_records", "q4_adaptive_mask",
-    "q4_set_prompt_ingest", "q4_get_prompt_ingest", "q4_prompt_passes",
+    "q4_set_prompt_ingest", "q4_get_prompt_ingest", "q4_prompt_passes", "q4_set_pass_context", "q4_get_pass_context",
     "q4_verify_tokens", "q4_verify_covers", "q4_set_speculative", "q4_get_speculative", "q4_parse_speculative", "q4_set_drafter", "q4_spec_draft",
     "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept",
 ]
@@ -345,6 +345,11 @@ def lib():
     if hasattr(L, "q4_set_prompt_ingest"):         # (older builds under tools/ab.py do not have it)
         L.q4_set_prompt_ingest.argtypes = [i]
         L.q4_set_prompt_ingest.restype = None
+    if hasattr(L, "q4_set_pass_context"):          # (older builds under tools/ab.py do not have it)
+        L.q4_set_pass_context.argtypes = [i]
+        L.q4_set_pass_context.restype = None
+        L.q4_get_pass_context.argtypes = []
+        L.q4_get_pass_context.restype = i
     if hasattr(L, "q4_verify_tokens"):             # (older builds under tools/ab.py do not have it)
         ll = C.c_longlong
         L.q4_verify_tokens.argtypes = [vp, vp, i, vp, C.POINTER(i)]
@@ -734,6 +739,15 @@ def set_prompt_ingest(max_tokens):
 
 def get_prompt_ingest():
     return lib().q4_get_prompt_ingest()
+
+
+def set_pass_context(positions):
+    """q4_set_pass_context: the exclusive upper bound on the positions a prompt pass or a verify pass may touch; 256 (the default) at the least."""
+    lib().q4_set_pass_context(int(positions))
+
+
+def get_pass_context():
+    return lib().q4_get_pass_context()
 
 
 def prompt_passes():

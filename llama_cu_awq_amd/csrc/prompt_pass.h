@@ -6,19 +6,29 @@
 namespace q4 {
 
 constexpr int PROMPT_PASS_MAX = 8;      // tokens per weight read (T)
+constexpr int PASS_CONTEXT_MIN = 256;   // q4_set_pass_context: the default bound, the end of the V-slice bins
 
 // The geometry part of the admission (q4_step.hip decides the rest): Llama-2-7B's shape -- dim 4096, multi-head, 128-wide heads, a hidden size the
 // three-phase FFN launch admits (its down projection is the two-part K split in three k-slots), a rotation table, an fp16 cache, an unmasked stream.
 bool prompt_pass_covers(const Config* p, const Model* m);
-// Positions *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all below bin 256's end, all prompt-only) on the launch stream: K / V rows of every layer, then
-// RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No classifier, no sampler.
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n);
+// Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_step.hip, the admission's one place): for every position the
+// form of the step's attention -> o-proj launch (attention_oproj_form of the bin argument the step would hand to run_network there) is either a V-slice
+// form (5 / 6: form = 5, prompt_attention_kernel) or ONE split-context form for all of them (form = 4 / 2 / 3, chunk = 64 / 128 / 256 positions:
+// prompt_split_attention_kernel + prompt_merge_kernel). nsp: chunks per head the pass launches and lays its records out by; nsp_of_bin: the chunk count
+// the step's launch merges in that bin, or 0 where the step is handed its own size (no graphs): ceil((position + 1) / chunk). False: no pass.
+struct PassAttention { int form, chunk, nsp, nsp_of_bin; };
+bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, PassAttention* out);
+// Positions pos0 = *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all inside one bin and below the bound of q4_set_pass_context, all prompt-only) on the
+// launch stream: K / V rows of every layer, then RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No
+// classifier, no sampler.
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n);
 void prompt_pass_release(const RunState* s);   // q4_free_transformer: the pass's scratch vectors of this model
 // What the verify pass (spec_verify.h) shares with the prompt pass: the model's scratch rows -- x [PROMPT_PASS_MAX][dim] residual streams, pos
 // [PROMPT_PASS_MAX] their positions (allocated on first use) -- and the layer loop over rows 0 .. n - 1 of them: the five launches per layer of
-// run_prompt_pass, which reads the device position and moves nothing. The caller fills x and pos in front and takes the final residual streams from x.
+// run_prompt_pass (six in the split-context bins: the records' merge is a launch of its own), which reads the device position and moves nothing. The
+// caller fills x and pos in front and takes the final residual streams from x.
 struct PassRows { q4_half* x; int* pos; };
 int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out);
-int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n);
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n);
 
 }  // namespace q4

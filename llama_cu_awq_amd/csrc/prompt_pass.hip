@@ -1,6 +1,7 @@
 // prompt_pass.hip -- a prompt pass (prompt_pass.h): n consecutive prompt-only positions run layer by layer, every launch reading its
 // weights ONCE into registers and looping over the n tokens' activations. Five launches per layer -- rmsnorm + q/k/v + RoPE + K/V write, attention (one
-// block per (token, head, V slice)), o-proj + residual, rmsnorm + gate/up + SiLU, down projection + residual -- between an embedding launch and one that
+// block per (token, head, V slice); in the split-context bins, positions >= 256 under q4_set_pass_context: one block per (head, chunk) that loops over the
+// tokens, and a launch that merges each token's records), o-proj + residual, rmsnorm + gate/up + SiLU, down projection + residual -- between an embedding launch and one that
 // leaves RunState::x and the position words as the per-token steps would. No launch waits for another block: every dependency is a launch boundary.
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
@@ -310,6 +311,144 @@ __global__ void __launch_bounds__(LA16_WAVES * 64) prompt_attention_kernel(const
     }
 }
 
+// Attention of a pass whose tokens sit in the split-context bins (positions >= 256 where the step runs forms 4 / 2 / 3 inside attention_oproj_kernel:
+// one block of LA_WAVES waves per (head, chunk of 64 / 128 / 256 positions), a flash-decode record per chunk, the records merged in chunk order). Block
+// (h, sp) requests the chunk's K and V rows ONCE -- split_live's request order and policy, clamped to the last row the pass may read -- and loops over the
+// pass's tokens: each token's record is split_live's middle restated on the same helpers (row_sum<16>, round_h, wave_max / row16_max, expf, the fma chain
+// over u in order, the shuffle folds, wave_sum / row16_sum, split_store_record<false, LA_WAVES>) with size = pos[t] + 1, written to token t's own record
+// area as plain floats. A record depends on the chunk's rows, q, size and the reduction shape -- not on whether it leaves as granules or floats -- so the
+// words are the step's. No tag, no poll, no counter, no atomic: the merge is the next launch (prompt_merge_kernel).
+//  * rows above a token's position are later tokens' rows (or stale ones), possibly non-finite: a masked lane multiplies its zero probability by the V
+//    row the step's clamp would have handed it -- row pos[t], the token's own -- never by the row it holds.
+//  * LDS across tokens: token t + 1 writes red_max in front of its first barrier and outp / red_sum behind it; every reader of token t's outp / red_*
+//    (split_store_record included) has issued its reads before it arrives at that barrier, so one outp area serves all tokens.
+struct PassSplitArgs {
+    float* records;              // [ntok][n_heads][nsp][head_size + ATT_REC_PAD]
+    const q4_half* q;            // [ntok][dim]
+    const q4_half* key_cache;    // already offset to the layer
+    const q4_half* value_cache;
+    const int* pos;              // [ntok], ascending
+    int ntok, dim, kv_dim, nsp;
+    size_t tok_stride;           // floats between two tokens' record areas
+    float alpha;
+};
+template <int U>
+__global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(const PassSplitArgs a) {
+    constexpr int LPR = 16, NW = LA_WAVES, R = 64 / LPR, stride = NW * R, CHUNK = stride * U, HS = LPR * 8;
+    __shared__ __attribute__((aligned(16))) float lds[32 + NW * HS];
+    float* red_max = lds;
+    float* red_sum = lds + 16;
+    float* outp = lds + 32;                                  // [NW][HS]
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    const int wave = tid >> 6;
+    const int row = lane / LPR, sub = lane % LPR;
+    const int h = blockIdx.x, sp = blockIdx.y;
+    const int ntok = a.ntok, kv_dim = a.kv_dim;
+    const int rec = HS + ATT_REC_PAD;
+    const int t_base = sp * CHUNK;
+    const int size_last = __builtin_amdgcn_readfirstlane(a.pos[ntok - 1]) + 1;      // rows the pass may read: [0, size_last)
+    if (NW < 16 && tid >= NW && tid < 16) { red_max[tid] = -INFINITY; red_sum[tid] = 0.f; }   // the reductions read 16 entries
+    auto neutral = [&](int t) {      // a chunk wholly above pos[t]: attention_split_body's plain neutral words (m = -inf, l = 0)
+        const f32x4 r4 = {-INFINITY, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(a.records + (size_t)t * a.tok_stride + ((size_t)h * a.nsp + sp) * rec + HS) = r4;
+    };
+    if (t_base >= size_last) {
+        if ((int)tid < ntok) neutral((int)tid);
+        return;
+    }
+    const q4_half* kh = a.key_cache + (size_t)h * HS + sub * 8;
+    const q4_half* vh = a.value_cache + (size_t)h * HS + sub * 8;
+    u32x4 kv[U], vv[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int r = t_base + wave * R + row + u * stride;
+        const int rc = r < size_last ? r : size_last - 1;
+        kv[u] = ld_nt(reinterpret_cast<const u32x4*>(kh + (size_t)rc * kv_dim));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int r = t_base + wave * R + row + u * stride;
+        const int rc = r < size_last ? r : size_last - 1;
+        vv[u] = ld_nt(reinterpret_cast<const u32x4*>(vh + (size_t)rc * kv_dim));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    SplitArgs sa = {};
+    sa.head_size = HS;
+    for (int t = 0; t < ntok; t++) {
+        const int size = __builtin_amdgcn_readfirstlane(a.pos[t]) + 1;
+        if (t_base >= size) {                                // (block-uniform: no barrier is skipped by part of the block)
+            if (tid == 0) neutral(t);
+            continue;
+        }
+        const u32x4 qv = *reinterpret_cast<const u32x4*>(a.q + (size_t)t * a.dim + (size_t)h * HS + sub * 8);
+        const u32x4 vown = *reinterpret_cast<const u32x4*>(vh + (size_t)(size - 1) * kv_dim);      // what split_live's clamp gives a masked lane
+        float sc[U];
+        float wmax = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int r = t_base + wave * R + row + u * stride;
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; e++) s = __builtin_amdgcn_fdot2(as_h2(kv[u][e]), as_h2(qv[e]), s, false);
+            s = row_sum<LPR>(s);
+            s = round_h(s * a.alpha);
+            sc[u] = r < size ? s : -INFINITY;
+            wmax = fmaxf(wmax, sc[u]);
+        }
+        wmax = wave_max(wmax);
+        if (lane == 0) red_max[wave] = wmax;
+        __syncthreads();
+        const float m = row16_max(red_max[lane & 15]);
+        float acc[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) acc[e] = 0.f;
+        float lsum = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int r = t_base + wave * R + row + u * stride;
+            const float p = expf(sc[u] - m);                 // 0 for masked positions (sc = -inf)
+            if (sub == 0) lsum += p;
+            const u32x4 vsel = r < size ? vv[u] : vown;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const h2 v2 = as_h2(vsel[e]);
+                acc[2 * e] = __builtin_fmaf((float)v2.x, p, acc[2 * e]);
+                acc[2 * e + 1] = __builtin_fmaf((float)v2.y, p, acc[2 * e + 1]);
+            }
+        }
+        lsum = wave_sum(lsum);
+        if (lane == 0) red_sum[wave] = lsum;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            float v = acc[e];
+            v += __shfl_xor(v, 32);
+            v += __shfl_xor(v, 16);
+            acc[e] = v;
+        }
+        if (lane < LPR) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) outp[wave * HS + sub * 8 + e] = acc[e];
+        }
+        __syncthreads();
+        const float l = row16_sum(red_sum[lane & 15]);
+        sa.partials = a.records + (size_t)t * a.tok_stride;
+        split_store_record<false, NW>(sa, Handoff{}, outp, m, l, h, sp, a.nsp);
+    }
+}
+
+// The merge of a split pass: one block per (head, token) runs the step's merge arithmetic (combine_partials, chunk order) over the token's records and
+// writes xb[t]. nsp_of_bin: the chunk count of the step's launch for the bin (graph bins), or 0: ceil((pos[t] + 1) / chunk), the count of a step that
+// is handed its own size as the bin (no graphs) -- the chunks between the two are neutral either way.
+__global__ void __launch_bounds__(128) prompt_merge_kernel(q4_half* xb, const float* records, const int* pos, int dim, int head_size, int nsp, size_t tok_stride,
+                                                           int nsp_of_bin, int chunk) {
+    const int h = blockIdx.x, t = blockIdx.y;
+    const int n_merge = nsp_of_bin ? nsp_of_bin : (pos[t] + chunk) / chunk;
+    const float* base = records + (size_t)t * tok_stride + (size_t)h * nsp * (head_size + ATT_REC_PAD);
+    for (int n = threadIdx.x; n < head_size; n += blockDim.x)
+        combine_partials<false>(xb + (size_t)t * dim + (size_t)h * head_size, base, head_size, n_merge, n);
+}
+
 // the n tokens' embedding rows, and the positions of the pass for its attention blocks
 __global__ void prompt_embed_kernel(q4_half* xs, const q4_half* table, int dim, const int* tokens, const int* pPos, int* pos_arr) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
@@ -332,13 +471,14 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-struct PassBuf { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; u32x2v* sink; size_t sink_stride; };
+struct PassBuf { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; u32x2v* sink; size_t sink_stride; float* records; size_t record_floats; };
 static std::map<const RunState*, PassBuf>& pass_bufs() { static std::map<const RunState*, PassBuf> b; return b; }
 
 void prompt_pass_release(const RunState* s) {
     auto it = pass_bufs().find(s);
     if (it == pass_bufs().end()) return;
     if (it->second.slab) (void)hipFree(it->second.slab);
+    if (it->second.records) (void)hipFree(it->second.records);
     pass_bufs().erase(it);
 }
 
@@ -363,6 +503,23 @@ static int pass_buf_of(const RunState* s, int dim, int hidden, PassBuf** out) {
         it = pass_bufs().insert({s, b}).first;
     }
     *out = &it->second;
+    return Q4_OK;
+}
+
+// The split passes' flash-decode records: the pass's own buffer (never RunState::att, whose words are validated by tag), allocated on the first split
+// pass of the model for the longest context it can meet -- PROMPT_PASS_MAX tokens x heads x chunks x (head_size + ATT_REC_PAD) floats.
+static int pass_records_of(PassBuf* b, size_t floats) {
+    if (b->record_floats >= floats) return Q4_OK;
+    if (b->records) {
+        Q4_HIP(hipStreamSynchronize(g_stream));              // a pass that reads the old area may still be in flight
+        (void)hipFree(b->records);
+        b->records = nullptr;
+        b->record_floats = 0;
+    }
+    void* r = nullptr;
+    if (hipMalloc(&r, floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+    b->records = (float*)r;
+    b->record_floats = floats;
     return Q4_OK;
 }
 
@@ -393,12 +550,24 @@ int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out) {
 }
 
 // The layer loop of a pass, shared by the prompt pass below and the verify pass (spec_verify.hip): rows 0 .. n - 1 of the model's scratch rows hold the
-// positions' residual streams going in (and pos[t] their positions), and their final residual streams coming out.
-int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
+// positions' residual streams going in (and pos[t] their positions), and their final residual streams coming out. pos0: the position of row 0 as the
+// host knows it (the device position when the pass runs) -- which attention launch the layers take is decided from it (pass_attention_plan), the kernels
+// read the positions from pos[].
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
     PassBuf* b = nullptr;
     Q4_TRY(pass_buf_of(s, dim, hidden, &b));
+    PassAttention plan = {};
+    if (!pass_attention_plan(p, s, pos0, n, &plan)) return Q4_ERR_ARG;
+    const bool split = att_is_split(plan.form);
+    const int rec = head_size + ATT_REC_PAD;
+    const size_t tok_stride = (size_t)p->n_heads * plan.nsp * rec;
+    if (split) {
+        if (head_size != 128 || pos0 + n > p->seq_len) return Q4_ERR_ARG;
+        const int most = divUp(p->seq_len, 64) > plan.nsp ? divUp(p->seq_len, 64) : plan.nsp;      // the smallest chunk's count over the whole context
+        Q4_TRY(pass_records_of(b, (size_t)PROMPT_PASS_MAX * p->n_heads * most * rec));
+    }
     constexpr int TB = PP_WAVES * 64;
     constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
     static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024, "no LDS opt-in");
@@ -417,7 +586,17 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         }
-        {   // attention
+        if (split) {   // attention in the split-context bins: one block per (head, chunk) loops over the tokens, then the step's merge per (head, token)
+            const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, dim, plan.nsp, tok_stride, alpha};
+            const dim3 grid((unsigned)p->n_heads, (unsigned)plan.nsp);
+            if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a);
+            else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a);
+            else Q4_LAUNCH(prompt_split_attention_kernel<8>, grid, dim3(LA_WAVES * 64), 0, a);
+            Q4_LAUNCH_CHECK();
+            Q4_LAUNCH(prompt_merge_kernel, dim3((unsigned)p->n_heads, (unsigned)n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
+                      plan.nsp, tok_stride, plan.nsp_of_bin, plan.chunk);
+            Q4_LAUNCH_CHECK();
+        } else {   // attention below bin 512: the V-slice units
             const AttArgs a = {b->xb, b->q, s->key_cache + loff, s->value_cache + loff, head_size, 1, dim, b->pos, alpha, 256, nullptr};
             Q4_LAUNCH(prompt_attention_kernel, dim3((unsigned)n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, b->sink, (unsigned)b->sink_stride,
                       (unsigned)p->n_heads, natt, dim);
@@ -452,7 +631,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     return Q4_OK;
 }
 
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int n) {
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim;
     PassBuf* b = nullptr;
@@ -460,7 +639,7 @@ int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, c
     Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
               (const int*)s->pos, b->pos);
     Q4_LAUNCH_CHECK();
-    Q4_TRY(prompt_pass_layers(p, s, w, m, n));
+    Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
     Q4_LAUNCH(prompt_finish_kernel, dim3(1), dim3(1024), 0, s->x, (const q4_half*)(b->x + (size_t)(n - 1) * dim), dim, &(s->shared_data->pos), s->pos, n);
     Q4_LAUNCH_CHECK();
     return Q4_OK;

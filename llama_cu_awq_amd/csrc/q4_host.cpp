@@ -578,6 +578,17 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and how far prompt and verify passes go (q4_set_pass_context): Q4_PASS_CONTEXT=2048; values up to 256 are the default
+    const char* pass_context = getenv("Q4_PASS_CONTEXT");
+    if (pass_context && *pass_context) {
+        char* rest = nullptr;
+        const long v = pass_context[0] >= '0' && pass_context[0] <= '9' ? strtol(pass_context, &rest, 10) : -1;     // (no sign, no leading blank)
+        if (v < 0 || !rest || *rest || v > Q4_MAX_SEQ_LEN) {
+            fprintf(stderr, "Q4_PASS_CONTEXT: cannot use '%s' (one integer, 0 .. %d: the positions below which prompt and verify passes run; e.g. 2048)\n", pass_context, Q4_MAX_SEQ_LEN);
+            exit(EXIT_FAILURE);
+        }
+        q4_set_pass_context((int)v);
+    }
     int steps = a.steps;
     if (steps <= 0 || (!shifting && steps > transformer.config.seq_len)) steps = transformer.config.seq_len;   // :690
     if (shifting && steps > Q4_MAX_SEQ_LEN - 1) steps = Q4_MAX_SEQ_LEN - 1;

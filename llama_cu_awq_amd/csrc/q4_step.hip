@@ -126,12 +126,63 @@ static bool step_screens(const Model* m, bool may_screen, int gen_token, bool gr
            !any_stage_on(sampler, m) && cls_screen_shape(m->screen.n, m->screen.d);
 }
 
+// The graph bin of a step whose sequence length is seq_len (llama2_q4.cu:355-360): the index of its graph set and the bin's size
+static int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out) {
+    int graphIndex;
+    int seq_len_bin = 128;
+    for (graphIndex = 0; graphIndex < Q4_MAX_GRAPHS - 1; seq_len_bin *= 2, graphIndex++)
+        if (seq_len <= seq_len_bin) break;                                         // :356-359
+    if ((seq_len > seq_len_bin) || (graphIndex == Q4_MAX_GRAPHS - 1)) seq_len_bin = p->seq_len;   // :360
+    *seq_len_bin_out = seq_len_bin;
+    return graphIndex;
+}
+
+// ---- what a pass (prompt pass, verify pass) may touch: the admission's position rules, in one place ----
+// q4_set_pass_context: the exclusive upper bound on the positions of a pass; in force for a model: min(value, seq_len). 256 (the default, and the
+// least) keeps passes to the V-slice bins.
+static int g_pass_context = PASS_CONTEXT_MIN;
+static int pass_bound(const Config* p) { return g_pass_context < p->seq_len ? g_pass_context : p->seq_len; }
+// The seq_len_bin argument the step at position `pos` hands to run_network (run_transformer_steps_screenable): the graph bin of pos + 1 where steps run
+// by bin (graphs, eager bins), pos + 1 itself without graphs.
+static int step_bin_arg(const Config* p, int pos) {
+    int bin;
+    (void)graph_bin(pos + 1, p, &bin);
+    return g_use_graphs ? bin : pos + 1;
+}
+// Where the bin of `pos` ends: positions [0, 256) are one stretch for a pass (the V-slice forms of bins 128 and 256), then [256, 512), [512, 1024), ...
+// No pass reaches across an end: above 255 the step's attention form or its chunk size may change there.
+static int pass_bin_end(int pos) {
+    int end = 256;
+    while (end <= pos && end < Q4_MAX_SEQ_LEN) end *= 2;
+    return end;
+}
+bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, PassAttention* out) {
+    if (pos < 0 || n < 1 || pos + n > p->seq_len || p->n_heads < 1) return false;
+    const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
+    int kind = -1, arg = -1, form = -1;
+    for (int i = 0; i < n; i++) {
+        const int arg_i = step_bin_arg(p, pos + i);
+        if (arg_i != arg) form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, arg_i, s->att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
+        const int kind_i = form == 5 || form == 6 ? 5 : form >= 2 && form <= 4 ? form : -1;   // V-slice forms mix (prompt_attention_kernel picks per token); a split form stands alone
+        if (kind_i < 0 || (i > 0 && kind_i != kind)) return false;
+        if (kind_i != 5 && g_use_graphs && i > 0 && arg_i != arg) return false;               // split tokens of one pass share the step's launch shape
+        kind = kind_i;
+        arg = arg_i;
+    }
+    out->form = kind;
+    out->chunk = kind == 4 ? 64 : kind == 2 ? 128 : kind == 3 ? 256 : 0;
+    out->nsp = kind == 5 ? 0 : divUp(arg, out->chunk);       // (arg: the last position's -- without graphs its own size, the largest of the pass)
+    out->nsp_of_bin = g_use_graphs ? out->nsp : 0;
+    return true;
+}
+
 // A prompt pass (prompt_pass.h) in place of the per-token prompt steps from `pos`: how many positions it takes, 0 for none. Only a token
 // loop asks (the per-step entry points, scoring and perplexity keep their steps), and only where the pass computes what the steps would and nothing reads
-// what it leaves out: the switch on; the fusion level in force >= 3 with the V-slice attention form (5 / 6) for every bin the pass touches -- so never the
-// level-1 redo after a time-out --; the geometry prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps` and
-// below 256; no log-probability records (they describe prompt steps' logits); neither the guide nor the adaptive truncation on (their state by position is
-// put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.)
+// what it leaves out: the switch on; the fusion level in force >= 3 with an attention form the pass reproduces at every position it touches
+// (pass_attention_plan: the V-slice forms 5 / 6, or one split-context form 4 / 2 / 3) -- so never the level-1 redo after a time-out --; the geometry
+// prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps`, below the bound of q4_set_pass_context and inside
+// the bin of `pos`; no log-probability records (they describe prompt steps' logits); neither the guide nor the adaptive truncation on (their state by
+// position is put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.)
 static int g_prompt_ingest = PROMPT_PASS_MAX;
 static int g_prompt_passes = 0;
 static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int num_prompt_tokens, int steps, int off) {
@@ -140,21 +191,18 @@ static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sample
     int n = num_prompt_tokens - 1 - pos;
     if (n > g_prompt_ingest) n = g_prompt_ingest;
     if (n > steps - pos) n = steps - pos;
-    if (n > 256 - pos) n = 256 - pos;
-    if (n > p->seq_len - pos) n = p->seq_len - pos;
+    if (n > pass_bin_end(pos) - pos) n = pass_bin_end(pos) - pos;
+    if (n > pass_bound(p) - pos) n = pass_bound(p) - pos;
     if (n < 2 || guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m) || !prompt_pass_covers(p, m)) return 0;
-    const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
-    for (int bin = pos + 1 <= 128 ? 128 : 256; bin <= (pos + n <= 128 ? 128 : 256); bin *= 2) {
-        const int form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, bin, t->state.att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
-        if (form != 5 && form != 6) return 0;
-    }
-    return n;
+    PassAttention plan;
+    return pass_attention_plan(p, &t->state, pos, n, &plan) ? n : 0;
 }
 
 
 // A verify pass (spec_verify.h) at position `pos` with n_draft drafts, positions pos .. pos + n_draft: what a prompt pass requires -- the
-// fusion level in force >= 3 with the V-slice attention form (5 / 6) in every bin touched, prompt_pass_covers' geometry (fp16 cache, unmasked stream), no
-// log-probability records, no guide, no context-shift offset, every position below 256 and inside seq_len -- plus a classifier shape the pass's launch
+// fusion level in force >= 3 with an attention form the pass reproduces at every position (pass_attention_plan), prompt_pass_covers' geometry (fp16 cache,
+// unmasked stream), no log-probability records, no guide, no context-shift offset, every position inside the bin of `pos`, below the bound of
+// q4_set_pass_context and inside seq_len -- plus a classifier shape the pass's launch
 // takes. A token loop adds (sampler non-null): temperature 0, no logit stage on, every position inside `steps`. With all of that off a greedy generating
 // step leaves, by position: its K / V rows, ring[pos + 1], the two position words; and, not by position: RunState::logits, RunState::x (un-normalised
 // behind the strips classifier; what the pass writes), the scratch vectors xb / hb / q / att (rewritten by every step before it reads them), the hand-off
@@ -163,15 +211,11 @@ static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sample
 static bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off) {
     if (g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0 || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
     const Config* p = &t->config;
-    if (pos + n_draft >= 256 || pos + n_draft >= p->seq_len || pos + n_draft >= steps) return false;
+    if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps) return false;
     if (sampler && (sampler->temperature != 0.0f || any_stage_on(sampler, m))) return false;
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return false;
-    const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
-    for (int bin = pos + 1 <= 128 ? 128 : 256; bin <= (pos + n_draft + 1 <= 128 ? 128 : 256); bin *= 2) {
-        const int form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, bin, t->state.att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
-        if (form != 5 && form != 6) return false;
-    }
-    return true;
+    PassAttention plan;
+    return pass_attention_plan(p, &t->state, pos, n_draft + 1, &plan);
 }
 // The drafter's answer for ring[0 .. n_tokens), at most max_draft ids, cut in front of the first id outside the vocabulary
 static int ask_drafter(const Model* m, const int* ring, int n_tokens, int max_draft, int vocab, int* draft) {
@@ -213,6 +257,11 @@ int q4_get_greedy_screen(void) { return g_greedy_screen; }
 void q4_set_prompt_ingest(int max_tokens) { g_prompt_ingest = max_tokens < 2 ? 0 : max_tokens > PROMPT_PASS_MAX ? PROMPT_PASS_MAX : max_tokens; }
 int q4_get_prompt_ingest(void) { return g_prompt_ingest; }
 int q4_prompt_passes(void) { return g_prompt_passes; }
+// The exclusive upper bound on the positions a prompt pass or a verify pass may touch (process-wide; min(value, seq_len) holds for a model). 256, the
+// default and the least value, keeps the passes to the V-slice bins; above it they follow the step into the split-context bins. No captured graph
+// contains a pass: nothing to drop.
+void q4_set_pass_context(int positions) { g_pass_context = positions > PASS_CONTEXT_MIN ? positions : PASS_CONTEXT_MIN; }
+int q4_get_pass_context(void) { return g_pass_context; }
 
 // ---- speculative greedy decoding: the settings, the built-in drafter, the primitive (spec_verify.h) ----
 int q4_spec_draft(const int* tokens, int n_tokens, int max_draft, int ngram_max, int ngram_min, int* draft_out) {
@@ -295,7 +344,7 @@ int q4_verify_tokens(Transformer* t, const int* draft, int n_draft, int* out_tok
     Q4_HIP(hipStreamSynchronize(g_stream));
     const int pos = t->state.shared_data->pos;
     if (m->rows_suspect || !verify_covers(t, m, nullptr, pos, n_draft, t->config.seq_len, 0)) return Q4_NOT_ADMITTED;
-    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, draft, n_draft));
+    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, pos, draft, n_draft));
     Q4_HIP(hipStreamSynchronize(g_stream));
     const int acc = t->state.shared_data->pos - (pos + 1);
     if (acc < 0 || acc > n_draft) return Q4_ERR_HIP;
@@ -468,16 +517,6 @@ int q4_run_transformer(int gen_token, const Config* p, RunState* s, const Transf
 // The same step with the position supplied by the caller instead of read back from SharedData::pos: the device keeps
 // its own position (`s->pos`) and reads its input token from the ring, so step pos+1 can be queued while step pos is
 // still running (generate() below); only the graph bin depends on the host's idea of the position.
-static int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out) {
-    int graphIndex;
-    int seq_len_bin = 128;
-    for (graphIndex = 0; graphIndex < Q4_MAX_GRAPHS - 1; seq_len_bin *= 2, graphIndex++)
-        if (seq_len <= seq_len_bin) break;                                         // :356-359
-    if ((seq_len > seq_len_bin) || (graphIndex == Q4_MAX_GRAPHS - 1)) seq_len_bin = p->seq_len;   // :360
-    *seq_len_bin_out = seq_len_bin;
-    return graphIndex;
-}
-
 int q4_run_transformer_at(int pos, int gen_token, const Config* p, RunState* s, const TransformerWeights* w, int copyLogits,
                           Sampler* pSampler) {
     return q4_run_transformer_steps(pos, 1, gen_token, p, s, w, copyLogits, pSampler);
@@ -851,12 +890,12 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                 group_start = pos;
                 group_rng = sampler->rng_state;
                 if (nd) {      // positions pos .. pos + m run, m the accepted drafts: known once the pass has published its position
-                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, draft, nd));
+                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, pos, draft, nd));
                     verify_pos = pos;
                     verify_drafts = nd;
                 } else if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them
                     for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
-                    Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, np));
+                    Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, pos - off, np));
                     g_prompt_passes++;
                 } else {
                     Q4_TRY(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off)));

@@ -28,8 +28,9 @@ int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, c
 // x: rows of dim halves. report (device, 9 ints, may be null): the rows' greedy tokens and, in [8], m.
 int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
                          int* ring, volatile int* pPos, int* pPosGpu, int* report);
-// The whole pass at the device position; the caller (q4_step.hip's verify_covers) has admitted it. On the launch stream; nothing is waited for.
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, const int* draft, int n_draft);
+// The whole pass at the device position, which the caller knows to be pos0 (q4_step.hip's verify_covers has admitted it there). On the launch stream;
+// nothing is waited for.
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft);
 void verify_release(const RunState* s);   // q4_free_transformer: the pass's logits rows of this model
 
 }  // namespace q4

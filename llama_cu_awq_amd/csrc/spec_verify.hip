@@ -196,7 +196,7 @@ void verify_release(const RunState* s) {
     logit_rows().erase(it);
 }
 
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, const int* draft, int n_draft) {
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft) {
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size) || !draft || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
     VerifyDrafts d = {};
     d.n = n_draft;
@@ -216,7 +216,7 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, c
     Q4_LAUNCH(verify_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, rows.x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens, d,
               (const int*)s->pos, rows.pos);
     Q4_LAUNCH_CHECK();
-    Q4_TRY(prompt_pass_layers(p, s, w, m, n));
+    Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
     Q4_TRY(launch_verify_cls(it->second, rows.x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
     return launch_verify_accept(it->second, p->vocab_size, p->vocab_size, d, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens, &(s->shared_data->pos),
                                 s->pos, nullptr);

@@ -71,6 +71,9 @@ GEOMETRIES = {
     "ffn_pair_wide": (4096, 11264, 2, 32, 32, 512, 300, 10000.0),
     # a verify pass (csrc/spec_verify.h) whose classifier has the strips form with a ragged row split (16600 rows over 256 CUs): Llama-2-7B's layer, once
     "spec_cls_ragged": (4096, 11008, 1, 32, 32, 16600, 300, 10000.0),
+    # prompt and verify passes in the split-context bins (q4_set_pass_context): Llama-2-7B's layer twice with a context of 2304 -- positions 2048 .. 2303
+    # run in graph bin 4096 (sixteen 256-position chunks: the records' merge takes its two-round branch); the records scratch holds 18 chunks per head
+    "pass_long": (4096, 11008, 2, 32, 32, 512, 2304, 10000.0),
 }
 
 
