@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import hostile_models as hm
+import hostile_ref
 from llama_cu_awq_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -65,24 +66,13 @@ def hostile(tmp_path_factory):
     return out
 
 
-_REF = {}
-
-
 @pytest.fixture(scope="module")
 def restatement(orc, hostile):
-    """(logits [T, vocab] f16, K rows, V rows of positions 0 and T-1 per layer, f64 logits of the first positions) per model, computed once."""
+    """(logits [T, vocab] f16, K rows, V rows of positions 0 and T-1 per layer, f64 logits of the first positions) per model, computed once
+    (tests/hostile_ref.py keeps it, for tests/test_pass_hostile_gpu.py too)."""
     def get(g, t):
-        if (g, t) not in _REF:
-            m = orc.Model(hostile[g, t])
-            logits = np.stack([m.forward(tok, pos) for pos, tok in enumerate(SEQ)])
-            k, v = m.kv()
-            kv = (k[:, [0, len(SEQ) - 1]].copy(), v[:, [0, len(SEQ) - 1]].copy())
-            m.close()
-            m = orc.Model(hostile[g, t])
-            f64 = np.stack([m.forward_f64(tok, pos, cap=F64_POSITIONS) for pos, tok in enumerate(SEQ[:F64_POSITIONS])])
-            m.close()
-            _REF[g, t] = (logits, kv, f64)
-        return _REF[g, t]
+        logits, (k, v), f64 = hostile_ref.restatement(orc, hostile[g, t], (g, t, SEED), SEQ, F64_POSITIONS)
+        return logits, (k[:, [0, len(SEQ) - 1]], v[:, [0, len(SEQ) - 1]]), f64
     return get
 
 

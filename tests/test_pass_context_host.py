@@ -97,6 +97,12 @@ def test_prompt_passes_by_hand():
     assert ref.prompt_passes(600, 300, S, S)[-1] == (296, 4)
     # smaller passes
     assert len(ref.prompt_passes(17, 23, S, S, ingest=3)) == 5
+    # ... above 256: 1040 prompt tokens in passes of five. [0, 256) and [256, 512): 51 passes each, the position in front of the end a step; [512, 1024):
+    # 102 passes and one of two (1022, 1023); 1024 .. 1038: three. Passes of five from 256 and from 512 straddle the chunk ends 320 and 640
+    p = ref.prompt_passes(1040, 1046, S, S, ingest=5)
+    assert len(p) == 51 + 51 + 103 + 3 and (250, 5) in p and (256, 5) in p and (316, 5) in p and (506, 5) in p and (637, 5) in p
+    assert (1022, 2) in p and p[-1] == (1034, 5) and [x for x in p if x[1] != 5] == [(1022, 2)]
+    assert len(ref.prompt_passes(1040, 1046, S, S)) == 32 + 32 + 64 + 2 and ref.prompt_passes(1040, 1046, S, S)[-1] == (1032, 7)
 
 
 def test_covers_by_hand():
