@@ -398,8 +398,8 @@ int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const 
  * position p + m + 1, RunState::logits and RunState::x of step p + m, the K / V rows. K / V rows p + m + 1 .. p + D hold rows computed from rejected drafts:
  * they lie at or above the position (q4_common_prefix, q4_resume_sequence and snapshots never trust such rows) and are written again by whatever runs there next.
  * A pass is admitted where a prompt pass is (q4_set_prompt_ingest above: geometry, fusion level >= 3, fp16 cache, unmasked stream, no context-shift offset,
- * log-probability records off, no guide) and, in a token loop, only for a greedy sampler (temperature 0) with no logit stage on (sampling controls, logit
- * bias, DRY, adaptive truncation), with p .. p + D inside one bin (ends at 256, 512, 1024, ...), below the bound of q4_set_pass_context
+ * log-probability records off, no guide) and, in a token loop, only for a greedy sampler (temperature 0; q4_set_speculative_sampled below adds the
+ * temperature / top-p sampler) with no logit stage on (sampling controls, logit bias, DRY, adaptive truncation), with p .. p + D inside one bin (ends at 256, 512, 1024, ...), below the bound of q4_set_pass_context
  * (256 unless raised), inside `steps` and seq_len. Cost (7B, measured: DESIGN.md 3.8): a pass pays where drafts are usually
  * right and loses where they are not. */
 #define Q4_SPEC_MAX_DRAFT 7
@@ -441,6 +441,33 @@ int q4_spec_stats(const Transformer* t, long long* passes, long long* drafted, l
 int q4_verify_classifier(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n_rows);
 int q4_verify_accept(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
                      int* ring, int* pos_host, int* pos_dev, int* report);
+
+/* ---- verify passes under the temperature / top-p sampler ("Under the sampler"). Off by default; a switch of its own. ----
+ * A sampled step is a function of its logits and one coin, and the coin is a function of (seed, position). With the switch on, a pass under a sampler with
+ * a finite temperature above 0 samples EVERY row with its own position's coin -- the step's two sampler launches, one grid slice per row, each row
+ * normalised in place -- and accepts the leading drafts that equal the sampled tokens. Lossless: tokens, K / V rows, RunState::logits (row m's fp16
+ * probabilities, what the sampled step leaves there) and the Sampler's random state are those of the run without it, byte for byte. On top of the greedy
+ * admission: no logit stage on, a vocabulary of at most 32768 entries (a multiple of 8); a negative temperature, a larger vocabulary or the switch off
+ * run steps. A drafter's tokens are point guesses: the chance that a draft is accepted is the target's probability of it. Rejection sampling against a
+ * sampling draft model (min(1, p / q)) is not this and not here. */
+int q4_set_speculative_sampled(Transformer* t, int on);
+int q4_get_speculative_sampled(const Transformer* t);                  /* 1: on; 0: off, or not a Transformer the library built */
+/* The CLI's Q4_SPECULATIVE_SAMPLED (a variable of its own beside Q4_SPECULATIVE): "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
+int q4_parse_speculative_sampled(const char* text, int* on);
+/* q4_verify_tokens under `sampler`: same contract (Q4_ERR_ARG before any launch, a null sampler included; Q4_NOT_ADMITTED when nothing ran, the switch off
+ * or temperature 0 included). The sampler's stream must stand at the current position's coin; the call consumes *n_accepted + 1 coins of it, one per
+ * position that ran, as that many steps would. */
+int q4_verify_tokens_sampled(Transformer* t, Sampler* sampler, const int* draft, int n_draft, int* out_tokens, int* n_accepted);
+int q4_verify_covers_sampled(const Transformer* t, const Sampler* sampler, int pos, int n_draft);   /* 1: q4_verify_tokens_sampled would run there; else 0 */
+/* Op-level forms, for tests and tools, on the q4 stream.
+ * q4_verify_sample_rows: rows r < n_rows (1 .. 8) of logits (device, `ld` halves apart, ld a multiple of 8 and >= the sampler's vocabulary) are normalised IN
+ * PLACE and sampled with coins_host[r] (host array) under the sampler's temperature / top-p: tokens_dev[r] (device) and the row's probabilities are what
+ * q4_sample leaves for that row alone with that coin. Nothing else is written; halves behind a row's vocabulary are neither read nor written.
+ * Q4_ERR_UNSUPPORTED_SIZE: a vocabulary above 32768 or no multiple of 8, a temperature that is not finite and above 0.
+ * q4_verify_accept_tokens: q4_verify_accept with the rows' tokens given in tokens_dev (device, n_draft + 1 ints) instead of each row's argmax. */
+int q4_verify_sample_rows(Sampler* sampler, q4_half* logits, int ld, int n_rows, const float* coins_host, int* tokens_dev);
+int q4_verify_accept_tokens(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const int* tokens_dev, const q4_half* x, int dim,
+                            q4_half* logits_out, q4_half* x_out, int* ring, int* pos_host, int* pos_dev, int* report);
 
 /* build_sampler / destroy_sampler sampler.h:15-29; random_u32 / random_f32 :31-40; sample :43-82 */
 int build_sampler(Sampler* sampler, int vocab_size, float temperature, float topp, unsigned long long rng_seed);

@@ -206,7 +206,8 @@ SYMBOLS = [
     "q4_sampler_set_adaptive", "q4_sampler_get_adaptive", "q4_parse_adaptive", "q4_get_adaptive_records", "q4_adaptive_mask",
     "q4_set_prompt_ingest", "q4_get_prompt_ingest", "q4_prompt_passes", "q4_set_pass_context", "q4_get_pass_context",
     "q4_verify_tokens", "q4_verify_covers", "q4_set_speculative", "q4_get_speculative", "q4_parse_speculative", "q4_set_drafter", "q4_spec_draft",
-    "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept",
+    "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept", "q4_set_speculative_sampled", "q4_get_speculative_sampled", "q4_verify_tokens_sampled",
+    "q4_verify_covers_sampled", "q4_verify_sample_rows", "q4_verify_accept_tokens", "q4_parse_speculative_sampled",
 ]
 
 _lib = None
@@ -362,6 +363,14 @@ def lib():
         L.q4_spec_stats.argtypes = [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]
         L.q4_verify_classifier.argtypes = [vp, vp, vp, vp, i, i, i]
         L.q4_verify_accept.argtypes = [vp, i, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "q4_verify_tokens_sampled"):     # (older builds under tools/ab.py do not have it)
+        L.q4_set_speculative_sampled.argtypes = [vp, i]
+        L.q4_get_speculative_sampled.argtypes = [vp]
+        L.q4_parse_speculative_sampled.argtypes = [C.c_char_p, C.POINTER(i)]
+        L.q4_verify_tokens_sampled.argtypes = [vp, vp, vp, i, vp, C.POINTER(i)]
+        L.q4_verify_covers_sampled.argtypes = [vp, vp, i, i]
+        L.q4_verify_sample_rows.argtypes = [vp, vp, i, i, vp, vp]
+        L.q4_verify_accept_tokens.argtypes = [vp, i, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "q4_sampler_set_controls"):      # (older builds under tools/ab.py do not have it)
         L.q4_sampler_set_controls.argtypes = [vp, C.POINTER(SamplingControls)]
         L.q4_sampler_get_controls.argtypes = [vp, C.POINTER(SamplingControls)]
@@ -717,6 +726,19 @@ def verify_accept(logits, ld, size, draft, x, dim, logits_out, x_out, ring, pos_
                                  ring.ptr, pos_host.ptr, pos_dev.ptr, report.ptr if report else None))
 
 
+def verify_accept_tokens(logits, ld, size, draft, tokens, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report=None):
+    """q4_verify_accept_tokens over DevBufs (draft: host ids; tokens: the rows' tokens, device): the accept launch of a pass under the sampler."""
+    d = np.ascontiguousarray(draft, dtype=np.int32)
+    check(lib().q4_verify_accept_tokens(logits.ptr, ld, size, d.ctypes.data, d.shape[0], tokens.ptr if tokens else None, x.ptr if x else None, dim,
+                                        logits_out.ptr, x_out.ptr if x_out else None, ring.ptr, pos_host.ptr, pos_dev.ptr, report.ptr if report else None))
+
+
+def verify_sample_rows(sampler, logits, ld, n_rows, coins, tokens):
+    """q4_verify_sample_rows over DevBufs (sampler: a q4_sampler_new handle; coins: host floats): rows normalised in place, tokens[r] sampled with coins[r]."""
+    c = np.ascontiguousarray(coins, dtype=np.float32)
+    check(lib().q4_verify_sample_rows(sampler, logits.ptr, ld, n_rows, c.ctypes.data, tokens.ptr))
+
+
 def greedy_screen_op(x, w, n, d, rms_w=None):
     """q4_greedy_screen_op over DevBufs: (token, A [d] float32, B [d] float32, refined logits [d] float16, candidate rows)."""
     tok, cand = C.c_int(), C.c_int()
@@ -1031,10 +1053,31 @@ class Transformer:
         check(lib().q4_screen_candidates(self.h, C.byref(last), C.byref(mx), C.byref(total), C.byref(steps)))
         return last.value, mx.value, total.value, steps.value
 
-    def set_speculative(self, draft=4, ngram=3, min=2):
+    def set_speculative(self, draft=4, ngram=3, min=2, sampled=False):
         """q4_set_speculative: the token loops verify up to `draft` drafted tokens per pass over the weights (0: off); ngram / min: the longest and the
-        shortest n-gram the built-in prompt-lookup drafter matches. Greedy runs only; the tokens are those of the run without it."""
+        shortest n-gram the built-in prompt-lookup drafter matches. Greedy runs, and with sampled=True (q4_set_speculative_sampled) runs under the
+        temperature / top-p sampler too: every row is sampled with its own position's coin. The tokens are those of the run without it."""
         check(lib().q4_set_speculative(self.h, int(draft), int(ngram), int(min)))
+        check(lib().q4_set_speculative_sampled(self.h, 1 if sampled else 0))
+
+    def speculative_sampled(self):
+        """q4_get_speculative_sampled: whether verify passes also run under the temperature / top-p sampler"""
+        return bool(lib().q4_get_speculative_sampled(self.h))
+
+    def verify_sampled(self, draft):
+        """q4_verify_tokens_sampled at the current position under the model's sampler: (emitted tokens, n_accepted), or None where nothing ran. The
+        sampler's stream must stand at the current position's coin; n_accepted + 1 coins of it are consumed."""
+        d = np.ascontiguousarray(draft, dtype=np.int32)
+        out = np.zeros(d.shape[0] + 1, dtype=np.int32)
+        acc = C.c_int()
+        rc = lib().q4_verify_tokens_sampled(self.h, self.sampler, d.ctypes.data, d.shape[0], out.ctypes.data, C.byref(acc))
+        if rc == NOT_ADMITTED:
+            return None
+        check(rc)
+        return out[: acc.value + 1].copy(), acc.value
+
+    def verify_covers_sampled(self, pos, n_draft):
+        return bool(lib().q4_verify_covers_sampled(self.h, self.sampler, int(pos), int(n_draft)))
 
     def speculative(self):
         d, g, m = C.c_int(), C.c_int(), C.c_int()

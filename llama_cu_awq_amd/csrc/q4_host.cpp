@@ -569,12 +569,21 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
-    // ... and speculative greedy decoding (q4_parse_speculative): Q4_SPECULATIVE="draft=4,ngram=3,min=2"; runs that are not greedy keep their steps
+    // ... and speculative greedy decoding (q4_parse_speculative): Q4_SPECULATIVE="draft=4,ngram=3,min=2"; runs that are not greedy keep their steps unless Q4_SPECULATIVE_SAMPLED says otherwise
     const char* spec = getenv("Q4_SPECULATIVE");
     if (spec && *spec) {
         int draft = 0, ngram = 0, ngram_min = 0;
         if (q4_parse_speculative(spec, &draft, &ngram, &ngram_min) || q4_set_speculative(&transformer, draft, ngram, ngram_min)) {
             fprintf(stderr, "Q4_SPECULATIVE: cannot use '%s' (keys: draft, ngram, min; draft 0 .. %d, 1 <= min <= ngram <= %d; e.g. draft=4,ngram=3,min=2)\n", spec, Q4_SPEC_MAX_DRAFT, Q4_SPEC_MAX_NGRAM);
+            exit(EXIT_FAILURE);
+        }
+    }
+    // ... and verify passes under the temperature / top-p sampler (q4_set_speculative_sampled), a variable of its own: Q4_SPECULATIVE_SAMPLED=1
+    const char* spec_sampled = getenv("Q4_SPECULATIVE_SAMPLED");
+    if (spec_sampled && *spec_sampled) {
+        int on = 0;
+        if (q4_parse_speculative_sampled(spec_sampled, &on) || q4_set_speculative_sampled(&transformer, on)) {
+            fprintf(stderr, "Q4_SPECULATIVE_SAMPLED: cannot use '%s' (0 or 1: verify passes also under the temperature / top-p sampler; needs Q4_SPECULATIVE)\n", spec_sampled);
             exit(EXIT_FAILURE);
         }
     }

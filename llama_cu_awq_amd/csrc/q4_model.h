@@ -49,7 +49,8 @@ struct Model {
     int shift_keep = 0, shift_discard = 0;   // q4_set_context_shift: what the library's own token loops shift by at seq_len; discard 0: off
     int shifted_keep = -1;          // the smallest n_keep of the q4_shift_context calls since the last q4_reset_sequence, -1: none -- rows above it are not "computed from the ring's tokens" (q4_common_prefix)
     int spec_draft = 0, spec_ngram_max = 0, spec_ngram_min = 0;   // q4_set_speculative: the most drafts a verify pass of the token loops carries (0: off) and the built-in drafter's n-gram range
-    q4_drafter_fn drafter = nullptr;   // q4_set_drafter: null, the built-in drafter (q4_spec_draft)
+    bool spec_sampled = false;      // q4_set_speculative_sampled: verify passes also under a temperature / top-p sampler (each row sampled with its position's coin)
+    q4_drafter_fn drafter = nullptr;  // q4_set_drafter: null, the built-in drafter (q4_spec_draft)
     void* drafter_ctx = nullptr;
     long long spec_passes = 0, spec_drafted = 0, spec_accepted = 0;   // q4_spec_stats
     bool rows_suspect = false;      // q4_handoff_status reported a time-out and no q4_reset_sequence has followed: the K / V rows below the position are not to be reused (q4_common_prefix)

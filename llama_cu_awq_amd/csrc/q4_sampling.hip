@@ -14,8 +14,10 @@
 //     restates this one. An entry of probability 0 is never that index (scan_search_phase has the reason).
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <map>
 #include "q4_device.h"
 #include "q4_internal.h"
+#include "spec_verify.h"
 using namespace q4;
 
 namespace {
@@ -351,11 +353,19 @@ __device__ __forceinline__ int block_last_nonzero(int last, int n, int* wmin) {
 // elements k = 2 j, 2 j + 1 of virtual thread l, the fp32 exponentials meet in LDS, wave 0 adds each virtual thread's 32 values in
 // order, and the wave tree's result goes to wave_total[b]. The fp16-rounded exponentials go to a scratch array (`logits` is still
 // being read by slower blocks); topp_sample_kernel<true> normalises them with the 16-lane tree over wave_total.
+// ROWS (a verify pass under the sampler, spec_verify.h): blockIdx.y is a row of logits `ld` halves apart; its exponentials go to e16 + row * n, its
+// wave totals to wave_total + row * 16. The arithmetic of a row is the step's.
 constexpr int SMX_B = 16;
+template <bool ROWS>
 __global__ void __launch_bounds__(SMP_T) softmax_spread_kernel(const q4_half* __restrict__ logits, int n, float temperature,
-                                                             uint16_t* __restrict__ e16, float* __restrict__ wave_total) {
+                                                             uint16_t* __restrict__ e16, float* __restrict__ wave_total, int ld) {
     __shared__ float red[16];
     __shared__ float es[SMP_E][64];
+    if (ROWS) {
+        logits += (size_t)blockIdx.y * ld;
+        e16 += (size_t)blockIdx.y * n;
+        wave_total += blockIdx.y * SMX_B;
+    }
     const int tid = threadIdx.x, lane = tid & 63, j = tid >> 6, b = blockIdx.x;
     // global maximum of the raw logits, 16-byte loads (n % 8 == 0)
     float m = -3.402823466e+38f;
@@ -393,20 +403,28 @@ __global__ void __launch_bounds__(SMP_T) softmax_spread_kernel(const q4_half* __
 // xorshift stream (sampler.h:31-40) ahead of the replay and leaves the values in a pinned ring, so the launch carries no
 // per-step argument -- else `coin`. x_next != nullptr (several steps per replay): the sampled token's embedding row becomes the
 // next step's residual stream right here, like argmax_kernel does for greedy steps.
-template <bool PRE>
+// ROWS (a verify pass under the sampler, spec_verify.h; PRE, on chip): block t is row t -- its logits `ld` halves behind row 0's, its exponentials at
+// k0 + t * n, its wave totals at wave_total + 16 t, its coin coins[*pPosGpu + t] (coins[t] where pPosGpu is null) -- and all it leaves behind the
+// probabilities in its logits row is result[t], its token: no ring entry, no position word, no x_next. Everything between is the step's, one body.
+template <bool PRE, bool ROWS = false>
 __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int n, float temperature, int do_sort,
                                                           float coin, const float* coins, float topp, int* indices, uint16_t* k0, int* v0,
                                                           uint16_t* k1, int* v1, int* result, volatile int* pPos,
-                                                          int* pPosGpu, q4_half* x_next, const q4_half* table, int dim, const float* wave_total) {
+                                                          int* pPosGpu, q4_half* x_next, const q4_half* table, int dim, const float* wave_total, int ld) {
     extern __shared__ __attribute__((aligned(16))) unsigned dyn[];   // [32768] sort buffer (on-chip path) + [4096] counters
     __shared__ float red[16];
     __shared__ unsigned wtot[16];
     __shared__ int wmin[16];
     __shared__ int s_token;
     __shared__ float red6[96];
-    if (coins != nullptr) coin = coins[*pPosGpu];            // (requested first: a PCIe read that returns under the softmax)
+    if (ROWS) {
+        coin = coins[(pPosGpu != nullptr ? *pPosGpu : 0) + (int)blockIdx.x];
+        logits += (size_t)blockIdx.x * ld;
+        k0 += (size_t)blockIdx.x * n;
+        wave_total += blockIdx.x * SMX_B;
+    } else if (coins != nullptr) coin = coins[*pPosGpu];     // (requested first: a PCIe read that returns under the softmax)
     const float threshold = do_sort ? coin * topp : coin;    // sampler.h:57-59,69
-    const bool onchip = n <= SMP_T * SMP_E;
+    const bool onchip = ROWS || n <= SMP_T * SMP_E;
     unsigned* buf = dyn;
     unsigned* cnt = onchip ? dyn + SMP_T * SMP_E : dyn;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -712,6 +730,10 @@ __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int
         if (tid == 0) token = v1[hit];
     }
     SMP_STAMP(6);
+    if (ROWS) {
+        if (tid == 0) result[blockIdx.x] = token;
+        return;
+    }
     if (x_next != nullptr) {                                 // (uniform: a kernel argument)
         if (tid == 0) s_token = token;
         __syncthreads();
@@ -729,7 +751,73 @@ __global__ void __launch_bounds__(SMP_T) topp_sample_kernel(q4_half* logits, int
     }
 }
 
+// Scratch of the row form, beside the Sampler (whose layout is the reference's): fp16 exponentials [PROMPT_PASS_MAX][vocab], wave totals
+// [PROMPT_PASS_MAX][16], and -- for q4_verify_sample_rows -- the rows' explicit coins. Allocated by sample_rows_prepare, freed by sample_rows_release.
+struct RowScratch { uint16_t* e16; float* wave_total; float* coins; };
+std::map<const Sampler*, RowScratch>& row_scratch() { static std::map<const Sampler*, RowScratch> m; return m; }
+
 }  // namespace
+
+namespace q4 {
+
+bool sample_rows_covers(const Sampler* sampler) {
+    const int n = sampler->vocab_size;
+    return n >= 8 && n <= SMP_T * SMP_E && (n & 7) == 0 && sampler->temperature > 0.0f && sampler->temperature <= 3.402823466e+38f;
+}
+
+int sample_rows_prepare(Sampler* sampler) {
+    if (!sample_rows_covers(sampler)) return Q4_ERR_UNSUPPORTED_SIZE;
+    if (row_scratch().find(sampler) == row_scratch().end()) {
+        RowScratch r = {nullptr, nullptr, nullptr};
+        const size_t n = (size_t)sampler->vocab_size;
+        if (hipMalloc((void**)&r.e16, PROMPT_PASS_MAX * n * sizeof(uint16_t)) != hipSuccess || hipMalloc((void**)&r.wave_total, PROMPT_PASS_MAX * SMX_B * sizeof(float)) != hipSuccess ||
+            hipMalloc((void**)&r.coins, PROMPT_PASS_MAX * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (r.e16) (void)hipFree(r.e16);
+            if (r.wave_total) (void)hipFree(r.wave_total);
+            if (r.coins) (void)hipFree(r.coins);
+            return Q4_ERR_ALLOC;
+        }
+        row_scratch()[sampler] = r;
+    }
+    return q4::lds_opt_in((const void*)topp_sample_kernel<true, true>, SMP_T * SMP_E * 4 + 256 * SMP_W * 4);
+}
+
+void sample_rows_release(const Sampler* sampler) {
+    auto it = row_scratch().find(sampler);
+    if (it == row_scratch().end()) return;
+    (void)hipFree(it->second.e16);
+    (void)hipFree(it->second.wave_total);
+    (void)hipFree(it->second.coins);
+    row_scratch().erase(it);
+}
+
+int launch_sample_rows(Sampler* sampler, q4_half* logits, int ld, int n_rows, const float* coins, int* pPosGpu, int* win) {
+    if (!sampler || !logits || !coins || !win || n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < sampler->vocab_size || (ld & 7)) return Q4_ERR_ARG;
+    auto it = row_scratch().find(sampler);
+    if (it == row_scratch().end()) return Q4_ERR_ARG;       // (sample_rows_prepare first: nothing is allocated on the launch path)
+    const int n = sampler->vocab_size;
+    const int do_sort = !(sampler->topp <= 0 || sampler->topp >= 1);
+    Q4_LAUNCH(softmax_spread_kernel<true>, dim3(SMX_B, n_rows), dim3(SMP_T), 0, logits, n, sampler->temperature, it->second.e16, it->second.wave_total, ld);
+    Q4_LAUNCH((topp_sample_kernel<true, true>), dim3(n_rows), dim3(SMP_T), (size_t)SMP_T * SMP_E * 4 + 256 * SMP_W * 4, logits, n, sampler->temperature, do_sort, 0.f,
+              coins, sampler->topp, sampler->indices, it->second.e16, (int*)nullptr, (uint16_t*)nullptr, (int*)nullptr, win, (volatile int*)nullptr, pPosGpu,
+              (q4_half*)nullptr, (const q4_half*)nullptr, 0, (const float*)it->second.wave_total, ld);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+
+}  // namespace q4
+
+// The row form on rows the caller holds, with explicit coins (include/llama2_q4.h): for tests and tools
+extern "C" int q4_verify_sample_rows(Sampler* sampler, q4_half* logits, int ld, int n_rows, const float* coins_host, int* tokens_dev) {
+    if (!sampler || !logits || !coins_host || !tokens_dev || n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < sampler->vocab_size || (ld & 7)) return Q4_ERR_ARG;
+    if (!q4::sample_rows_covers(sampler)) return Q4_ERR_UNSUPPORTED_SIZE;
+    int rc = q4::sample_rows_prepare(sampler);
+    if (rc) return rc;
+    float* coins = row_scratch()[sampler].coins;
+    Q4_HIP(hipMemcpyAsync(coins, coins_host, (size_t)n_rows * sizeof(float), hipMemcpyHostToDevice, g_stream));   // (pageable: staged before the call returns)
+    return q4::launch_sample_rows(sampler, logits, ld, n_rows, coins, nullptr, tokens_dev);
+}
 
 // scratch and LDS opt-in of the sampling launch: outside any stream capture (hipMalloc / hipFuncSetAttribute are not capturable)
 extern "C" __attribute__((visibility("hidden"))) int q4_sample_topp_prepare(Sampler* sampler) {
@@ -762,12 +850,12 @@ extern "C" __attribute__((visibility("hidden"))) int q4_sample_topp_device(Sampl
     // (the spread softmax takes max(logit) / T for the maximum of the scaled logits: true for T > 0 only. A negative temperature -- the CLI clamps it,
     // the C / Python API does not -- goes the one-block way, which like the reference takes the maximum of the scaled values and stays finite)
     if (n <= SMP_T * SMP_E && (n & 7) == 0 && sampler->temperature > 0.0f) {      // the softmax over 16 CUs, then normalise + search on one
-        Q4_LAUNCH(softmax_spread_kernel, dim3(SMX_B), dim3(SMP_T), 0, s->logits, n, sampler->temperature, k0, wave_total);
+        Q4_LAUNCH(softmax_spread_kernel<false>, dim3(SMX_B), dim3(SMP_T), 0, s->logits, n, sampler->temperature, k0, wave_total, 0);
         Q4_LAUNCH(topp_sample_kernel<true>, dim3(1), dim3(SMP_T), smem, s->logits, n, sampler->temperature, do_sort, coin, coins, sampler->topp,
-                  sampler->indices, k0, v0, k1, v1, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, x_next, table, dim, wave_total);
+                  sampler->indices, k0, v0, k1, v1, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, x_next, table, dim, wave_total, 0);
     } else {
         Q4_LAUNCH(topp_sample_kernel<false>, dim3(1), dim3(SMP_T), smem, s->logits, n, sampler->temperature, do_sort, coin, coins, sampler->topp,
-                  sampler->indices, k0, v0, k1, v1, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, x_next, table, dim, wave_total);   // :53-80
+                  sampler->indices, k0, v0, k1, v1, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, x_next, table, dim, wave_total, 0);   // :53-80
     }
     Q4_LAUNCH_CHECK();
     return Q4_OK;

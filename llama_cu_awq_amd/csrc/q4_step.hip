@@ -203,7 +203,8 @@ static int prompt_pass_tokens(const Transformer* t, const Model* m, const Sample
 // fusion level in force >= 3 with an attention form the pass reproduces at every position (pass_attention_plan), prompt_pass_covers' geometry (fp16 cache,
 // unmasked stream), no log-probability records, no guide, no context-shift offset, every position inside the bin of `pos`, below the bound of
 // q4_set_pass_context and inside seq_len -- plus a classifier shape the pass's launch
-// takes. A token loop adds (sampler non-null): temperature 0, no logit stage on, every position inside `steps`. With all of that off a greedy generating
+// takes. A token loop adds (sampler non-null): temperature 0 -- or, with the model's spec_sampled switch on, a sampler the row form of the sampling
+// launches takes (sample_rows_covers) --, no logit stage on, every position inside `steps`. With all of that off a greedy generating
 // step leaves, by position: its K / V rows, ring[pos + 1], the two position words; and, not by position: RunState::logits, RunState::x (un-normalised
 // behind the strips classifier; what the pass writes), the scratch vectors xb / hb / q / att (rewritten by every step before it reads them), the hand-off
 // epoch (never rewound; a pass does not advance it, as a prompt pass does not), the screen's tallies (q4_screen_candidates counts screened steps: a pass
@@ -212,7 +213,12 @@ static bool verify_covers(const Transformer* t, const Model* m, const Sampler* s
     if (g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0 || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
     const Config* p = &t->config;
     if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps) return false;
-    if (sampler && (sampler->temperature != 0.0f || any_stage_on(sampler, m))) return false;
+    if (sampler && sampler->temperature != 0.0f) {
+        // q4_set_speculative_sampled: the pass under the sampler -- the row form of its two launches (the on-chip vocabulary, a finite temperature above 0;
+        // a negative one keeps the one-block softmax of the step) and a vocabulary that is the model's
+        if (!m->spec_sampled || sampler->vocab_size != p->vocab_size || !sample_rows_covers(sampler)) return false;
+    }
+    if (sampler && any_stage_on(sampler, m)) return false;
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return false;
     PassAttention plan;
     return pass_attention_plan(p, &t->state, pos, n_draft + 1, &plan);
@@ -317,6 +323,11 @@ int q4_parse_speculative(const char* text, int* max_draft, int* ngram_max, int* 
     *ngram_min = (int)v[2];
     return Q4_OK;
 }
+int q4_parse_speculative_sampled(const char* text, int* on) {     // the CLI's Q4_SPECULATIVE_SAMPLED: "0" or "1", nothing else
+    if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
+    *on = text[0] - '0';
+    return Q4_OK;
+}
 int q4_set_drafter(Transformer* t, q4_drafter_fn fn, void* ctx) {
     Model* m = t ? model_of(&t->state) : nullptr;
     if (!m) return Q4_ERR_ARG;
@@ -417,7 +428,23 @@ static int coin_ring_for(const Sampler* sampler, int positions, CoinRing** out) 
     *out = &r;
     return Q4_OK;
 }
+// The coins of a verify pass under the sampler (spec_verify.h) at positions pos .. pos + n_draft: drawn from the sampler's stream into the ring -- the
+// coin at a position is the same value whoever draws it -- and the stream put back where it stood. The pass's advance m says how many positions ran, and
+// the caller then draws m + 1: one coin per position that ran, as the steps draw them. Entries above the new position are stale and harmless: whatever
+// runs there next writes its own.
+static int stage_pass_coins(Sampler* sampler, const Config* p, int pos, int n_draft, const float** coins_dev) {
+    CoinRing* ring = nullptr;
+    Q4_TRY(coin_ring_for(sampler, p->seq_len, &ring));
+    if (pos < 0 || pos + n_draft >= ring->cap) return Q4_ERR_ARG;
+    const unsigned long long rng = sampler->rng_state;
+    for (int i = 0; i <= n_draft; i++) ring->host[pos + i] = random_f32(&sampler->rng_state);
+    sampler->rng_state = rng;
+    Q4_HIP(hipMemcpyAsync(ring->dev + pos, ring->host + pos, (size_t)(n_draft + 1) * sizeof(float), hipMemcpyHostToDevice, g_stream));
+    *coins_dev = ring->dev;
+    return Q4_OK;
+}
 void destroy_sampler(Sampler* sampler) {
+    sample_rows_release(sampler);
     for (int i = 0; i < N_STAGES; i++) {
         if (!STAGES[i]->forget) continue;
         if (const void* block = STAGES[i]->block(sampler)) {        // graphs with the stage's launch hold the block's address
@@ -505,6 +532,44 @@ static int step_tail(const StepTail& t, const Config* p, RunState* s, const Tran
     else
         Q4_TRY(q4_argmax(s->logits, p->vocab_size, &(s->shared_data->tokens[0]), &(s->shared_data->pos), s->pos, t.gen_token));
     return t.lp_pick ? launch_logprobs_pick(t.lpm, p, s) : Q4_OK;
+}
+
+// ---- verify passes under the temperature / top-p sampler (spec_verify.h): the switch, the probe, the primitive ----
+int q4_set_speculative_sampled(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->spec_sampled = on != 0;
+    return Q4_OK;
+}
+int q4_get_speculative_sampled(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->spec_sampled ? 1 : 0;
+}
+int q4_verify_covers_sampled(const Transformer* t, const Sampler* sampler, int pos, int n_draft) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && sampler && sampler->temperature != 0.0f && verify_covers(t, m, sampler, pos, n_draft, t->config.seq_len, 0) ? 1 : 0;
+}
+int q4_verify_tokens_sampled(Transformer* t, Sampler* sampler, const int* draft, int n_draft, int* out_tokens, int* n_accepted) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || !sampler || !draft || !out_tokens || !n_accepted || n_draft < 1 || n_draft > Q4_SPEC_MAX_DRAFT) return Q4_ERR_ARG;
+    for (int i = 0; i < n_draft; i++)
+        if (draft[i] < 0 || draft[i] >= t->config.vocab_size) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const int pos = t->state.shared_data->pos;
+    if (m->rows_suspect || !q4_verify_covers_sampled(t, sampler, pos, n_draft)) return Q4_NOT_ADMITTED;
+    const float* coins = nullptr;
+    Q4_TRY(stage_pass_coins(sampler, &t->config, pos, n_draft, &coins));
+    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, pos, draft, n_draft, sampler, coins));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const int acc = t->state.shared_data->pos - (pos + 1);
+    if (acc < 0 || acc > n_draft) return Q4_ERR_HIP;
+    for (int i = 0; i <= acc; i++) (void)random_f32(&sampler->rng_state);      // one coin per position that ran
+    m->spec_passes++;
+    m->spec_drafted += n_draft;
+    m->spec_accepted += acc;
+    for (int i = 0; i <= acc; i++) out_tokens[i] = t->state.shared_data->tokens[pos + 1 + i];
+    *n_accepted = acc;
+    return Q4_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -890,7 +955,12 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                 group_start = pos;
                 group_rng = sampler->rng_state;
                 if (nd) {      // positions pos .. pos + m run, m the accepted drafts: known once the pass has published its position
-                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, pos, draft, nd));
+                    // under the sampler (q4_set_speculative_sampled): the coins of positions pos .. pos + nd go to the ring and the stream is put back; the m + 1
+                    // draws above, once m is known, leave it where the steps would
+                    Sampler* const vs = sampler->temperature != 0.0f ? sampler : nullptr;
+                    const float* coins = nullptr;
+                    if (vs) Q4_TRY(stage_pass_coins(vs, &t->config, pos, nd, &coins));
+                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, pos, draft, nd, vs, coins));
                     verify_pos = pos;
                     verify_drafts = nd;
                 } else if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them

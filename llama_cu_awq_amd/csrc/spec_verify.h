@@ -10,6 +10,12 @@
 // the next step or pass at those positions writes them again. Drafts travel by value in a kernel argument: an unconfirmed token never enters the ring or
 // pinned memory. Every dependency is a launch boundary: the pass waits on nothing in-launch and touches neither the model's hand-off words nor its
 // granules (the attention launch writes the prompt pass's own sink).
+//
+// Under the temperature / top-p sampler (q4_set_speculative_sampled): a sampled step is a function of its logits and one coin, and the coin is a function
+// of (seed, position) that reaches the device through the coin ring by position. So between the classifier and the accept launch every row is sampled in
+// place with its own position's coin, exactly as the step at that position would (the row form of the two sampler launches, q4_sampling.hip), and the
+// accept launch takes those tokens instead of the rows' argmax: the leading drafts that equal the sampled tokens are accepted, RunState::logits receives
+// row m's fp16 probabilities -- what the sampled step leaves there --, and the run is the run without passes for that seed, byte for byte.
 #pragma once
 #include "prompt_pass.h"
 
@@ -28,9 +34,24 @@ int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, c
 // x: rows of dim halves. report (device, 9 ints, may be null): the rows' greedy tokens and, in [8], m.
 int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
                          int* ring, volatile int* pPos, int* pPosGpu, int* report);
+// ... with the rows' tokens given (win, device, d.n + 1 ints) instead of each row's argmax: the pass under the sampler. The rows then hold what the row form
+// of the sampler left in place -- fp16 probabilities, which is what a sampled step leaves in RunState::logits -- and everything behind the tokens is the same.
+int launch_verify_accept_tokens(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
+                                q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report);
+// The row form of the temperature / top-p sampler (q4_sampling.hip): rows t < n_rows of logits, `ld` halves apart, each normalised IN PLACE and searched as
+// the sampled step does for that row alone -- softmax_spread_kernel's and topp_sample_kernel<true>'s arithmetic, one grid slice per row -- with the coin
+// coins[*pPosGpu + t] (coins[t] where pPosGpu is null); win[t] = the row's token and nothing else is written. Only the on-chip form: a vocabulary of at most
+// 32 x 1024 entries, a multiple of 8, and a finite temperature above 0 (sample_rows_covers). sample_rows_prepare allocates the per-row scratch beside the
+// Sampler on first use (outside the launch path); destroy_sampler releases it.
+bool sample_rows_covers(const Sampler* sampler);
+int sample_rows_prepare(Sampler* sampler);
+int launch_sample_rows(Sampler* sampler, q4_half* logits, int ld, int n_rows, const float* coins, int* pPosGpu, int* win);
+void sample_rows_release(const Sampler* sampler);
 // The whole pass at the device position, which the caller knows to be pos0 (q4_step.hip's verify_covers has admitted it there). On the launch stream;
-// nothing is waited for.
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft);
+// nothing is waited for. sampler null: greedy. Else the pass under that sampler: behind the classifier the rows are sampled (coins: the device coin ring by
+// position, entries pos0 .. pos0 + n_draft drawn by the caller) and the accept launch takes those tokens.
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler = nullptr,
+                    const float* coins = nullptr);
 void verify_release(const RunState* s);   // q4_free_transformer: the pass's logits rows of this model
 
 }  // namespace q4

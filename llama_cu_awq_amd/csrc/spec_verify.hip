@@ -96,15 +96,23 @@ int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, c
 // One block. Row by row argmax_kernel's rule (q4_kernels.hip): 16-byte loads, the first maximum inside a thread, the tail past the last whole chunk, value
 // then lower index across threads, 0 for a row without a finite or +inf entry. Then m = the leading drafts the rows confirm, the copies of row m, and --
 // in argmax_kernel's order -- the ring entries, a fence, both position words. No atomics; one writer per word.
+// GIVEN (a pass under the sampler): the rows' tokens are win[0 .. d.n], what the row form of the sampler left (q4_sampling.hip), and no row is searched;
+// the rows then hold probabilities, which is what a sampled step leaves in RunState::logits. Everything behind the tokens is the one code.
+template <bool GIVEN>
 __global__ void __launch_bounds__(1024) verify_accept_kernel(const q4_half* logits, const int ld, const int size, const VerifyDrafts d, const q4_half* x, const int dim,
-                                                             q4_half* logits_out, q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report) {
+                                                             q4_half* logits_out, q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report,
+                                                             const int* win) {
     __shared__ float sval[16];
     __shared__ int sidx[16];
     __shared__ int s_win[PROMPT_PASS_MAX];
     __shared__ int s_m;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n8 = size >> 3;
-    for (int t = 0; t <= d.n; t++) {
+    if (GIVEN) {
+        if (tid <= d.n) s_win[tid] = win[tid];
+        __syncthreads();
+    }
+    for (int t = 0; !GIVEN && t <= d.n; t++) {
         const q4_half* row = logits + (size_t)t * ld;
         float max_val = -INFINITY;
         int max_pos = 0x7fffffff;
@@ -171,7 +179,15 @@ __global__ void __launch_bounds__(1024) verify_accept_kernel(const q4_half* logi
 int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
                          int* ring, volatile int* pPos, int* pPosGpu, int* report) {
     if (d.n < 1 || d.n > VERIFY_MAX_DRAFT || size < 1 || ld < size || (ld & 7) || (dim & 7) || !logits || !logits_out || !ring || !pPos || !pPosGpu) return Q4_ERR_ARG;
-    Q4_LAUNCH(verify_accept_kernel, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report);
+    Q4_LAUNCH(verify_accept_kernel<false>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report,
+              (const int*)nullptr);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+int launch_verify_accept_tokens(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
+                                q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report) {
+    if (d.n < 1 || d.n > VERIFY_MAX_DRAFT || size < 1 || ld < size || (ld & 7) || (dim & 7) || !logits || !logits_out || !ring || !pPos || !pPosGpu || !win) return Q4_ERR_ARG;
+    Q4_LAUNCH(verify_accept_kernel<true>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report, win);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -196,7 +212,10 @@ void verify_release(const RunState* s) {
     logit_rows().erase(it);
 }
 
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft) {
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler,
+                    const float* coins) {
+    if (sampler && (!coins || sampler->vocab_size != p->vocab_size)) return Q4_ERR_ARG;
+    if (sampler) Q4_TRY(sample_rows_prepare(sampler));       // (scratch on first use and the LDS opt-in: in front of the pass's first launch)
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size) || !draft || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
     VerifyDrafts d = {};
     d.n = n_draft;
@@ -210,7 +229,8 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, c
     auto it = logit_rows().find(s);
     if (it == logit_rows().end()) {
         void* buf = nullptr;
-        if (hipMalloc(&buf, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half)) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+        // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
+        if (hipMalloc(&buf, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half) + PROMPT_PASS_MAX * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
         it = logit_rows().insert({s, (q4_half*)buf}).first;
     }
     Q4_LAUNCH(verify_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, rows.x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens, d,
@@ -218,6 +238,12 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, c
     Q4_LAUNCH_CHECK();
     Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
     Q4_TRY(launch_verify_cls(it->second, rows.x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
+    if (sampler) {      // each row sampled in place with its own position's coin, as the step at that position would; then the accept on those tokens
+        int* win = reinterpret_cast<int*>(it->second + (size_t)PROMPT_PASS_MAX * p->vocab_size);
+        Q4_TRY(launch_sample_rows(sampler, it->second, p->vocab_size, n, coins, s->pos, win));
+        return launch_verify_accept_tokens(it->second, p->vocab_size, p->vocab_size, d, win, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens,
+                                           &(s->shared_data->pos), s->pos, nullptr);
+    }
     return launch_verify_accept(it->second, p->vocab_size, p->vocab_size, d, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens, &(s->shared_data->pos),
                                 s->pos, nullptr);
 }
@@ -241,6 +267,15 @@ int q4_verify_accept(const q4_half* logits, int ld, int size, const int* draft, 
     d.n = n_draft;
     for (int i = 0; i < n_draft; i++) d.tok[i] = draft[i];
     return launch_verify_accept(logits, ld, size, d, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
+}
+
+int q4_verify_accept_tokens(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const int* tokens_dev, const q4_half* x, int dim,
+                            q4_half* logits_out, q4_half* x_out, int* ring, int* pos_host, int* pos_dev, int* report) {
+    if (!draft || !tokens_dev || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
+    VerifyDrafts d = {};
+    d.n = n_draft;
+    for (int i = 0; i < n_draft; i++) d.tok[i] = draft[i];
+    return launch_verify_accept_tokens(logits, ld, size, d, tokens_dev, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
 }
 
 }  // extern "C"
