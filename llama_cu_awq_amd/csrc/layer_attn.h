@@ -17,7 +17,7 @@
 //  * the tag is the value of the model's epoch word at entry. The word is advanced by the PRECEDING launch of the stream
 //    (the fused QKV GEMV, gemv_q4.h `bump`), never by this one: all blocks read the same value, whatever their timing.
 //  * every wait is a bounded poll; one that runs out sets the model's sticky error word, which the token loops turn into a
-//    clean retry at fusion level 1 (q4_step.hip).
+//    clean retry at fusion level 1 (q4_sequence.hip, q4_loops.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "attention.h"

@@ -1,5 +1,5 @@
 // prompt_pass.h -- a prompt pass: up to PROMPT_PASS_MAX consecutive prompt-only positions run layer by layer with ONE read of every weight
-// (prompt_pass.hip). What q4_step.hip's token loop and q4_model.hip see of it.
+// (prompt_pass.hip). What q4_loops.hip's token loop, q4_passes.hip's admission and q4_model.hip see of it.
 #pragma once
 #include "q4_model.h"
 
@@ -8,10 +8,10 @@ namespace q4 {
 constexpr int PROMPT_PASS_MAX = 8;      // tokens per weight read (T)
 constexpr int PASS_CONTEXT_MIN = 256;   // q4_set_pass_context: the default bound, the end of the V-slice bins
 
-// The geometry part of the admission (q4_step.hip decides the rest): Llama-2-7B's shape -- dim 4096, multi-head, 128-wide heads, a hidden size the
+// The geometry part of the admission (q4_passes.hip decides the rest): Llama-2-7B's shape -- dim 4096, multi-head, 128-wide heads, a hidden size the
 // three-phase FFN launch admits (its down projection is the two-part K split in three k-slots), a rotation table, an fp16 cache, an unmasked stream.
 bool prompt_pass_covers(const Config* p, const Model* m);
-// Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_step.hip, the admission's one place): for every position the
+// Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_passes.hip, the admission's one place): for every position the
 // form of the step's attention -> o-proj launch (attention_oproj_form of the bin argument the step would hand to run_network there) is either a V-slice
 // form (5 / 6: form = 5, prompt_attention_kernel) or ONE split-context form for all of them (form = 4 / 2 / 3, chunk = 64 / 128 / 256 positions:
 // prompt_split_attention_kernel + prompt_merge_kernel). nsp: chunks per head the pass launches and lays its records out by; nsp_of_bin: the chunk count
@@ -21,14 +21,15 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // Positions pos0 = *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all inside one bin and below the bound of q4_set_pass_context, all prompt-only) on the
 // launch stream: K / V rows of every layer, then RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No
 // classifier, no sampler.
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n);
-void prompt_pass_release(const RunState* s);   // q4_free_transformer: the pass's scratch vectors of this model
-// What the verify pass (spec_verify.h) shares with the prompt pass: the model's scratch rows -- x [PROMPT_PASS_MAX][dim] residual streams, pos
-// [PROMPT_PASS_MAX] their positions (allocated on first use) -- and the layer loop over rows 0 .. n - 1 of them: the five launches per layer of
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
+void pass_release(Model* m);   // q4_free_transformer: the scratch of this model's prompt and verify passes (Model::pass)
+// q4_passes.hip. A prompt pass in place of the token loop's per-token prompt steps from `pos`: how many positions it takes, 0 for none (its comment there)
+int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int num_prompt_tokens, int steps, int off);
+// What the verify pass (spec_verify.h) shares with the prompt pass: the model's scratch rows -- Model::pass.x [PROMPT_PASS_MAX][dim] residual streams, .pos
+// [PROMPT_PASS_MAX] their positions (prompt_pass_rows allocates the scratch on first use) -- and the layer loop over rows 0 .. n - 1 of them: the five launches per layer of
 // run_prompt_pass (six in the split-context bins: the records' merge is a launch of its own), which reads the device position and moves nothing. The
 // caller fills x and pos in front and takes the final residual streams from x.
-struct PassRows { q4_half* x; int* pos; };
-int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out);
-int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n);
+int prompt_pass_rows(Model* m, const Config* p);
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
 
 }  // namespace q4

@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <math.h>
-#include <map>
 #include "layer_attn.h"
 #include "prompt_pass.h"
 
@@ -471,44 +470,38 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-struct PassBuf { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; u32x2v* sink; size_t sink_stride; float* records; size_t record_floats; };
-static std::map<const RunState*, PassBuf>& pass_bufs() { static std::map<const RunState*, PassBuf> b; return b; }
-
-void prompt_pass_release(const RunState* s) {
-    auto it = pass_bufs().find(s);
-    if (it == pass_bufs().end()) return;
-    if (it->second.slab) (void)hipFree(it->second.slab);
-    if (it->second.records) (void)hipFree(it->second.records);
-    pass_bufs().erase(it);
+void pass_release(Model* m) {
+    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows})
+        if (d) (void)hipFree(d);
+    m->pass = PassScratch{};
 }
 
-static int pass_buf_of(const RunState* s, int dim, int hidden, PassBuf** out) {
-    auto it = pass_bufs().find(s);
-    if (it == pass_bufs().end()) {
-        const size_t T = PROMPT_PASS_MAX;
-        const size_t sink_words = line_area_words((size_t)dim / 2);      // 32-bit words of one token's granule area
-        const size_t vec = T * (size_t)dim * sizeof(q4_half), hb = T * (size_t)hidden * sizeof(q4_half);
+int prompt_pass_rows(Model* m, const Config* p) {
+    PassScratch& b = m->pass;
+    if (!b.slab) {
+        const size_t T = PROMPT_PASS_MAX, dim = p->dim, hidden = p->hidden_dim;
+        const size_t sink_words = line_area_words(dim / 2);      // 32-bit words of one token's granule area
+        const size_t vec = T * dim * sizeof(q4_half), hb = T * hidden * sizeof(q4_half);
         const size_t bytes = 3 * vec + hb + 256 + T * sink_words * 4;
-        PassBuf b = {};
-        if (hipMalloc(&b.slab, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
-        Q4_HIP(hipMemsetAsync(b.slab, 0, bytes, g_stream));
-        char* c = (char*)b.slab;
+        void* slab = nullptr;
+        if (hipMalloc(&slab, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+        Q4_HIP(hipMemsetAsync(slab, 0, bytes, g_stream));
+        char* c = (char*)slab;
         b.x = (q4_half*)c; c += vec;
         b.q = (q4_half*)c; c += vec;
         b.xb = (q4_half*)c; c += vec;
         b.hb = (q4_half*)c; c += hb;
         b.pos = (int*)c; c += 256;
-        b.sink = (u32x2v*)c;
+        b.sink = (unsigned*)c;
         b.sink_stride = sink_words / 2;
-        it = pass_bufs().insert({s, b}).first;
+        b.slab = slab;
     }
-    *out = &it->second;
     return Q4_OK;
 }
 
 // The split passes' flash-decode records: the pass's own buffer (never RunState::att, whose words are validated by tag), allocated on the first split
 // pass of the model for the longest context it can meet -- PROMPT_PASS_MAX tokens x heads x chunks x (head_size + ATT_REC_PAD) floats.
-static int pass_records_of(PassBuf* b, size_t floats) {
+static int pass_records_of(PassScratch* b, size_t floats) {
     if (b->record_floats >= floats) return Q4_OK;
     if (b->records) {
         Q4_HIP(hipStreamSynchronize(g_stream));              // a pass that reads the old area may still be in flight
@@ -516,9 +509,7 @@ static int pass_records_of(PassBuf* b, size_t floats) {
         b->records = nullptr;
         b->record_floats = 0;
     }
-    void* r = nullptr;
-    if (hipMalloc(&r, floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
-    b->records = (float*)r;
+    if (hipMalloc((void**)&b->records, floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); b->records = nullptr; return Q4_ERR_ALLOC; }
     b->record_floats = floats;
     return Q4_OK;
 }
@@ -541,23 +532,15 @@ bool prompt_pass_covers(const Config* p, const Model* m) {
     return stream_cu_count() == cu_count();
 }
 
-int prompt_pass_rows(const RunState* s, const Config* p, PassRows* out) {
-    PassBuf* b = nullptr;
-    Q4_TRY(pass_buf_of(s, p->dim, p->hidden_dim, &b));
-    out->x = b->x;
-    out->pos = b->pos;
-    return Q4_OK;
-}
-
 // The layer loop of a pass, shared by the prompt pass below and the verify pass (spec_verify.hip): rows 0 .. n - 1 of the model's scratch rows hold the
 // positions' residual streams going in (and pos[t] their positions), and their final residual streams coming out. pos0: the position of row 0 as the
 // host knows it (the device position when the pass runs) -- which attention launch the layers take is decided from it (pass_attention_plan), the kernels
 // read the positions from pos[].
-int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n) {
+int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
-    PassBuf* b = nullptr;
-    Q4_TRY(pass_buf_of(s, dim, hidden, &b));
+    Q4_TRY(prompt_pass_rows(m, p));
+    PassScratch* const b = &m->pass;
     PassAttention plan = {};
     if (!pass_attention_plan(p, s, pos0, n, &plan)) return Q4_ERR_ARG;
     const bool split = att_is_split(plan.form);
@@ -598,7 +581,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             Q4_LAUNCH_CHECK();
         } else {   // attention below bin 512: the V-slice units
             const AttArgs a = {b->xb, b->q, s->key_cache + loff, s->value_cache + loff, head_size, 1, dim, b->pos, alpha, 256, nullptr};
-            Q4_LAUNCH(prompt_attention_kernel, dim3((unsigned)n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, b->sink, (unsigned)b->sink_stride,
+            Q4_LAUNCH(prompt_attention_kernel, dim3((unsigned)n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, (u32x2v*)b->sink, (unsigned)b->sink_stride,
                       (unsigned)p->n_heads, natt, dim);
             Q4_LAUNCH_CHECK();
         }
@@ -631,11 +614,11 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     return Q4_OK;
 }
 
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, int n) {
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim;
-    PassBuf* b = nullptr;
-    Q4_TRY(pass_buf_of(s, dim, p->hidden_dim, &b));
+    Q4_TRY(prompt_pass_rows(m, p));
+    const PassScratch* const b = &m->pass;
     Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
               (const int*)s->pos, b->pos);
     Q4_LAUNCH_CHECK();

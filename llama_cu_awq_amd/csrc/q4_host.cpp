@@ -1,6 +1,6 @@
 // q4_host.cpp -- host-only side of llama2_q4: the llama2.c BPE tokenizer (tokenizer.h), the generate / chat /
 // perplexity drivers (llama2_q4.cu:436-601, perplexity.h:57-139) and the CLI (llama2_q4.cu:604-720).
-// No device code here; everything reaches the GPU through the C ABI in llama2_q4.h, but for q4_step.hip's token loop and the step it queues (q4_loop.h).
+// No device code here; everything reaches the GPU through the C ABI in llama2_q4.h, but for q4_loops.hip's token loop and the step it queues (q4_loop.h).
 #include <ctype.h>
 #include <math.h>
 #include <stdint.h>

@@ -110,6 +110,7 @@ extern int g_ao_vslice;
 extern int g_ao_hold_pct;
 extern int g_ao16;
 extern int g_multi_steps;
+extern int g_prompt_passes;   // q4_passes.hip: prompt passes run since the library was loaded (q4_prompt_passes)
 // Which form of the int4 GEMV launches run. The shipped library only ever holds GEMV_PRODUCT; the profiling library's knob 11
 // (q4_set_gemv_early(11, form)) sets the others for A/B runs and for the bit-equality cases of tests/prof_cases.py.
 enum GemvForm {

@@ -1,5 +1,5 @@
 // q4_logprobs.hip -- per-token log-probabilities and top-k alternatives of the model's OWN distribution (temperature 1, no nucleus: not
-// what the sampler drew from), computed from the step's fp16 logits before the sampler destroys them. Not in the reference.
+// what the sampler drew from), computed from the step's fp16 logits before the sampler destroys them, and the record ring's switch and read-out. Not in the reference.
 //   lse = m + logf(sum_i expf(l_i - m)), m = max_i l_i, fp32; a log-probability is l - lse (one fp32 subtraction).
 // ONE 1024-thread block (the argmax launch beside it is one block too; the whole vocabulary is 64 KB of L2 hits):
 //   * thread t owns the 16-byte chunks t, t + 1024, ... (8 consecutive logits each) and, past the last whole chunk, one tail element -- argmax_kernel's
@@ -273,4 +273,50 @@ extern "C" int q4_logprob_topk(const q4_half* logits, int n, int top_k, const in
                                float* top_logprobs) {
     if (!logits || !lse || !target_logprob || (top_k > 0 && (!top_ids || !top_logprobs))) return Q4_ERR_ARG;
     return launch_topk(logits, n, top_k, LP_TARGET, target, 0, nullptr, 1, lse, target_logprob, top_ids, top_logprobs, nullptr);
+}
+
+// the record ring: the per-model switch and the read-out (teacher-forced scoring over them: q4_loops.hip's q4_score_ids)
+extern "C" int q4_set_logprobs(Transformer* t, int top_k) {
+    if (!t || top_k < -1 || top_k > Q4_MAX_TOP_LOGPROBS) return Q4_ERR_ARG;
+    Model* m = model_of(&t->state);
+    if (!m || top_k > t->config.vocab_size) return Q4_ERR_ARG;
+    if (top_k == m->logprobs_k) return Q4_OK;
+    if (top_k >= 0 && !logprobs_size_ok(t->config.vocab_size, top_k)) return Q4_ERR_UNSUPPORTED_SIZE;
+    const size_t S = (size_t)t->config.seq_len, K = (size_t)(top_k < 0 ? 0 : top_k);
+    const size_t side = ((size_t)t->config.vocab_size * sizeof(q4_half) + 255) / 256 * 256;
+    const size_t bytes = side + S * sizeof(float) * 2 + S * K * (sizeof(int) + sizeof(float));
+    void* ring = nullptr;                                                          // the new ring first: a failed allocation leaves the setting as it was
+    if (top_k >= 0 && hipMalloc(&ring, bytes) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
+    drop_logprob_graphs_of(&t->state);
+    (void)hipStreamSynchronize(g_stream);                                         // an eager launch may still be writing the old ring
+    if (m->lp_ring) (void)hipFree(m->lp_ring);
+    m->lp_ring = nullptr; m->lp_lse = m->lp_token = m->lp_top = nullptr; m->lp_ids = nullptr; m->lp_side = nullptr;
+    m->logprobs_k = -1;
+    if (top_k < 0) return Q4_OK;
+    m->lp_ring = ring;
+    Q4_HIP(hipMemsetAsync(m->lp_ring, 0, bytes, g_stream));
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    char* c = (char*)m->lp_ring;
+    m->lp_side = (q4_half*)c; c += side;
+    m->lp_lse = (float*)c; c += S * sizeof(float);
+    m->lp_token = (float*)c; c += S * sizeof(float);
+    m->lp_ids = (int*)c; c += S * K * sizeof(int);
+    m->lp_top = (float*)c;
+    m->logprobs_k = top_k;
+    return Q4_OK;
+}
+extern "C" int q4_get_logprobs_k(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m ? m->logprobs_k : -1;
+}
+extern "C" int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_logprob, int* top_ids, float* top_logprobs) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m || m->logprobs_k < 0 || first_pos < 0 || n < 0 || (long long)first_pos + n > t->config.seq_len) return Q4_ERR_ARG;
+    Q4_HIP(hipStreamSynchronize(g_stream));
+    const size_t K = (size_t)m->logprobs_k, f = (size_t)first_pos;
+    if (n == 0) return Q4_OK;
+    if (token_logprob) Q4_HIP(hipMemcpy(token_logprob, m->lp_token + f, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (top_ids && K) Q4_HIP(hipMemcpy(top_ids, m->lp_ids + f * K, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost));
+    if (top_logprobs && K) Q4_HIP(hipMemcpy(top_logprobs, m->lp_top + f * K, (size_t)n * K * sizeof(float), hipMemcpyDeviceToHost));
+    return Q4_OK;
 }

@@ -1,4 +1,4 @@
-// q4_loop.h -- what q4_step.hip keeps for q4_host.cpp's drivers beside the C ABI: the step a token loop queues and the generate loop itself. Not
+// q4_loop.h -- what q4_step.hip and q4_loops.hip keep for q4_host.cpp's drivers beside the C ABI: the step a token loop queues and the generate loop itself. Not
 // exported (exports.map lists neither); plain C++ over llama2_q4.h's types, no HIP.
 #pragma once
 #include "llama2_q4.h"

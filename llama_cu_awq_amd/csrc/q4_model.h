@@ -1,6 +1,7 @@
-// q4_model.h -- what the library keeps beside a Transformer, what q4_model.hip, q4_network.hip and q4_step.hip share, and the row a logit stage gives
-// the step (not part of the C ABI).
+// q4_model.h -- what the library keeps beside a Transformer, what the host side's translation units (q4_model.hip, q4_network.hip, q4_step.hip,
+// q4_sequence.hip, q4_passes.hip, q4_loops.hip) share, and the row a logit stage gives the step (not part of the C ABI).
 #pragma once
+#include <stddef.h>
 #include <map>
 #include <vector>
 #include "q4_internal.h"
@@ -8,6 +9,9 @@
 
 namespace q4 {
 
+// The scratch of the prompt and verify passes (prompt_pass.h, spec_verify.h), each allocation made on first use and released by pass_release. slab: the rows x / q / xb
+// / hb, their positions and the attention launch's sink (u32x2v granules); records: the split passes' flash-decode records; logit_rows: the verify pass's logits and tokens
+struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; };
 // every Transformer owns two HBM slabs (weights, run state) instead of ~750 small allocations: layers sit
 // back to back in HBM in the order the token loop streams them. ONE record per model: q4_build_transformer registers it as soon as its
 // first allocation exists, q4_free_transformer is the only place that releases and forgets it.
@@ -53,6 +57,7 @@ struct Model {
     q4_drafter_fn drafter = nullptr;  // q4_set_drafter: null, the built-in drafter (q4_spec_draft)
     void* drafter_ctx = nullptr;
     long long spec_passes = 0, spec_drafted = 0, spec_accepted = 0;   // q4_spec_stats
+    PassScratch pass = {};          // nothing until the model's first prompt or verify pass
     bool rows_suspect = false;      // q4_handoff_status reported a time-out and no q4_reset_sequence has followed: the K / V rows below the position are not to be reused (q4_common_prefix)
 };
 // the network entry points take (Config, RunState, TransformerWeights), not the Transformer: the record is found by RunState (&t->state)
@@ -64,6 +69,9 @@ static inline Model* model_of(const RunState* s) {
     return it == models().end() ? nullptr : &it->second;
 }
 
+// The Transformer around a RunState / a Config that model_of has said the library built: both sit inside it
+static inline const Transformer* transformer_of(const RunState* s) { return reinterpret_cast<const Transformer*>(reinterpret_cast<const char*>(s) - offsetof(Transformer, state)); }
+static inline const Transformer* transformer_of(const Config* p) { return reinterpret_cast<const Transformer*>(reinterpret_cast<const char*>(p) - offsetof(Transformer, config)); }
 #define Q4_TRY(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
 
 // q4_model.hip: the process-wide setting q4_build_transformer reads (q4_set_rope_scaling); its inv_freq points at the library's copy
@@ -76,6 +84,8 @@ int run_network(const int* pPos, const Config* p, RunState* s, const Transformer
 // q4_step.hip
 void drop_graphs_of(const RunState* s);   // the model's captured graphs, after the launch stream has drained
 void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the log-probability launch only
+bool any_stage_on(const Sampler* sampler, const Model* m);        // a logit stage of the table below is on for this sampler and model
+int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out);   // the graph bin of a step whose sequence length is seq_len: its index, and its size
 // q4_logprobs.hip. The record launch of a step (in front of the sampler: reads the position before it advances) and the chosen token's look-up behind
 // the sampler of a sampled step
 bool logprobs_size_ok(int n, int top_k);

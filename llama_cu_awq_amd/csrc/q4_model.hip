@@ -504,8 +504,7 @@ void q4_free_transformer(Transformer* t) {                                      
         hipDeviceSynchronize();
         guide_release(&m);
         adaptive_release(&m);
-        prompt_pass_release(&t->state);
-        verify_release(&t->state);
+        pass_release(&m);
         for (void* d : {m.weights, m.state, m.logits_array, (void*)m.rope_table, (void*)m.inv_freq_dev, (void*)m.sync, m.lp_ring, m.screen.base})
             if (d) hipFree(d);
         if (m.shared) hipHostFree(m.shared);

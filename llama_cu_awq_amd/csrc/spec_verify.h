@@ -22,8 +22,11 @@
 namespace q4 {
 
 constexpr int VERIFY_MAX_DRAFT = PROMPT_PASS_MAX - 1;
+static_assert(VERIFY_MAX_DRAFT == Q4_SPEC_MAX_DRAFT, "the public bound on a pass's drafts is the kernel argument's capacity");
 
 struct VerifyDrafts { int n; int tok[VERIFY_MAX_DRAFT]; };
+// *out from draft[0 .. n_draft). Q4_ERR_ARG: draft null, n_draft outside [1, VERIFY_MAX_DRAFT], an id outside [0, vocab) (vocab < 0: ids are not checked)
+int verify_drafts(const int* draft, int n_draft, int vocab, VerifyDrafts* out);
 
 // Geometry the classifier launch of a pass takes: dim 4096 (eight 1 KiB pieces per vocabulary row) and a vocabulary that is a multiple of 8 -- both forms
 // classifier_with_final_norm can take for such a model (strips, or rmsnorm_kernel + gemv_f16_kernel) round the same sums in the same order.
@@ -31,13 +34,11 @@ bool verify_cls_covers(int dim, int vocab);
 // logits [n][vocab] = wcls . rmsnorm(x[t], rms_w) for rows t < n <= PROMPT_PASS_MAX, x [n][dim]; on the launch stream
 int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n);
 // The accept launch. logits: rows of `size` halves `ld` apart (ld a multiple of 8: rows stay 16-byte aligned), row t the logits at position *pPosGpu + t;
-// x: rows of dim halves. report (device, 9 ints, may be null): the rows' greedy tokens and, in [8], m.
-int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
-                         int* ring, volatile int* pPos, int* pPosGpu, int* report);
-// ... with the rows' tokens given (win, device, d.n + 1 ints) instead of each row's argmax: the pass under the sampler. The rows then hold what the row form
+// x: rows of dim halves. report (device, 9 ints, may be null): the rows' tokens and, in [8], m. win null: a row's token is its argmax.
+// Else the rows' tokens are given (win, device, d.n + 1 ints) instead of each row's argmax: the pass under the sampler. The rows then hold what the row form
 // of the sampler left in place -- fp16 probabilities, which is what a sampled step leaves in RunState::logits -- and everything behind the tokens is the same.
-int launch_verify_accept_tokens(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
-                                q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report);
+int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
+                         q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report);
 // The row form of the temperature / top-p sampler (q4_sampling.hip): rows t < n_rows of logits, `ld` halves apart, each normalised IN PLACE and searched as
 // the sampled step does for that row alone -- softmax_spread_kernel's and topp_sample_kernel<true>'s arithmetic, one grid slice per row -- with the coin
 // coins[*pPosGpu + t] (coins[t] where pPosGpu is null); win[t] = the row's token and nothing else is written. Only the on-chip form: a vocabulary of at most
@@ -47,11 +48,16 @@ bool sample_rows_covers(const Sampler* sampler);
 int sample_rows_prepare(Sampler* sampler);
 int launch_sample_rows(Sampler* sampler, q4_half* logits, int ld, int n_rows, const float* coins, int* pPosGpu, int* win);
 void sample_rows_release(const Sampler* sampler);
-// The whole pass at the device position, which the caller knows to be pos0 (q4_step.hip's verify_covers has admitted it there). On the launch stream;
+// The whole pass at the device position, which the caller knows to be pos0 (q4_passes.hip's verify_covers has admitted it there). On the launch stream;
 // nothing is waited for. sampler null: greedy. Else the pass under that sampler: behind the classifier the rows are sampled (coins: the device coin ring by
 // position, entries pos0 .. pos0 + n_draft drawn by the caller) and the accept launch takes those tokens.
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler = nullptr,
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler = nullptr,
                     const float* coins = nullptr);
-void verify_release(const RunState* s);   // q4_free_transformer: the pass's logits rows of this model
+// q4_passes.hip. The admission of a pass at `pos` (sampler null: the primitive's greedy form); the drafter's answer for ring[0 .. n_tokens); q4_spec_stats' counters
+bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off);
+int ask_drafter(const Model* m, const int* ring, int n_tokens, int max_draft, int vocab, int* draft);
+void count_verify_pass(Model* m, int n_draft, int accepted);
+// q4_step.hip (the coin ring lives there). The coins of positions pos .. pos + n_draft into the sampler's device ring, the sampler's stream put back
+int stage_pass_coins(Sampler* sampler, const Config* p, int pos, int n_draft, const float** coins_dev);
 
 }  // namespace q4

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <math.h>
-#include <map>
 #include "gemv_q4.h"
 #include "spec_verify.h"
 
@@ -176,19 +175,21 @@ __global__ void __launch_bounds__(1024) verify_accept_kernel(const q4_half* logi
     }
 }
 
-int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
-                         int* ring, volatile int* pPos, int* pPosGpu, int* report) {
+int launch_verify_accept(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
+                         q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report) {
     if (d.n < 1 || d.n > VERIFY_MAX_DRAFT || size < 1 || ld < size || (ld & 7) || (dim & 7) || !logits || !logits_out || !ring || !pPos || !pPosGpu) return Q4_ERR_ARG;
-    Q4_LAUNCH(verify_accept_kernel<false>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report,
-              (const int*)nullptr);
+    if (win) Q4_LAUNCH(verify_accept_kernel<true>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report, win);
+    else Q4_LAUNCH(verify_accept_kernel<false>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report, win);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
-int launch_verify_accept_tokens(const q4_half* logits, int ld, int size, const VerifyDrafts& d, const int* win, const q4_half* x, int dim, q4_half* logits_out,
-                                q4_half* x_out, int* ring, volatile int* pPos, int* pPosGpu, int* report) {
-    if (d.n < 1 || d.n > VERIFY_MAX_DRAFT || size < 1 || ld < size || (ld & 7) || (dim & 7) || !logits || !logits_out || !ring || !pPos || !pPosGpu || !win) return Q4_ERR_ARG;
-    Q4_LAUNCH(verify_accept_kernel<true>, dim3(1), dim3(1024), 0, logits, ld, size, d, x, dim, logits_out, x ? x_out : nullptr, ring, pPos, pPosGpu, report, win);
-    Q4_LAUNCH_CHECK();
+int verify_drafts(const int* draft, int n_draft, int vocab, VerifyDrafts* out) {
+    if (!draft || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
+    *out = VerifyDrafts{n_draft, {}};
+    for (int i = 0; i < n_draft; i++) {
+        if (vocab >= 0 && (draft[i] < 0 || draft[i] >= vocab)) return Q4_ERR_ARG;
+        out->tok[i] = draft[i];
+    }
     return Q4_OK;
 }
 
@@ -203,48 +204,31 @@ __global__ void verify_embed_kernel(q4_half* xs, const q4_half* table, int dim, 
     reinterpret_cast<u32x4*>(xs + (size_t)t * dim)[u] = reinterpret_cast<const u32x4*>(table + (size_t)token * dim)[u];
 }
 
-static std::map<const RunState*, q4_half*>& logit_rows() { static std::map<const RunState*, q4_half*> b; return b; }
-
-void verify_release(const RunState* s) {
-    auto it = logit_rows().find(s);
-    if (it == logit_rows().end()) return;
-    if (it->second) (void)hipFree(it->second);
-    logit_rows().erase(it);
-}
-
-int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, const Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler,
+int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler,
                     const float* coins) {
     if (sampler && (!coins || sampler->vocab_size != p->vocab_size)) return Q4_ERR_ARG;
     if (sampler) Q4_TRY(sample_rows_prepare(sampler));       // (scratch on first use and the LDS opt-in: in front of the pass's first launch)
-    if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size) || !draft || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
-    VerifyDrafts d = {};
-    d.n = n_draft;
-    for (int i = 0; i < n_draft; i++) {
-        if (draft[i] < 0 || draft[i] >= p->vocab_size) return Q4_ERR_ARG;
-        d.tok[i] = draft[i];
-    }
+    if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return Q4_ERR_ARG;
+    VerifyDrafts d;
+    Q4_TRY(verify_drafts(draft, n_draft, p->vocab_size, &d));
     const int dim = p->dim, n = n_draft + 1;
-    PassRows rows = {};
-    Q4_TRY(prompt_pass_rows(s, p, &rows));
-    auto it = logit_rows().find(s);
-    if (it == logit_rows().end()) {
-        void* buf = nullptr;
-        // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
-        if (hipMalloc(&buf, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half) + PROMPT_PASS_MAX * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return Q4_ERR_ALLOC; }
-        it = logit_rows().insert({s, (q4_half*)buf}).first;
+    Q4_TRY(prompt_pass_rows(m, p));
+    const PassScratch& rows = m->pass;
+    // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
+    if (!m->pass.logit_rows && hipMalloc((void**)&m->pass.logit_rows, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half) + PROMPT_PASS_MAX * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError(); m->pass.logit_rows = nullptr; return Q4_ERR_ALLOC;
     }
     Q4_LAUNCH(verify_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, rows.x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens, d,
               (const int*)s->pos, rows.pos);
     Q4_LAUNCH_CHECK();
     Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
-    Q4_TRY(launch_verify_cls(it->second, rows.x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
+    Q4_TRY(launch_verify_cls(rows.logit_rows, rows.x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
+    int* win = nullptr;
     if (sampler) {      // each row sampled in place with its own position's coin, as the step at that position would; then the accept on those tokens
-        int* win = reinterpret_cast<int*>(it->second + (size_t)PROMPT_PASS_MAX * p->vocab_size);
-        Q4_TRY(launch_sample_rows(sampler, it->second, p->vocab_size, n, coins, s->pos, win));
-        return launch_verify_accept_tokens(it->second, p->vocab_size, p->vocab_size, d, win, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens,
-                                           &(s->shared_data->pos), s->pos, nullptr);
+        win = reinterpret_cast<int*>(rows.logit_rows + (size_t)PROMPT_PASS_MAX * p->vocab_size);
+        Q4_TRY(launch_sample_rows(sampler, rows.logit_rows, p->vocab_size, n, coins, s->pos, win));
     }
-    return launch_verify_accept(it->second, p->vocab_size, p->vocab_size, d, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens, &(s->shared_data->pos),
+    return launch_verify_accept(rows.logit_rows, p->vocab_size, p->vocab_size, d, win, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens, &(s->shared_data->pos),
                                 s->pos, nullptr);
 }
 
@@ -262,20 +246,17 @@ int q4_verify_classifier(q4_half* logits, const q4_half* x, const q4_half* rms_w
 
 int q4_verify_accept(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const q4_half* x, int dim, q4_half* logits_out, q4_half* x_out,
                      int* ring, int* pos_host, int* pos_dev, int* report) {
-    if (!draft || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
-    VerifyDrafts d = {};
-    d.n = n_draft;
-    for (int i = 0; i < n_draft; i++) d.tok[i] = draft[i];
-    return launch_verify_accept(logits, ld, size, d, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
+    VerifyDrafts d;
+    Q4_TRY(verify_drafts(draft, n_draft, -1, &d));
+    return launch_verify_accept(logits, ld, size, d, nullptr, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
 }
 
 int q4_verify_accept_tokens(const q4_half* logits, int ld, int size, const int* draft, int n_draft, const int* tokens_dev, const q4_half* x, int dim,
                             q4_half* logits_out, q4_half* x_out, int* ring, int* pos_host, int* pos_dev, int* report) {
-    if (!draft || !tokens_dev || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT) return Q4_ERR_ARG;
-    VerifyDrafts d = {};
-    d.n = n_draft;
-    for (int i = 0; i < n_draft; i++) d.tok[i] = draft[i];
-    return launch_verify_accept_tokens(logits, ld, size, d, tokens_dev, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
+    VerifyDrafts d;
+    if (!tokens_dev) return Q4_ERR_ARG;
+    Q4_TRY(verify_drafts(draft, n_draft, -1, &d));
+    return launch_verify_accept(logits, ld, size, d, tokens_dev, x, dim, logits_out, x_out, ring, pos_host, pos_dev, report);
 }
 
 }  // extern "C"

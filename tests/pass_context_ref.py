@@ -1,5 +1,5 @@
 """Python restatement of where the token loop takes a prompt pass or a verify pass once q4_set_pass_context lets passes above position 255
-(csrc/q4_step.hip: pass_attention_plan, prompt_pass_tokens, verify_covers). Pure arithmetic on positions: no GPU, no library.
+(csrc/q4_passes.hip: pass_attention_plan, prompt_pass_tokens, verify_covers). Pure arithmetic on positions: no GPU, no library.
 
 The rules restated:
   * a pass touches positions below min(bound, seq_len) only, bound = max(256, the value set);

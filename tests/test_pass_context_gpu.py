@@ -44,7 +44,7 @@ def _rows(t, n_pos):
 
 def _x(q4, t, normalise=False):
     """RunState::x. A step of this model (vocabulary 512: q4_rmsnorm + q4_matmul_f16, no strips classifier) leaves it normalised in place, a verify pass
-    leaves the accepted row's residual stream as it is (csrc/q4_step.hip, verify_covers' comment); normalise: through the step's own q4_rmsnorm."""
+    leaves the accepted row's residual stream as it is (csrc/q4_passes.hip, verify_covers' comment); normalise: through the step's own q4_rmsnorm."""
     L = q4.lib()
     if normalise:
         q4.check(L.q4_rmsnorm(t.state.contents.x, t.state.contents.x, t.weights.contents.rms_final_weight, DIM))

@@ -490,3 +490,67 @@ def test_snapshot_after_a_speculative_run(q4, models):
         if t2 is not None:
             t2.close()
     _assert_same(off, got, "restored snapshot")
+
+
+# ---- 8. the passes' scratch belongs to its model -----------------------------------------------------------------------------------------------
+def test_pass_scratch_lives_and_dies_with_its_model(q4, models):
+    """The scratch of prompt and verify passes is part of the model's record (csrc/q4_model.h PassScratch): allocated by the model's first pass, released
+    by q4_free_transformer. Model A runs prompt passes and a verify pass and is freed; B, built where A may have lived, runs the same; C is built beside B
+    and verify passes alternate between the two, with drafts accepted and rejected. Every run's tokens and the K / V rows below its position are the
+    bytes of the per-token steps: the same checkpoint with q4_set_prompt_ingest(0) and no speculation."""
+    L = q4.lib()
+    path, prompt, p = models["spec_cls_ragged"], _prompt(), 20
+    ingest_max = q4.get_prompt_ingest()
+    q4.set_prompt_ingest(0)
+    ref = q4.Transformer(path)
+    try:
+        passes = q4.prompt_passes()
+        R = ref.generate_ids(prompt, p + 12)[0].copy()
+        q4.check(L.q4_handoff_status(ref.state))
+        assert q4.prompt_passes() == passes and ref.spec_stats() == (0, 0, 0)
+        assert len(R) == p + 13 and 2 not in R[1:].tolist()              # (no EOS: the run reached its last step)
+        kv = _state(ref, p + 12)[0]
+    finally:
+        ref.close()
+        q4.set_prompt_ingest(ingest_max)
+
+    def ingest(t, what):          # positions 0 .. 15 in prompt passes, 16 .. p - 1 in steps
+        before = q4.prompt_passes()
+        toks = t.generate_ids(prompt, p)[0]
+        assert q4.prompt_passes() > before, "%s: no prompt pass ran" % what
+        assert np.array_equal(toks, R[:p + 1]), "%s: tokens behind the prompt passes" % what
+        return p
+
+    def verify(t, pos, k, what):  # a verify pass with 2 drafts, the first k of them right: the position behind it
+        assert t.pos() == pos and t.verify_covers(pos, 2), what
+        drafts = [int(R[pos + 1]), int(R[pos + 2])]
+        if k < 2:
+            drafts[k] = _wrong(R[pos + 1 + k])
+        before = t.spec_stats()
+        emitted, acc = t.verify(drafts)
+        assert acc == k and emitted.tolist() == R[pos + 1:pos + k + 2].tolist() and t.pos() == pos + k + 1, "%s: pass at %d, %d right" % (what, pos, k)
+        assert t.spec_stats() == (before[0] + 1, before[1] + 2, before[2] + k), what
+        bad = np.unique(np.argwhere(_state(t, pos + k + 1)[0] != kv[:pos + k + 1])[:, 0])
+        assert bad.size == 0, "%s: K / V rows differ at positions %s behind the pass at %d" % (what, bad[:8], pos)
+        return pos + k + 1
+
+    a = q4.Transformer(path)
+    try:
+        verify(a, ingest(a, "A"), 2, "A")
+        q4.check(L.q4_handoff_status(a.state))
+    finally:
+        a.close()
+    b, c = q4.Transformer(path), None
+    try:
+        pos_b = verify(b, ingest(b, "B, built after A was freed"), 2, "B, built after A was freed")
+        c = q4.Transformer(path)
+        pos_c = ingest(c, "C beside B")
+        for k_b, k_c in ((2, 0), (1, 2), (0, 1)):
+            pos_b = verify(b, pos_b, k_b, "B, alternating with C")
+            pos_c = verify(c, pos_c, k_c, "C, alternating with B")
+        q4.check(L.q4_handoff_status(b.state))
+        q4.check(L.q4_handoff_status(c.state))
+    finally:
+        b.close()
+        if c is not None:
+            c.close()
