@@ -217,6 +217,13 @@ int q4_argmax(const q4_half* x, int size, int* result, volatile int* pPos, int* 
 enum { Q4_MAX_TOP_LOGPROBS = 20 };
 int q4_logprob_topk(const q4_half* logits, int n, int top_k, const int* target, float* lse, float* target_logprob, int* top_ids,
                     float* top_logprobs);
+/* The row form of the same launch, for tests and tools: one block per row, n_rows rows (1 .. 8) of n halves, `ld` halves apart (ld a multiple of 8 and
+ * >= n: rows stay 16-byte aligned; the halves between n and ld are neither read nor written). Row r's outputs -- lse[r], target_logprob[r], top_ids and
+ * top_logprobs [r][top_k] -- are, byte for byte, what q4_logprob_topk writes for that row alone; targets: NULL, or [n_rows] device-visible ints. This is
+ * the launch prompt and verify passes run with q4_set_pass_logprobs on. Errors: q4_logprob_topk's, plus Q4_ERR_ARG for n_rows outside 1 .. 8 and for an
+ * ld below n or not a multiple of 8. */
+int q4_logprob_topk_rows(const q4_half* logits, int ld, int n, int n_rows, int top_k, const int* targets, float* lse, float* target_logprob, int* top_ids,
+                         float* top_logprobs);
 
 /* ---- network + per-token step ------------------------------------------------------------- */
 
@@ -348,6 +355,18 @@ int q4_get_logprobs_k(const Transformer* t);      /* -1: off, or a Transformer t
 /* Synchronises the stream (like the parity dumps), then copies records first_pos .. first_pos + n - 1 to the host: token_logprob [n], top_ids and
  * top_logprobs [n x K] (K = q4_get_logprobs_k). Any of the three may be NULL. Records off, or positions outside [0, seq_len]: Q4_ERR_ARG. */
 int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_logprob, int* top_ids, float* top_logprobs);
+/* Records inside prompt passes and verify passes (below; DESIGN.md 3.7 / 3.8, "With records"). Per model, off by default: off, records on keep every
+ * position on per-token steps, and the admission, every launch list, every captured graph, every bit and every counter are what they are without this
+ * call. on != 0 lifts only that one exclusion; everything else a pass requires stays, and with records on a prompt pass also needs the verify pass's
+ * classifier shape (dim 4096, a vocabulary that is a multiple of 8). A prompt pass then runs that classifier over its rows and the row form of the record
+ * launch (q4_logprob_topk_rows; the target of a row is the next prompt token) and leaves its last row in RunState::logits, as the last prompt step would.
+ * A verify pass runs the row form between its classifier and its accept launch (greedy: token_logprob is entry 0; under the sampler the raw rows are
+ * kept aside and the chosen tokens looked up behind the sampler's row form). Records p .. p + m of a verify pass that accepts m drafts are what m + 1
+ * steps write. Records p + m + 1 .. p + D describe rejected drafts: they lie at or above the device position and are rewritten by whatever runs there
+ * next -- the same contract as the K / V rows of rejected drafts. q4_score_ids takes prompt passes with the switch on. Every record, token, K / V row and
+ * the logits are those of the per-token run, byte for byte. Q4_ERR_ARG / 0: a Transformer the library did not build. */
+int q4_set_pass_logprobs(Transformer* t, int on);
+int q4_get_pass_logprobs(const Transformer* t);   /* 1: on; 0: off, or not a Transformer the library built */
 
 /* The classifier of a greedy step without streaming every fp16 row of wcls (csrc/cls_screen.h): where the classifier runs as strips (dim 4096 or
  * 5120, at least 64 vocabulary rows per CU, an unmasked stream) q4_build_transformer derives a per-row-scaled int8 copy of wcls (vocab x dim bytes: 131 MB
@@ -369,8 +388,8 @@ int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* t
  * its weights once and multiplies all the positions' activations. The K / V rows, the generated tokens and the final logits are the per-token steps', bit
  * for bit; a pass runs no classifier, so RunState::logits is not written by the positions it covers. Taken only where the result is the same and nothing
  * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits), fusion level
- * >= 3, an fp16 K / V cache, positions below the bound of q4_set_pass_context (256 unless raised), log-probability records off, no guide, no adaptive truncation, no context-shift offset, an unmasked
- * stream; everything else -- and q4_run_transformer*, q4_score_ids, q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
+ * >= 3, an fp16 K / V cache, positions below the bound of q4_set_pass_context (256 unless raised), log-probability records off or q4_set_pass_logprobs on, no guide, no adaptive truncation, no context-shift offset, an unmasked
+ * stream; everything else -- and q4_run_transformer*, q4_score_ids (unless q4_set_pass_logprobs is on), q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
  * clamped to 8, the default. q4_prompt_passes: passes run since the library was loaded. */
 void q4_set_prompt_ingest(int max_tokens);
 int q4_get_prompt_ingest(void);
@@ -398,7 +417,7 @@ int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const 
  * position p + m + 1, RunState::logits and RunState::x of step p + m, the K / V rows. K / V rows p + m + 1 .. p + D hold rows computed from rejected drafts:
  * they lie at or above the position (q4_common_prefix, q4_resume_sequence and snapshots never trust such rows) and are written again by whatever runs there next.
  * A pass is admitted where a prompt pass is (q4_set_prompt_ingest above: geometry, fusion level >= 3, fp16 cache, unmasked stream, no context-shift offset,
- * log-probability records off, no guide) and, in a token loop, only for a greedy sampler (temperature 0; q4_set_speculative_sampled below adds the
+ * log-probability records off or q4_set_pass_logprobs on, no guide) and, in a token loop, only for a greedy sampler (temperature 0; q4_set_speculative_sampled below adds the
  * temperature / top-p sampler) with no logit stage on (sampling controls, logit bias, DRY, adaptive truncation), with p .. p + D inside one bin (ends at 256, 512, 1024, ...), below the bound of q4_set_pass_context
  * (256 unless raised), inside `steps` and seq_len. Cost (7B, measured: DESIGN.md 3.8): a pass pays where drafts are usually
  * right and loses where they are not. */
@@ -836,13 +855,18 @@ float q4_get_dataset_perplexity(char* dataset, struct Tokenizer* tokenizer, Tran
 double q4_parse_dataset_and_compute_perplexity(const char* textFileName, struct Tokenizer* tokenizer,
                                                Transformer* t, Sampler* sampler);
 /* teacher-forced logits for given token ids (perplexity path without a tokenizer): runs num_tokens steps with
- * copyLogits, returns perplexity of targets[i] under step i's logits */
+ * copyLogits, returns perplexity of targets[i] under step i's logits. Always per token: the fp32 logits_array path is the reference's (one copy per
+ * step), and q4_set_pass_logprobs does not change it -- q4_score_ids below is the call that takes passes. */
 float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, int num_tokens);
 /* Teacher-forced scoring without the (seq_len, vocab) fp32 array -- works on a model built with perplexity = 0: logprobs_out[i] is the log-probability of
  * tokens_with_bos[i + 1] under step i's logits, i < num_tokens <= seq_len - 1 (more: Q4_ERR_ARG). The steps are queued like generate()'s prompt steps
  * (q4_steps_that_fit / q4_run_transformer_steps), one synchronise at the end, one retry after a timed-out hand-off. Records are switched on with
  * top_k = 0 for the call if they were off, and the setting is put back -- the ring and the graphs with the record launch then live for one call (each
- * such call captures them again, q4_graph_captures counts it): a host that scores repeatedly calls q4_set_logprobs(t, 0) once beforehand. */
+ * such call captures them again, q4_graph_captures counts it): a host that scores repeatedly calls q4_set_logprobs(t, 0) once beforehand.
+ * With q4_set_pass_logprobs on, wherever a prompt pass is admitted (q4_set_prompt_ingest; every position of this call is prompt-only, so a pass may take
+ * the last one too) up to 8 positions go out as one pass over the weights; a remainder of one position, positions at or above the bound of
+ * q4_set_pass_context and models the passes do not cover keep their steps. logprobs_out, the records with K > 0, RunState::logits and the position
+ * afterwards are the stepwise call's, byte for byte; q4_prompt_passes counts these passes too. */
 int q4_score_ids(Transformer* t, Sampler* s, const int* tokens_with_bos, int num_tokens, float* logprobs_out);
 
 /* ---- tokenizer.h:1-223 ------------------------------------------------------------------------ */

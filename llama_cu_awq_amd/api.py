@@ -208,6 +208,7 @@ SYMBOLS = [
     "q4_verify_tokens", "q4_verify_covers", "q4_set_speculative", "q4_get_speculative", "q4_parse_speculative", "q4_set_drafter", "q4_spec_draft",
     "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept", "q4_set_speculative_sampled", "q4_get_speculative_sampled", "q4_verify_tokens_sampled",
     "q4_verify_covers_sampled", "q4_verify_sample_rows", "q4_verify_accept_tokens", "q4_parse_speculative_sampled",
+    "q4_logprob_topk_rows", "q4_set_pass_logprobs", "q4_get_pass_logprobs",
 ]
 
 _lib = None
@@ -338,6 +339,10 @@ def lib():
         L.q4_get_logprobs_k.argtypes = [vp]
         L.q4_get_logprobs.argtypes = [vp, i, i, vp, vp, vp]
         L.q4_score_ids.argtypes = [vp, vp, vp, i, vp]
+    if hasattr(L, "q4_set_pass_logprobs"):         # (older builds under tools/ab.py do not have it)
+        L.q4_logprob_topk_rows.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp]
+        L.q4_set_pass_logprobs.argtypes = [vp, i]
+        L.q4_get_pass_logprobs.argtypes = [vp]
     if hasattr(L, "q4_set_greedy_screen"):         # (older builds under tools/ab.py do not have it)
         L.q4_set_greedy_screen.argtypes = [i]
         L.q4_set_greedy_screen.restype = None
@@ -763,6 +768,13 @@ def get_prompt_ingest():
     return lib().q4_get_prompt_ingest()
 
 
+def logprob_topk_rows(logits, ld, n, n_rows, top_k, targets, lse, target_logprob, top_ids=None, top_logprobs=None):
+    """q4_logprob_topk_rows over DevBufs: q4_logprob_topk for n_rows rows `ld` halves apart, one block per row. targets: a DevBuf of n_rows int32, or None;
+    the outputs hold n_rows (x top_k) entries."""
+    check(lib().q4_logprob_topk_rows(logits.ptr, ld, n, n_rows, top_k, targets.ptr if targets else None, lse.ptr, target_logprob.ptr,
+                                     top_ids.ptr if top_ids else None, top_logprobs.ptr if top_logprobs else None))
+
+
 def set_pass_context(positions):
     """q4_set_pass_context: the exclusive upper bound on the positions a prompt pass or a verify pass may touch; 256 (the default) at the least."""
     lib().q4_set_pass_context(int(positions))
@@ -809,7 +821,8 @@ class Transformer:
     """build_transformer / free_transformer (llama2_q4.cu:408-432) + run_transformer + sampler, by handle."""
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
-                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None):
+                 logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None,
+                 pass_logprobs=False):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -858,6 +871,8 @@ class Transformer:
         try:
             if logprobs is not None:
                 self.set_logprobs(logprobs)
+            if pass_logprobs:
+                self.set_pass_logprobs(True)
             if sampling is not None:
                 self.set_sampling(**sampling)
             if logit_bias is not None:
@@ -1191,6 +1206,15 @@ class Transformer:
     def set_logprobs(self, top_k):
         """Per-token log-probability records inside the decode step: None / -1 off, 0 the chosen or target token only, K <= 20 also the top K."""
         check(lib().q4_set_logprobs(self.h, -1 if top_k is None else int(top_k)))
+
+    def set_pass_logprobs(self, on):
+        """q4_set_pass_logprobs: prompt passes, verify passes and score_ids' passes also while the records are on (off by default: records keep the steps).
+        Records, tokens, K / V rows and logits are the per-token run's, byte for byte."""
+        check(lib().q4_set_pass_logprobs(self.h, 1 if on else 0))
+
+    def pass_logprobs(self):
+        """q4_get_pass_logprobs"""
+        return bool(lib().q4_get_pass_logprobs(self.h))
 
     def logprobs_k(self):
         return lib().q4_get_logprobs_k(self.h)

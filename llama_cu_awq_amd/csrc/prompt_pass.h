@@ -21,6 +21,9 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // Positions pos0 = *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all inside one bin and below the bound of q4_set_pass_context, all prompt-only) on the
 // launch stream: K / V rows of every layer, then RunState::x, the device position and SharedData::pos as n per-token prompt steps leave them. No
 // classifier, no sampler.
+// With log-probability records on (admitted only with q4_set_pass_logprobs on): behind the layer loop the verify pass's classifier (spec_verify.h) over the
+// n residual rows, the row form of the record launch (q4_logprobs.hip; the target of row r is the ring's tokens[pos0 + r + 1]) and a copy of the last row
+// to RunState::logits -- records pos0 .. pos0 + n - 1 and the logits are what n prompt steps with records leave, byte for byte -- then the finish launch.
 int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
 void pass_release(Model* m);   // q4_free_transformer: the scratch of this model's prompt and verify passes (Model::pass)
 // q4_passes.hip. A prompt pass in place of the token loop's per-token prompt steps from `pos`: how many positions it takes, 0 for none (its comment there)
@@ -30,6 +33,10 @@ int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* samp
 // run_prompt_pass (six in the split-context bins: the records' merge is a launch of its own), which reads the device position and moves nothing. The
 // caller fills x and pos in front and takes the final residual streams from x.
 int prompt_pass_rows(Model* m, const Config* p);
+// Model::pass.logit_rows ([PROMPT_PASS_MAX][vocab] logits and the PROMPT_PASS_MAX tokens behind them) and Model::pass.lp_side ([PROMPT_PASS_MAX][vocab]
+// raw rows of a pass under the sampler with records), each allocated on first use and released by pass_release
+int pass_logit_rows(Model* m, const Config* p);
+int pass_side_rows(Model* m, const Config* p);
 int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
 
 }  // namespace q4

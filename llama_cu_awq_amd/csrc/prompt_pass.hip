@@ -3,6 +3,8 @@
 // block per (token, head, V slice); in the split-context bins, positions >= 256 under q4_set_pass_context: one block per (head, chunk) that loops over the
 // tokens, and a launch that merges each token's records), o-proj + residual, rmsnorm + gate/up + SiLU, down projection + residual -- between an embedding launch and one that
 // leaves RunState::x and the position words as the per-token steps would. No launch waits for another block: every dependency is a launch boundary.
+// With log-probability records on (q4_set_pass_logprobs): the verify pass's classifier over the n rows and the row form of the record launch in front of
+// that last launch (run_prompt_pass).
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
 // parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
@@ -14,6 +16,7 @@
 #include <math.h>
 #include "layer_attn.h"
 #include "prompt_pass.h"
+#include "spec_verify.h"
 
 namespace q4 {
 
@@ -471,7 +474,7 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 
 // ---- host ------------------------------------------------------------------------------------------
 void pass_release(Model* m) {
-    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows})
+    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side})
         if (d) (void)hipFree(d);
     m->pass = PassScratch{};
 }
@@ -495,6 +498,22 @@ int prompt_pass_rows(Model* m, const Config* p) {
         b.sink = (unsigned*)c;
         b.sink_stride = sink_words / 2;
         b.slab = slab;
+    }
+    return Q4_OK;
+}
+
+// The logits of a pass that runs the classifier (a verify pass; a prompt pass with records): [PROMPT_PASS_MAX][vocab] halves and, behind them, the
+// PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch. pass_side_rows: the raw rows a pass under the sampler keeps for the
+// records' look-up behind it (q4_logprobs.hip). Both allocated on first use, outside the launch path of later passes.
+int pass_logit_rows(Model* m, const Config* p) {
+    if (!m->pass.logit_rows && hipMalloc((void**)&m->pass.logit_rows, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half) + PROMPT_PASS_MAX * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError(); m->pass.logit_rows = nullptr; return Q4_ERR_ALLOC;
+    }
+    return Q4_OK;
+}
+int pass_side_rows(Model* m, const Config* p) {
+    if (!m->pass.lp_side && hipMalloc((void**)&m->pass.lp_side, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half)) != hipSuccess) {
+        (void)hipGetLastError(); m->pass.lp_side = nullptr; return Q4_ERR_ALLOC;
     }
     return Q4_OK;
 }
@@ -617,12 +636,21 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
 int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim;
+    const bool records = m->logprobs_k >= 0;               // (admitted with records on: q4_set_pass_logprobs, q4_passes.hip)
+    if (records && (!m->pass_logprobs || !verify_cls_covers(dim, p->vocab_size))) return Q4_ERR_ARG;
     Q4_TRY(prompt_pass_rows(m, p));
+    if (records) Q4_TRY(pass_logit_rows(m, p));
     const PassScratch* const b = &m->pass;
     Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
               (const int*)s->pos, b->pos);
     Q4_LAUNCH_CHECK();
     Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
+    if (records) {      // what n prompt steps with records leave besides: records pos0 .. pos0 + n - 1 (the target of row r is the ring's next token) and, in
+        // RunState::logits, the last position's logits. The classifier of the verify pass over the n rows, then the row form of the record launch
+        Q4_TRY(launch_verify_cls(b->logit_rows, b->x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
+        Q4_TRY(launch_logprobs_rows(m, p, s, b->logit_rows, p->vocab_size, n, LP_TARGET));
+        Q4_HIP(hipMemcpyAsync(s->logits, b->logit_rows + (size_t)(n - 1) * p->vocab_size, (size_t)p->vocab_size * sizeof(q4_half), hipMemcpyDeviceToDevice, g_stream));
+    }
     Q4_LAUNCH(prompt_finish_kernel, dim3(1), dim3(1024), 0, s->x, (const q4_half*)(b->x + (size_t)(n - 1) * dim), dim, &(s->shared_data->pos), s->pos, n);
     Q4_LAUNCH_CHECK();
     return Q4_OK;

@@ -13,11 +13,15 @@
 //     the k largest of those 16 x k); at least k elements are >= T, and the elements >= T live in exactly k threads, so at most k x (elements per
 //     thread) of them exist -- usually k plus a few. They are appended to an LDS list in any order (an integer counter) and each finds its rank by
 //     counting the larger ones: rank r < k writes entry r.
+// The row form (ROWS; prompt and verify passes with q4_set_pass_logprobs on, q4_logprob_topk_rows): block r of up to PROMPT_PASS_MAX is row r -- its logits
+// `ld` halves behind row 0's, its record *pPos + r, its side copy side + r * n -- and everything between is the step's, one body: a row's record is, byte
+// for byte, what the one-block launch writes for that row alone. The halves between n and ld are neither read nor written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "q4_device.h"
 #include "q4_model.h"
 #include "logit_block.h"
+#include "prompt_pass.h"
 using namespace q4;
 
 namespace {
@@ -27,7 +31,6 @@ constexpr int LP_K = Q4_MAX_TOP_LOGPROBS;
 // LDS candidate list: k x (elements per thread) entries always fit. In registers a thread has 32 + 1 elements: 20 x 33 = 660; the looping path's list
 // fills what is left of 64 KB of static LDS (k x (8 x chunks per thread + 1) <= 6144: 311,000 logits at k = 20; the launcher refuses more)
 constexpr int LP_CAND_REG = LP_K * (LP_Q * 8 + 1), LP_CAND_LOOP = 6144;
-enum { LP_TARGET = 0, LP_GREEDY = 1, LP_SAMPLED = 2 };
 
 typedef unsigned long long u64;
 
@@ -48,10 +51,11 @@ __device__ __forceinline__ u64 wave_max_u64(u64 v) {
 // REG: n <= 32 x 1024, the thread's chunks stay in registers. mode: LP_TARGET the target token is tokens[tok_off + position] (tokens null: none),
 // LP_GREEDY token_logprob = entry 0, LP_SAMPLED the raw logits go to `side` and logprob_pick_kernel fills token_logprob behind the sampler.
 // pPos null: the stand-alone launcher (record 0); else record *pPos of rings with `cap` records -- a position outside them writes nothing.
-template <bool REG>
+// ROWS: the row form of the header -- block r reads logits + r * ld and stands at position (*pPos, or 0) + r; nothing else differs.
+template <bool REG, bool ROWS = false>
 __global__ void __launch_bounds__(LB_T) logprob_topk_kernel(const q4_half* __restrict__ logits, int n, int top_k, int mode, const int* tokens, int tok_off,
                                                             const int* pPos, int cap, float* lse_out, float* tlp_out, int* top_ids, float* top_lps,
-                                                            q4_half* __restrict__ side) {
+                                                            q4_half* __restrict__ side, int ld) {
     constexpr int LP_CAND = REG ? LP_CAND_REG : LP_CAND_LOOP;
     __shared__ u64 cand[LP_CAND];
     __shared__ u64 wtop[LB_W * LP_K];
@@ -60,8 +64,12 @@ __global__ void __launch_bounds__(LB_T) logprob_topk_kernel(const q4_half* __res
     __shared__ unsigned s_count;
     __shared__ int s_top0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int pos = pPos ? *pPos : 0;
+    const int pos = (pPos ? *pPos : 0) + (ROWS ? (int)blockIdx.x : 0);
     if (pPos && (pos < 0 || pos >= cap)) return;               // (block-uniform)
+    if (ROWS) {
+        logits += (size_t)blockIdx.x * ld;
+        if (side != nullptr) side += (size_t)blockIdx.x * n;
+    }
     // the target token may sit in pinned host memory (the token ring): requested first, used last
     int target = -1;
     if (mode == LP_TARGET && tokens != nullptr && tid == 0 && tok_off + pos < Q4_MAX_SEQ_LEN) target = tokens[tok_off + pos];
@@ -224,23 +232,35 @@ __global__ void __launch_bounds__(LB_T) logprob_topk_kernel(const q4_half* __res
 }
 
 // behind the sampler launch of a sampled step: the position has advanced, the chosen token is tokens[position]; its raw logit comes from the side copy
+// ROWS (a verify pass under the sampler, behind the row form of the sampler and in front of the accept launch: the position has NOT advanced): block r is
+// row r -- record *pPos + r, the token tokens[r] (what the sampler's row form left), the side copy side + r * n.
+template <bool ROWS>
 __global__ void __launch_bounds__(64) logprob_pick_kernel(const q4_half* __restrict__ side, int n, const int* tokens, const int* pPos, int cap,
                                                           const float* lse_ring, float* tlp_ring) {
     if (threadIdx.x != 0) return;
-    const int pos = *pPos, rec = pos - 1;
-    if (rec < 0 || rec >= cap || pos >= Q4_MAX_SEQ_LEN) return;
-    const int tok = tokens[pos];
+    const int pos = *pPos, rec = ROWS ? pos + (int)blockIdx.x : pos - 1;
+    if (rec < 0 || rec >= cap || (!ROWS && pos >= Q4_MAX_SEQ_LEN)) return;
+    const int tok = ROWS ? tokens[blockIdx.x] : tokens[pos];
+    if (ROWS) side += (size_t)blockIdx.x * n;
     tlp_ring[rec] = (tok >= 0 && tok < n) ? h2f(side[tok]) - lse_ring[rec] : __builtin_nanf("");
 }
 
+// n_rows 0: the step's one-block launch. Else the row form: n_rows blocks (1 .. PROMPT_PASS_MAX), rows `ld` halves apart (a multiple of 8: the rows stay
+// 16-byte aligned; >= n)
 int launch_topk(const q4_half* logits, int n, int top_k, int mode, const int* tokens, int tok_off, const int* pPos, int cap, float* lse, float* tlp,
-                int* top_ids, float* top_lps, q4_half* side) {
+                int* top_ids, float* top_lps, q4_half* side, int ld = 0, int n_rows = 0) {
     if (n < 1 || top_k < 0 || top_k > LP_K || top_k > n) return Q4_ERR_ARG;
+    if (n_rows && (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7))) return Q4_ERR_ARG;
     if (!logprobs_size_ok(n, top_k)) return Q4_ERR_UNSUPPORTED_SIZE;
-    if (n <= LB_T * LP_Q * 8)
-        Q4_LAUNCH(logprob_topk_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
+    const bool reg = n <= LB_T * LP_Q * 8;
+    if (n_rows && reg)
+        Q4_LAUNCH((logprob_topk_kernel<true, true>), dim3(n_rows), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side, ld);
+    else if (n_rows)
+        Q4_LAUNCH((logprob_topk_kernel<false, true>), dim3(n_rows), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side, ld);
+    else if (reg)
+        Q4_LAUNCH(logprob_topk_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side, ld);
     else
-        Q4_LAUNCH(logprob_topk_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side);
+        Q4_LAUNCH(logprob_topk_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, top_k, mode, tokens, tok_off, pPos, cap, lse, tlp, top_ids, top_lps, side, ld);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -262,7 +282,22 @@ int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_t
                        m->lp_ids, m->lp_top, m->lp_side);
 }
 int launch_logprobs_pick(const Model* m, const Config* p, RunState* s) {
-    Q4_LAUNCH(logprob_pick_kernel, dim3(1), dim3(64), 0, m->lp_side, p->vocab_size, &(s->shared_data->tokens[0]), s->pos, p->seq_len, m->lp_lse, m->lp_token);
+    Q4_LAUNCH(logprob_pick_kernel<false>, dim3(1), dim3(64), 0, m->lp_side, p->vocab_size, &(s->shared_data->tokens[0]), s->pos, p->seq_len, m->lp_lse, m->lp_token);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+// The records of a pass (prompt_pass.h, spec_verify.h): row r < n of `rows` (ld halves apart) holds the logits at position *s->pos + r, and record
+// *s->pos + r of the model's rings is what the step at that position writes. LP_TARGET: the target of row r is the ring's tokens[*s->pos + r + 1] (prompt
+// passes, scoring); LP_GREEDY: entry 0 (greedy verify passes); LP_SAMPLED: the raw rows go to the pass's side rows (Model::pass.lp_side) and
+// launch_logprobs_pick_rows fills token_logprob behind the row form of the sampler. In front of the launch that advances the position.
+int launch_logprobs_rows(const Model* m, const Config* p, RunState* s, const q4_half* rows, int ld, int n, int mode) {
+    if (!m || m->logprobs_k < 0 || !rows || (mode == LP_SAMPLED && !m->pass.lp_side)) return Q4_ERR_ARG;
+    return launch_topk(rows, p->vocab_size, m->logprobs_k, mode, &(s->shared_data->tokens[0]), 1, s->pos, p->seq_len, m->lp_lse, m->lp_token, m->lp_ids,
+                       m->lp_top, mode == LP_SAMPLED ? m->pass.lp_side : nullptr, ld, n);
+}
+int launch_logprobs_pick_rows(const Model* m, const Config* p, RunState* s, int n, const int* win) {
+    if (!m || m->logprobs_k < 0 || !m->pass.lp_side || !win || n < 1 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
+    Q4_LAUNCH(logprob_pick_kernel<true>, dim3(n), dim3(64), 0, m->pass.lp_side, p->vocab_size, win, s->pos, p->seq_len, m->lp_lse, m->lp_token);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -273,6 +308,13 @@ extern "C" int q4_logprob_topk(const q4_half* logits, int n, int top_k, const in
                                float* top_logprobs) {
     if (!logits || !lse || !target_logprob || (top_k > 0 && (!top_ids || !top_logprobs))) return Q4_ERR_ARG;
     return launch_topk(logits, n, top_k, LP_TARGET, target, 0, nullptr, 1, lse, target_logprob, top_ids, top_logprobs, nullptr);
+}
+// The row form on rows the caller holds (include/llama2_q4.h): for tests and tools. Row r is "position" r: its target targets[r], its outputs entry r
+extern "C" int q4_logprob_topk_rows(const q4_half* logits, int ld, int n, int n_rows, int top_k, const int* targets, float* lse, float* target_logprob,
+                                    int* top_ids, float* top_logprobs) {
+    if (!logits || !lse || !target_logprob || (top_k > 0 && (!top_ids || !top_logprobs))) return Q4_ERR_ARG;
+    if (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7)) return Q4_ERR_ARG;
+    return launch_topk(logits, n, top_k, LP_TARGET, targets, 0, nullptr, 1, lse, target_logprob, top_ids, top_logprobs, nullptr, ld, n_rows);
 }
 
 // the record ring: the per-model switch and the read-out (teacher-forced scoring over them: q4_loops.hip's q4_score_ids)

@@ -204,12 +204,13 @@ float q4_perplexity_ids(Transformer* t, Sampler* sampler, const int* tokens_with
     return pplx;
 }
 
-// Teacher-forced scoring through the log-probability records (q4_logprobs.hip). Not in the reference.
+// Teacher-forced scoring through the log-probability records (q4_logprobs.hip). Not in the reference. (q4_perplexity_ids above keeps its steps: the fp32
+// logits_array path is the reference's, one copy per token.)
 int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, int num_tokens, float* logprobs_out) {
     if (!t || !sampler || !tokens_with_bos || !logprobs_out || num_tokens < 1) return Q4_ERR_ARG;
     Config* config = &t->config;
     RunState* state = &t->state;
-    const Model* m = model_of(state);
+    Model* m = model_of(state);
     if (!m || num_tokens > config->seq_len - 1) return Q4_ERR_ARG;
     const int before = m->logprobs_k;
     if (before < 0) Q4_TRY(q4_set_logprobs(t, 0));
@@ -217,8 +218,19 @@ int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, i
     int rc;
     for (int attempt = 0;; attempt++) {
         rc = q4_reset_sequence(state, tokens_with_bos, num_tokens + 1);
-        // every input token is known: the steps go out like generate()'s prompt steps (a target is the NEXT ring entry), up to Q4_MULTI_STEPS per replay
+        // every input token is known: the steps go out like generate()'s prompt steps (a target is the NEXT ring entry), up to Q4_MULTI_STEPS per replay.
+        // q4_set_pass_logprobs: where a prompt pass is admitted it takes up to PROMPT_PASS_MAX positions on one read of the weights and leaves their records
+        // and the last one's logits (prompt_pass.h); every position of this call is prompt-only, so a pass may include the last. One coin per position, as the
+        // steps draw them. The redo after a time-out runs at fusion level 1: steps.
         for (int pos = 0; pos < num_tokens && !rc;) {
+            const int np = m->pass_logprobs ? prompt_pass_tokens(t, m, sampler, pos, num_tokens + 1, num_tokens, 0) : 0;
+            if (np >= 2) {
+                for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
+                rc = run_prompt_pass(config, state, &t->weights, m, pos, np);
+                g_prompt_passes++;
+                pos += np;
+                continue;
+            }
             const int k = q4_steps_that_fit(pos, num_tokens + 1, num_tokens, config, sampler);
             rc = q4_run_transformer_steps(pos, k, 0, config, state, &t->weights, 0, sampler);
             pos += k;

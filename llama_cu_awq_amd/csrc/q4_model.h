@@ -10,8 +10,9 @@
 namespace q4 {
 
 // The scratch of the prompt and verify passes (prompt_pass.h, spec_verify.h), each allocation made on first use and released by pass_release. slab: the rows x / q / xb
-// / hb, their positions and the attention launch's sink (u32x2v granules); records: the split passes' flash-decode records; logit_rows: the verify pass's logits and tokens
-struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; };
+// / hb, their positions and the attention launch's sink (u32x2v granules); records: the split passes' flash-decode records; logit_rows: the logits of a verify pass or of a
+// prompt pass with records (pass_logit_rows) and the tokens behind them; lp_side: [PROMPT_PASS_MAX][vocab] raw rows of a verify pass under the sampler with records (pass_side_rows)
+struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; q4_half* lp_side; };
 // every Transformer owns two HBM slabs (weights, run state) instead of ~750 small allocations: layers sit
 // back to back in HBM in the order the token loop streams them. ONE record per model: q4_build_transformer registers it as soon as its
 // first allocation exists, q4_free_transformer is the only place that releases and forgets it.
@@ -40,6 +41,7 @@ struct Model {
     int* lp_ids = nullptr;          // [seq_len][K]
     float* lp_top = nullptr;        // [seq_len][K]
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
+    bool pass_logprobs = false;     // q4_set_pass_logprobs: prompt and verify passes (and q4_score_ids through prompt passes) also while the records are on
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
     const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model
     int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)
@@ -88,9 +90,14 @@ bool any_stage_on(const Sampler* sampler, const Model* m);        // a logit sta
 int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out);   // the graph bin of a step whose sequence length is seq_len: its index, and its size
 // q4_logprobs.hip. The record launch of a step (in front of the sampler: reads the position before it advances) and the chosen token's look-up behind
 // the sampler of a sampled step
+// ... and of a pass with q4_set_pass_logprobs on: the row form of both, one block per row of the pass's logits (their comments there). The modes of the
+// record launch: the target is the ring's next token (prompt steps), entry 0 (greedy generating steps), or looked up behind the sampler
+enum { LP_TARGET = 0, LP_GREEDY = 1, LP_SAMPLED = 2 };
 bool logprobs_size_ok(int n, int top_k);
 int launch_logprobs_step(const Model* m, const Config* p, RunState* s, int gen_token, bool greedy);
 int launch_logprobs_pick(const Model* m, const Config* p, RunState* s);
+int launch_logprobs_rows(const Model* m, const Config* p, RunState* s, const q4_half* rows, int ld, int n, int mode);
+int launch_logprobs_pick_rows(const Model* m, const Config* p, RunState* s, int n, const int* win);
 // A logit stage: ONE launch that rewrites a generating step's fp16 logits in place, between the record launch and the argmax / sampler. What it reads
 // sits in a small device block whose address -- and nothing else of the stage -- a captured graph holds. m is null for a RunState the
 // library did not build.

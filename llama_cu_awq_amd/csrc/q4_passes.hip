@@ -53,12 +53,19 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // what it leaves out: the switch on; the fusion level in force >= 3 with an attention form the pass reproduces at every position it touches
 // (pass_attention_plan: the V-slice forms 5 / 6, or one split-context form 4 / 2 / 3) -- so never the level-1 redo after a time-out --; the geometry
 // prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps`, below the bound of q4_set_pass_context and inside
-// the bin of `pos`; no log-probability records (they describe prompt steps' logits); neither the guide nor the adaptive truncation on (their state by
-// position is put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.)
+// the bin of `pos`; no log-probability records (they describe prompt steps' logits) or q4_set_pass_logprobs on (pass_records_ok: the pass then runs the
+// classifier and writes the records); neither the guide nor the adaptive truncation on (their state by
+// position is put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.) q4_score_ids asks too, with that
+// switch on: there every position is prompt-only (num_prompt_tokens = steps + 1).
+// Records and passes: records off, nothing to ask. On, a pass is taken only with the model's q4_set_pass_logprobs switch on and a shape that the pass's
+// classifier (a prompt pass then runs the verify pass's) and the row form of the record launch take.
+static bool pass_records_ok(const Config* p, const Model* m) {
+    return m->logprobs_k < 0 || (m->pass_logprobs && verify_cls_covers(p->dim, p->vocab_size) && logprobs_size_ok(p->vocab_size, m->logprobs_k));
+}
 static int g_prompt_ingest = PROMPT_PASS_MAX;
 int g_prompt_passes = 0;
 int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int num_prompt_tokens, int steps, int off) {
-    if (g_prompt_ingest < 2 || g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0) return 0;
+    if (g_prompt_ingest < 2 || g_fusion < 3 || off != 0 || !m || !pass_records_ok(&t->config, m)) return 0;
     const Config* p = &t->config;
     int n = num_prompt_tokens - 1 - pos;
     if (n > g_prompt_ingest) n = g_prompt_ingest;
@@ -72,16 +79,17 @@ int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* samp
 
 // A verify pass (spec_verify.h) at position `pos` with n_draft drafts, positions pos .. pos + n_draft: what a prompt pass requires -- the
 // fusion level in force >= 3 with an attention form the pass reproduces at every position (pass_attention_plan), prompt_pass_covers' geometry (fp16 cache,
-// unmasked stream), no log-probability records, no guide, no context-shift offset, every position inside the bin of `pos`, below the bound of
+// unmasked stream), no log-probability records or q4_set_pass_logprobs on (pass_records_ok), no guide, no context-shift offset, every position inside the bin of `pos`, below the bound of
 // q4_set_pass_context and inside seq_len -- plus a classifier shape the pass's launch
 // takes. A token loop adds (sampler non-null): temperature 0 -- or, with the model's spec_sampled switch on, a sampler the row form of the sampling
 // launches takes (sample_rows_covers) --, no logit stage on, every position inside `steps`. With all of that off a greedy generating
 // step leaves, by position: its K / V rows, ring[pos + 1], the two position words; and, not by position: RunState::logits, RunState::x (un-normalised
 // behind the strips classifier; what the pass writes), the scratch vectors xb / hb / q / att (rewritten by every step before it reads them), the hand-off
 // epoch (never rewound; a pass does not advance it, as a prompt pass does not), the screen's tallies (q4_screen_candidates counts screened steps: a pass
-// screens nothing). Guide states, Mirostat's mu, record rings, the coin ring and logits_array are written only by what the admission excludes.
+// screens nothing). Guide states, Mirostat's mu, the coin ring and logits_array are written only by what the admission excludes; the record rings by the
+// pass itself where q4_set_pass_logprobs admits it with records on (spec_verify.h: records p .. p + D, those of rejected drafts at or above the position).
 bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off) {
-    if (g_fusion < 3 || off != 0 || !m || m->logprobs_k >= 0 || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
+    if (g_fusion < 3 || off != 0 || !m || !pass_records_ok(&t->config, m) || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
     const Config* p = &t->config;
     if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps) return false;
     if (sampler && sampler->temperature != 0.0f) {
@@ -229,6 +237,17 @@ int q4_set_speculative_sampled(Transformer* t, int on) {
     if (!m) return Q4_ERR_ARG;
     m->spec_sampled = on != 0;
     return Q4_OK;
+}
+// Passes while the log-probability records are on (q4_set_logprobs): per model, off by default. No captured graph contains a pass: nothing to drop.
+int q4_set_pass_logprobs(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->pass_logprobs = on != 0;
+    return Q4_OK;
+}
+int q4_get_pass_logprobs(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->pass_logprobs ? 1 : 0;
 }
 int q4_get_speculative_sampled(const Transformer* t) {
     const Model* m = t ? model_of(&t->state) : nullptr;

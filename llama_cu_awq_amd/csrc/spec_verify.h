@@ -16,6 +16,12 @@
 // place with its own position's coin, exactly as the step at that position would (the row form of the two sampler launches, q4_sampling.hip), and the
 // accept launch takes those tokens instead of the rows' argmax: the leading drafts that equal the sampled tokens are accepted, RunState::logits receives
 // row m's fp16 probabilities -- what the sampled step leaves there --, and the run is the run without passes for that seed, byte for byte.
+//
+// With log-probability records on (admitted only with q4_set_pass_logprobs on): the row form of the record launch (q4_logprobs.hip) goes between the
+// classifier and the accept launch -- greedy: a row's token_logprob is entry 0 of its top order; under the sampler: the raw rows go to the pass's side rows
+// in front of the sampler's row form and a row form of the look-up fills token_logprob behind it from the rows' tokens. Records p .. p + m are what m + 1
+// steps write. Records p + m + 1 .. p + D describe rejected drafts: they lie at or above the device position and are rewritten by whatever runs there
+// next -- the same contract as the K / V rows of rejected drafts.
 #pragma once
 #include "prompt_pass.h"
 

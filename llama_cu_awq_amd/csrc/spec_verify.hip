@@ -1,5 +1,6 @@
 // spec_verify.hip -- the verify pass of speculative greedy decoding (spec_verify.h): an embedding launch (row 0 from the ring, rows
 // 1 .. D from the drafts in the kernel argument), the prompt pass's layer loop, the classifier for all rows on one read of wcls, the accept launch.
+// With log-probability records on (q4_set_pass_logprobs): the row form of the record launch behind the classifier (run_verify_pass).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <math.h>
@@ -214,19 +215,23 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, M
     const int dim = p->dim, n = n_draft + 1;
     Q4_TRY(prompt_pass_rows(m, p));
     const PassScratch& rows = m->pass;
-    // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
-    if (!m->pass.logit_rows && hipMalloc((void**)&m->pass.logit_rows, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half) + PROMPT_PASS_MAX * sizeof(int)) != hipSuccess) {
-        (void)hipGetLastError(); m->pass.logit_rows = nullptr; return Q4_ERR_ALLOC;
-    }
+    const bool records = m->logprobs_k >= 0;                 // (admitted with records on: q4_set_pass_logprobs, q4_passes.hip)
+    if (records && !m->pass_logprobs) return Q4_ERR_ARG;
+    Q4_TRY(pass_logit_rows(m, p));                           // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
+    if (records && sampler) Q4_TRY(pass_side_rows(m, p));
     Q4_LAUNCH(verify_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, rows.x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens, d,
               (const int*)s->pos, rows.pos);
     Q4_LAUNCH_CHECK();
     Q4_TRY(prompt_pass_layers(p, s, w, m, pos0, n));
     Q4_TRY(launch_verify_cls(rows.logit_rows, rows.x, w->rms_final_weight, w->wcls, dim, p->vocab_size, n));
+    // Records p .. p + D, in front of the accept launch (it advances the position): a greedy row's token_logprob is entry 0; under the sampler the raw rows go
+    // aside in front of the sampler's row form, which normalises them in place, and the rows' tokens are looked up behind it -- the order of the sampled step
+    if (records) Q4_TRY(launch_logprobs_rows(m, p, s, rows.logit_rows, p->vocab_size, n, sampler ? LP_SAMPLED : LP_GREEDY));
     int* win = nullptr;
     if (sampler) {      // each row sampled in place with its own position's coin, as the step at that position would; then the accept on those tokens
         win = reinterpret_cast<int*>(rows.logit_rows + (size_t)PROMPT_PASS_MAX * p->vocab_size);
         Q4_TRY(launch_sample_rows(sampler, rows.logit_rows, p->vocab_size, n, coins, s->pos, win));
+        if (records) Q4_TRY(launch_logprobs_pick_rows(m, p, s, n, win));
     }
     return launch_verify_accept(rows.logit_rows, p->vocab_size, p->vocab_size, d, win, rows.x, dim, s->logits, s->x, (int*)s->shared_data->tokens, &(s->shared_data->pos),
                                 s->pos, nullptr);
