@@ -59,11 +59,15 @@ GEOMETRIES = {
     # thread, 40000 = the global-memory fallback (> 32 x 1024 entries)
     "v32k": (64, 96, 1, 2, 2, 32000, 32, 10000.0),
     "v40k": (64, 96, 1, 2, 2, 40000, 32, 10000.0),
+    # Llama-3's vocabulary: four loop runs of the global-memory form, token ids above 65535 (nothing on the logit side may keep an id in 16 bits)
+    "v128k": (64, 96, 1, 2, 2, 128256, 32, 10000.0),
     # the classifier's strips launch (dim 4096 / 5120, >= 64 vocabulary rows per CU) with the greedy sampler as its epilogue, on a
     # one-layer body: a vocabulary that splits evenly over 256 CUs and one that does not
     "cls4096": (4096, 1408, 1, 32, 32, 32000, 300, 10000.0),
     "cls5120": (5120, 1408, 1, 40, 40, 20000, 300, 10000.0),
     "cls4096_ragged": (4096, 1408, 1, 32, 32, 16600, 300, 10000.0),
+    # cls4096's one-layer body (grouped-query 4:1) with the Llama-3 classifier: 128256 rows x 4096, embedding rows beyond 2^29 bytes (a 2.1 GB file)
+    "cls128k": (4096, 1408, 1, 32, 8, 128256, 300, 500000.0),
     # the FFN half of a layer as one launch (csrc/gemv_ffn_pair.h, fusion level 4): Llama-2-7B's dim / hidden at two layers; a hidden size that
     # splits raggedly over 256 CUs (20.5 column pairs per CU; a last k-slot of 36 units); and the widest the launch's LDS holds (22 pairs, 48)
     "ffn_pair7b": (4096, 11008, 2, 32, 32, 512, 300, 10000.0),
@@ -74,6 +78,9 @@ GEOMETRIES = {
     # prompt and verify passes in the split-context bins (q4_set_pass_context): Llama-2-7B's layer twice with a context of 2304 -- positions 2048 .. 2303
     # run in graph bin 4096 (sixteen 256-position chunks: the records' merge takes its two-round branch); the records scratch holds 18 chunks per head
     "pass_long": (4096, 11008, 2, 32, 32, 512, 2304, 10000.0),
+    # the Mistral-7B / Llama-3-8B layer, twice: 32 query heads over 8 K / V heads (kv_mul 4) at head 128, hidden 14336 (gate / up and down as strips),
+    # pass_long's context -- every graph bin up to 4096 with grouped-query attention at width 4096 (tests/test_gqa7b_gpu.py)
+    "gqa7b_pair": (4096, 14336, 2, 32, 8, 512, 2304, 500000.0),
 }
 
 

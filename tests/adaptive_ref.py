@@ -128,7 +128,9 @@ def expect_from_record(x16, rec, temperature=1.0):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # what the op-level tests and the parity measurement share
-SIZES = (1, 7, 64, 1000, 8192, 32768, 32776, 32000, 32779)      # (32779: the looping form with tail elements)
+# (32779: the looping form with tail elements; 128256 / 128259: Llama-3's vocabulary and one with tail elements -- sixteen loop runs, ids beyond 16 bits)
+SIZES = (1, 7, 64, 1000, 8192, 32768, 32776, 32000, 32779, 128256, 128259)
+HIGH = 65536                     # a size above it: the entries below this id lie 40 under the others, so the maximum, its ties and whatever a stage keeps sit at ids >= HIGH
 # (name, controls, temperature): every stage alone, typical-p at two masses, everything together (top-n-sigma wide enough to leave a distribution)
 CONFIGS = (
     ("top-n-sigma 1", dict(top_n_sigma=1.0), 1.0),
@@ -144,8 +146,9 @@ def inputs(n):
     (every deviation is one of two: the ties sit at the boundary)"""
     rng = np.random.default_rng(9100 + n)
     out = [("normal x1", rng.standard_normal(n).astype(np.float16)), ("normal x8", (rng.standard_normal(n) * 8.0).astype(np.float16))]
+    lo = HIGH if n > HIGH else 0
     hot = np.zeros(n, dtype=np.float16)
-    hot[n // 3] = 30.0
+    hot[100003 if lo else n // 3] = 30.0
     out.append(("one-hot", hot))
     out.append(("all equal", np.full(n, -1.25, dtype=np.float16)))
     holes = (rng.standard_normal(n) * 2.0).astype(np.float16)
@@ -154,6 +157,8 @@ def inputs(n):
     out.append(("-inf and NaN", holes))
     two = np.where(rng.random(n) < 0.25, 2.0, 0.5).astype(np.float16)
     out.append(("two values", two))
+    for _, x in out:
+        x[:lo] = (x[:lo].astype(F) - F(40.0)).astype(np.float16)
     return out
 
 

@@ -41,6 +41,17 @@ def round_trip(x, head_size):
     return dequantise(*quantise(x, head_size), head_size)
 
 
+def step(a, head_size):
+    """the spacing of the row's FP8 grid at each element of the round-tripped fp16 array a [..., n * head_size]: 2^e times e4m3's spacing at the scaled
+    magnitude (2^(floor(log2 m) - 3) from 2^-6 on, 2^-9 below)"""
+    _, e = quantise(a, head_size)
+    scale = np.repeat(2.0 ** e.astype(np.float64), head_size, axis=-1)
+    m = np.abs(np.asarray(a, dtype=np.float64)) / scale
+    with np.errstate(divide="ignore"):
+        ex = np.where(m >= 2.0 ** -6, np.floor(np.log2(np.maximum(m, 2.0 ** -6))), -6.0)
+    return scale * 2.0 ** (ex - 3.0)
+
+
 class Forward:
     """run_llama_network composed from the oracle's per-op functions over a checkpoint file; round_trip=True replaces each K / V row by
     its FP8 round trip before the row enters the cache. With round_trip=False it equals oracle.Model.forward bit for bit."""
@@ -60,10 +71,14 @@ class Forward:
         self.kc = np.zeros((layers, seq_len, self.kv_dim), dtype=np.float16)
         self.vc = np.zeros((layers, seq_len, self.kv_dim), dtype=np.float16)
 
-    def forward(self, token, pos):
+    def forward(self, token, pos, rows=None):
+        """rows: (K [layers, kv_dim], V [layers, kv_dim]) fp16 that enter the cache at `pos` in place of the rows computed here -- the step from another
+        evaluation's cache (a row that rounds to the other FP8 neighbour there is then no part of the difference). self.own then holds the rows
+        computed here at this position, (K, V) [layers, kv_dim], for the caller to compare."""
         dim, hidden, layers, heads, kv_heads, vocab, seq_len, theta = self.cfg
         hs, kv_dim, orc = dim // heads, self.kv_dim, oracle
         x = np.array(self.emb[token], dtype=np.float16)
+        self.own = (np.zeros((layers, kv_dim), dtype=np.float16), np.zeros((layers, kv_dim), dtype=np.float16))
         for l, L in enumerate(self.layers):
             xb = orc.rmsnorm(x, L["rms_att"])
             q = orc.matmul_q4(xb, *L["q"], dim, dim)
@@ -72,6 +87,9 @@ class Forward:
             q, k = orc.rope(q, k, heads, kv_heads, hs, pos, theta)
             if self.rt:
                 k, v = round_trip(k, hs), round_trip(v, hs)
+            self.own[0][l], self.own[1][l] = k, v
+            if rows is not None:
+                k, v = rows[0][l], rows[1][l]
             self.kc[l, pos], self.vc[l, pos] = k, v
             xb, _ = orc.attention(q, self.kc[l].reshape(-1), self.vc[l].reshape(-1), heads, hs, heads // kv_heads, pos,
                                   max_seq_len=orc.lib().orc_seq_len_bin(pos, seq_len))

@@ -23,8 +23,10 @@ F = np.float32
 NINF = float("-inf")
 T_THREADS, MAX_E = 1024, 32
 
-# the vocabulary sizes both test modules run: E = ceil(n / 1024) is 1, 1, 1, 1, 2, 8, 16, 17, 20, 32, 32, 32, 33, 40
-SIZES = (64, 1000, 1001, 1024, 2048, 8192, 16384, 16392, 20000, 32000, 32003, 32768, 32776, 40000)
+# the vocabulary sizes both test modules run: E = ceil(n / 1024) is 1, 1, 1, 1, 2, 8, 16, 17, 20, 32, 32, 32, 33, 40, 126, 126 (Llama-3's vocabulary and
+# one that is no multiple of eight: the global-memory form's loops run four times, and token ids pass 16 bits)
+SIZES = (64, 1000, 1001, 1024, 2048, 8192, 16384, 16392, 20000, 32000, 32003, 32768, 32776, 40000, 128256, 128259)
+HIGH = 65536                                                     # a size above it: every finite logit sits at an id >= HIGH, so every token that can be drawn does
 SUPPORTS = (1, 2, 3, 40, 64, 65, 500, 1000, 1024, 1025, 1500, 2048, 2049, 3000, 4096, 4097, 6000)      # ... and n itself
 SETTINGS = ((0.8, 0.9), (0.5, 0.6), (1.0, 1.0))                  # (temperature, topp)
 TIED = (1030, 2050, 4100)                                        # equal entries that straddle a band's 1024, a cut's 2048 and its 4096
@@ -103,9 +105,15 @@ def _fill(rng, kind, k):
     return rng.standard_normal(k) * (0.3 if kind == "x0.3" else 2.0)
 
 
+def low_id(n):
+    """the least id a finite logit has at this size"""
+    return HIGH if n > HIGH else 0
+
+
 def _holed(rng, n, k, values):
     x = np.full(n, NINF, dtype=np.float16)
-    x[rng.choice(n, size=k, replace=False)] = np.asarray(values, dtype=np.float16)
+    lo = low_id(n)
+    x[lo + rng.choice(n - lo, size=k, replace=False)] = np.asarray(values, dtype=np.float16)
     return x
 
 
@@ -201,16 +209,18 @@ def cases(n, round_=0):
         for T, topp in SETTINGS:
             out.append(("%s, T %g topp %g" % (name, T, topp), x, T, topp, ANY_COIN))
 
-    for k in sorted(set(s for s in SUPPORTS if s <= n) | {n}):
+    lo = low_id(n)
+    for k in sorted(set(s for s in SUPPORTS if s <= n - lo) | {n - lo}):
         for kind in ("equal", "x0.3", "x2"):
             add("support %d %s" % (k, kind), _holed(rng, n, k, _fill(rng, kind, k)))
     for k in TIED:
-        if k <= n:
+        if k <= n - lo:
             add("%d tied" % k, _holed(rng, n, k, np.zeros(k)))
     x = (rng.standard_normal(n) * 2.0).astype(np.float16)
     x[rng.random(n) < 0.1] = NINF
+    x[:lo] = NINF
     if not np.isfinite(x.astype(F)).any():
-        x[0] = 0.0
+        x[lo] = 0.0
     add("dense normal x2, 10 % holes", x)
     return out
 

@@ -94,7 +94,7 @@ def _check(what, x, got, rec, c, temperature, chain=None, pos=0, tok=None, mu_to
 @pytest.mark.parametrize("n", ref.SIZES)
 def test_op_holds_the_threshold_contract(q4, n):
     op = Op(q4, n)
-    launches = 0
+    launches = highest = 0
     for name, x in ref.inputs(n):
         for cname, c, t in ref.CONFIGS:
             what = "n %d, %s, %s" % (n, name, cname)
@@ -102,6 +102,13 @@ def test_op_holds_the_threshold_contract(q4, n):
             got, rec = op.launch(x, c, t)
             mu, side = op.mu.get(F, op.positions), op.side.get(F, n + 2)
             _check(what, x, got, rec, c, t)
+            if n > ref.HIGH:                                     # beyond 16 bits of id: on the mask the recorded thresholds give (the reference's answer)
+                stays = np.flatnonzero(np.isfinite(ref.expect_from_record(x, rec, t)[0].astype(F)))
+                v = x.astype(F)
+                if stays.size < int(np.isfinite(v).sum()):       # (a Mirostat span's first position masks nothing: then only the maximum decides)
+                    assert stays.size and stays.min() >= ref.HIGH, (what, stays[:4])
+                    highest = max(highest, int(stays.max()))
+                assert np.flatnonzero(v == np.nanmax(v)).min() >= ref.HIGH, what
             if c.get("mirostat_tau", 0) > 0:                     # a span starts: 2 * tau, written to the ring; the side buffer is w of what stayed
                 assert rec["mu"] == F(2.0) * F(c["mirostat_tau"]) and mu[0] == rec["mu"] and np.isnan(mu[1:]).all(), what
                 if np.isfinite(got.astype(F)).any():
@@ -117,6 +124,7 @@ def test_op_holds_the_threshold_contract(q4, n):
             assert again.tobytes() == got.tobytes() and all(np.array_equal(np.array(rec[k]), np.array(rec2[k]), equal_nan=True) for k in rec), what
             launches += 1
     assert launches == 30
+    assert n <= ref.HIGH or highest > 98304, highest
 
 
 def test_op_without_mirostat_needs_no_state(q4):

@@ -38,20 +38,26 @@ def _want(q4, x, ring, pos, c, breakers=()):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 1. the op against the reference
+HIGH = 65536
+
+
 def _cases(n):
     """(name, ring, pos, controls, breakers, logits, must_touch) -- every ring holds a few entries behind pos, which the launch must not read into the
-    window. Token 0 is in range for every n; `b` and `c` are in range where the vocabulary has them and plain ints outside it elsewhere."""
+    window. Token z = 0 is in range for every n; `b` and `c` are in range where the vocabulary has them and plain ints outside it elsewhere. A vocabulary
+    beyond 16 bits of token id (n > 65536) runs the same cases on z, b, c = 100003, 70001, 128255: every ring token in range, every breaker and every
+    touched entry then has an id >= 65536."""
     rng = np.random.default_rng(7000 + n)
-    b, c, X = (1 if n >= 2 else n + 9), (2 if n >= 3 else n + 11), n + 5
+    z = 100003 if n > HIGH else 0
+    b, c, X = (70001, 128255, n + 5) if z else ((1 if n >= 2 else n + 9), (2 if n >= 3 else n + 11), n + 5)
     length = 5004
 
     def periodic(vals):
         return np.tile(np.array(vals, dtype=np.int64), length // len(vals) + 1)[:length].astype(np.int32)
 
-    per3, one = periodic([0, b, c]), np.zeros(length, dtype=np.int32)     # per3[p] == c and the next token is 0 wherever p % 3 == 2
+    per3, one = periodic([z, b, c]), np.full(length, z, dtype=np.int32)   # per3[p] == c and the next token is z wherever p % 3 == 2
     a2 = rng.integers(0, 2, length).astype(np.int32)
-    if n < 2:
-        a2[a2 == 1] = b
+    if n < 2 or z:
+        a2 = np.where(a2 == 1, b, z).astype(np.int32)
     out = []
 
     def add(name, ring, pos, breakers=(), touch=True, x=None, **over):
@@ -74,18 +80,18 @@ def _cases(n):
     add("last_n 4096, alphabet 2", a2, 5000, last_n=4096)
     add("alphabet 2, ban 3 and DRY", a2, 301, last_n=64, no_repeat_ngram_size=3)
     # ids outside [0, n): as the last token, inside a match, as the next token (one flaw makes one candidate's next token valid)
-    add("outside: the last token", periodic([0, b, X]), 200)
-    add("outside: inside the match", periodic([0, X, b]), 200)
-    flawed = periodic([0, b, X])
-    flawed[8] = 0
+    add("outside: the last token", periodic([z, b, X]), 200)
+    add("outside: inside the match", periodic([z, X, b]), 200)
+    flawed = periodic([z, b, X])
+    flawed[8] = z
     add("outside: the next token", flawed, 199)
-    add("outside: huge ids", periodic([0, 2 ** 31 - 1, -2 ** 31]), 200)
+    add("outside: huge ids", periodic([z, 2 ** 31 - 1, -2 ** 31]), 200)
     # breakers: the last token itself; at distance 1, 2 and 64 (a token of its own in a ring of zeros: R is exactly the distance; a vocabulary of one
     # token has no second id that could be that breaker)
-    add("breaker at p", one, 1500, breakers=[0], touch=False)
+    add("breaker at p", one, 1500, breakers=[z], touch=False)
     if n >= 2:
-        many = list(range(1, min(n, 700)))
-        for d, allowed, ids in ((1, 1, [1]), (2, 2, many), (64, 5, [1])):
+        many = list(range(z + 1, min(n, z + 700)))
+        for d, allowed, ids in ((1, 1, [b]), (2, 2, many), (64, 5, [b])):
             ring = one.copy()
             ring[1500 - d] = ids[-1]
             add("breaker at distance %d" % d, ring, 1500, breakers=ids, allowed_length=allowed)
@@ -101,10 +107,10 @@ def _cases(n):
             add("ngram %d multiplier %g" % (ngram, multiplier), per3, 1499, no_repeat_ngram_size=ngram, multiplier=multiplier,
                 touch=bool(ngram or multiplier))
     add("ngram 65, a match of 62", per3[4936:], 64, no_repeat_ngram_size=65, multiplier=0.0, touch=False)
-    # touched logits among -inf, +inf, NaN, +-65504, -0 (the touched token of per3 at p % 3 == 2 is 0)
+    # touched logits among -inf, +inf, NaN, +-65504, -0 (the touched token of per3 at p % 3 == 2 is z)
     for v in (-np.inf, np.inf, np.nan, 65504.0, -65504.0, -0.0):
         x = (rng.standard_normal(n) * 3.0).astype(np.float16)
-        x[0] = v
+        x[z] = v
         add("touched %r" % v, per3, 1499, x=x)
         add("touched %r, base 4" % v, per3, 1499, x=x, base=4.0)
         add("banned %r" % v, per3, 1499, x=x, no_repeat_ngram_size=2)
@@ -118,11 +124,11 @@ def _apply(q4, dl, x, dr, dp, ctl, breakers):
     return dl.get(np.float16, x.shape[0])
 
 
-@pytest.mark.parametrize("n", [1, 8, 1027, 32000, 40000])
+@pytest.mark.parametrize("n", [1, 8, 1027, 32000, 40000, 128256, 128259])
 def test_op_matches_the_reference_bit_for_bit(q4, n):
     dl, dp = q4.DevBuf(nbytes=2 * n), q4.DevBuf(nbytes=4)
     rings = {}
-    touched_cases = 0
+    touched_cases = highest = 0
     for name, ring, pos, ctl, breakers, x, must_touch in _cases(n):
         what = "n %d, %s" % (n, name)
         if id(ring) not in rings:
@@ -136,10 +142,15 @@ def test_op_matches_the_reference_bit_for_bit(q4, n):
         untouched = np.setdiff1d(np.arange(n), touched)
         assert _bits(got)[untouched].tobytes() == _bits(x)[untouched].tobytes(), what + ": an untouched entry changed"
         assert bool(touched) == must_touch, "%s: the reference touched %s" % (what, touched)
+        if n > HIGH:                                                   # beyond 16 bits of id: what the reference touches, the breakers, the ring's ids in range
+            assert all(t >= HIGH for t in touched) and all(t >= HIGH for t in breakers), (what, touched)
+            assert ((ring >= HIGH) | (ring < 0) | (ring >= n)).all(), what
+            highest = max([highest] + [int(t) for t in touched])
         again = _apply(q4, dl, x, rings[id(ring)][1], dp, ctl, breakers)
         assert again.tobytes() == got.tobytes(), what + ": a second launch gave other bytes"
         touched_cases += bool(touched)
     assert touched_cases >= 40
+    assert n <= HIGH or highest > 98304, highest
 
 
 def test_op_argument_errors_leave_the_logits_alone(q4):

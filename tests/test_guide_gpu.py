@@ -19,18 +19,21 @@ SPECIALS = np.array([0x8000, 0x7C00, 0xFC00, 0x7E01, 0xFFFF, 0x7D55, 0x0000, 0xF
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 1. the op against the reference
-def _row(rng, kind, n, S):
-    """one row of a table: live entries are random states"""
+HIGH = 65536          # a vocabulary beyond 16 bits of token id: every live token and every ring token in range sits at an id >= HIGH
+
+
+def _row(rng, kind, n, S, lo=0):
+    """one row of a table: live entries are random states. lo: no live entry below this id"""
     live = np.zeros(n, dtype=bool)
     if kind == "all":
-        live[:] = True
+        live[lo:] = True
     elif kind == "one":
-        live[int(rng.integers(n))] = True
+        live[lo + int(rng.integers(n - lo))] = True
     elif kind == "last":
         live[n - 1] = True
     else:
-        live = rng.random(n) < 0.5
-        live[int(rng.integers(n))] = True                        # (never empty: q4_guide_new refuses a state nothing leaves)
+        live[lo:] = rng.random(n - lo) < 0.5
+        live[lo + int(rng.integers(n - lo))] = True              # (never empty: q4_guide_new refuses a state nothing leaves)
     row = np.full(n, DEAD, dtype=np.uint16)
     row[live] = rng.integers(0, S, int(live.sum())).astype(np.uint16)
     return row
@@ -39,11 +42,11 @@ def _row(rng, kind, n, S):
 KINDS = ("half", "one", "last", "all")
 
 
-def _tables(rng, n):
+def _tables(rng, n, lo=0):
     """(name, table): S = 1 with each kind of row, S = 3, S = 300 with the kinds taking turns"""
-    out = [("S 1 " + k, _row(rng, k, n, 1)[None, :]) for k in KINDS]
+    out = [("S 1 " + k, _row(rng, k, n, 1, lo)[None, :]) for k in KINDS]
     for S in (3, 300):
-        out.append(("S %d" % S, np.stack([_row(rng, KINDS[r % 4], n, S) for r in range(S)])))
+        out.append(("S %d" % S, np.stack([_row(rng, KINDS[r % 4], n, S, lo) for r in range(S)])))
     return out
 
 
@@ -54,12 +57,12 @@ def _logits(rng, n):
     return x
 
 
-def _rings(rng, table):
+def _rings(rng, table, lo=0):
     """(name, state ring, token ring, p): one crafted pair of rings per transition case"""
     S, n = table.shape
     out = []
     junk = lambda k: rng.integers(-5, S + 5, k).astype(np.int32)
-    toks = lambda k: rng.integers(0, n, k).astype(np.int32)
+    toks = lambda k: rng.integers(lo, n, k).astype(np.int32)
     out.append(("p = 0", junk(4), toks(4), 0))
     st = junk(8)
     st[4] = NONE
@@ -74,7 +77,7 @@ def _rings(rng, table):
         dead = np.nonzero(table[prev] == DEAD)[0]
         if dead.size:
             st, tk = junk(9), toks(9)
-            st[6], tk[7] = prev, int(rng.choice(dead))
+            st[6], tk[7] = prev, int(rng.choice(dead[dead >= lo] if (dead >= lo).any() else dead))
             out.append(("forbidden token", st, tk, 7))
             break
     for name, t in (("t < 0", -1), ("t = -2^31", -2 ** 31), ("t = V", n), ("t > V", n + 9), ("t = 2^31 - 1", 2 ** 31 - 1)):
@@ -90,15 +93,21 @@ def _rings(rng, table):
     return out
 
 
-@pytest.mark.parametrize("n", [1, 8, 1000, 1027, 32000, 32768, 32776, 40000])
+@pytest.mark.parametrize("n", [1, 8, 1000, 1027, 32000, 32768, 32776, 40000, 128256, 128259])
 def test_op_matches_the_reference_bit_for_bit(q4, n):
+    """(128256 / 128259: beyond 16 bits of token id, beside the tables' 16-bit states. There every live token of every table and every ring token in
+    range has an id >= 65536, some beyond 98304: asserted on the tables, the rings and the reference's mask.)"""
     rng = np.random.default_rng(7000 + n)
+    lo = HIGH if n > HIGH else 0
     pos = q4.DevBuf(nbytes=4)
     seen_nan = [False, False]
-    for tname, table in _tables(rng, n):
+    highest = 0
+    for tname, table in _tables(rng, n, lo):
         g = q4.Guide(table)
         x = _logits(rng, n)
-        for cname, st, tk, p in _rings(rng, table):
+        if lo:
+            assert (table[:, :lo] == DEAD).all(), tname
+        for cname, st, tk, p in _rings(rng, table, lo):
             what = "n %d, %s, %s" % (n, tname, cname)
             want_st = st.copy()
             want, s = ref.mask(x, table, want_st, tk, p, seq_len=128 * 1024)
@@ -123,9 +132,15 @@ def test_op_matches_the_reference_bit_for_bit(q4, n):
                 seen_nan[0] |= bool((nan & (table[s] != DEAD)).any())
                 seen_nan[1] |= bool((nan & (table[s] == DEAD)).any())
                 assert np.array_equal(out[table[s] != DEAD], x[table[s] != DEAD]) and (out[table[s] == DEAD] == 0xFC00).all()
+                if lo:                                               # on the reference's mask: what stays is beyond 16 bits
+                    kept = np.flatnonzero(want != 0xFC00)
+                    assert kept.size == 0 or kept.min() >= lo, what
+                    assert ((tk >= lo) | (tk < 0)).all(), what
+                    highest = max(highest, int(np.flatnonzero(table[s] != DEAD).max()))
         g.close()
     if n >= 1000:
         assert seen_nan == [True, True], "no NaN in an allowed and in a forbidden slot"
+    assert not lo or highest > 98304, highest
 
 
 def test_op_arguments(q4):

@@ -138,6 +138,10 @@ def test_synth_bin_layout(tmp_path, orc):
     # sizes of the real geometries
     assert synth.model_bytes(synth.GEOMETRIES["7b"]) == 3889438752
     assert synth.model_bytes(synth.GEOMETRIES["13b"]) == 7248291872
+    # the grouped-query 7B-width pair and the Llama-3 vocabulary (tests/test_gqa7b_gpu.py, tests/test_vocab128k_gpu.py)
+    assert synth.GEOMETRIES["gqa7b_pair"] == (4096, 14336, 2, 32, 8, 512, 2304, 500000.0) and synth.model_bytes(synth.GEOMETRIES["gqa7b_pair"]) == 235053088
+    assert synth.GEOMETRIES["v128k"] == (64, 96, 1, 2, 2, 128256, 32, 10000.0) and synth.model_bytes(synth.GEOMETRIES["v128k"]) == 32854432
+    assert synth.GEOMETRIES["cls128k"] == (4096, 1408, 1, 32, 8, 128256, 300, 500000.0) and synth.model_bytes(synth.GEOMETRIES["cls128k"]) == 2132160544
 
 
 def test_product_fails_loudly_without_the_library(tmp_path, monkeypatch):

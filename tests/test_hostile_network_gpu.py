@@ -1,8 +1,8 @@
 """The fused launches (levels 3 / 4 / 5 / 6) and the launch sequences (levels 0 / 1) on the hostile checkpoints of tests/hostile_models.py:
 massive residual channels, near-one-hot attention with a sink at position 0, pinned zero points / q == z groups / scales over two decades,
 norm weights with zeros and negatives, and all of them at once. Every trait on ffn_pair7b (levels 4 / 5 / 6) and head128 (the attention ->
-o-proj launch, split context from bin 512), `combined` on head128_gqa, head128_k5120 (the shared half slot), tinyllama (head 64, one k-slot)
-and small (the unfused forms).
+o-proj launch, split context from bin 512), `combined` on head128_gqa, head128_k5120 (the shared half slot), tinyllama (head 64, one k-slot),
+small (the unfused forms) and gqa7b_pair (grouped-query 4:1 at width 4096 on sixteen-wave blocks, hidden 14336 as strips).
 
   a. a fixed token sequence (the GPU's own tokens never feed back) against the restatement: every position's logits, the K / V rows of the
      first and last position, every level and graph mode; no bounded wait may run out, every output finite
@@ -25,7 +25,7 @@ SEED = 5
 SEQ = [1, 17, 300, 45, 9, 230, 77, 401, 12, 5, 498, 64, 33, 150]     # prompt = the first 10; the last 4 are generated steps, forced
 PROMPT_LEN = 10
 F64_POSITIONS = 4
-MODELS = [(g, t) for g in ("ffn_pair7b", "head128") for t in hm.TRAITS] + [(g, "combined") for g in ("head128_gqa", "head128_k5120", "tinyllama", "small")]
+MODELS = [(g, t) for g in ("ffn_pair7b", "head128") for t in hm.TRAITS] + [(g, "combined") for g in ("head128_gqa", "head128_k5120", "tinyllama", "small", "gqa7b_pair")]
 
 # logits vs the restatement, max |d| / max(1, |logit|): the benign models' bound of tests/test_forward_gpu.py (5e-3; measured <= 1.6e-3 on massive / combined)
 # unless a hostile model measured more. Those carry 3x their measured worst case (parity_observed.json "hostile_vs_restatement"): near-one-hot softmaxes,

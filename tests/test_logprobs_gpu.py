@@ -18,18 +18,22 @@ SAMPLED = (0.8, 0.9)
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 1. the kernel on crafted logits
-def _distributions(rng, n, k):
-    """(name, fp16 logits, target) -- the target lies outside the top k wherever n allows it"""
+HIGH = 65536          # a vocabulary beyond 16 bits of token id: every entry that decides a result sits at an id >= HIGH
+
+
+def _distributions(rng, n, k, lo=0):
+    """(name, fp16 logits, target) -- the target lies outside the top k wherever n allows it. lo > 0: the same distributions with the entries below id lo
+    moved 40 down (-60000 becomes -60032; the one at +60000 is placed above lo), so the maximum, its ties, the top k + 6 and the target all have ids >= lo."""
     out = []
     for scale in (1.0, 8.0):
         out.append(("normal x%g" % scale, (rng.standard_normal(n) * scale).astype(np.float16)))
     out.append(("all equal", np.full(n, 1.5, dtype=np.float16)))
     x = rng.standard_normal(n).astype(np.float16)
-    dup = np.sort(x)[::-1][min(k, n - 1)]                       # the value at rank k: the duplicates straddle it
-    x[rng.choice(n, size=min(300, max(1, n // 2)), replace=False)] = dup
+    dup = np.sort(x[lo:])[::-1][min(k, n - lo - 1)]             # the value at rank k: the duplicates straddle it
+    x[lo + rng.choice(n - lo, size=min(300, max(1, (n - lo) // 2)), replace=False)] = dup
     out.append(("duplicates at rank k", x))
     x = np.full(n, -60000.0, dtype=np.float16)
-    x[int(rng.integers(n))] = 60000.0
+    x[int(rng.integers(lo, n))] = 60000.0
     out.append(("one at +60000", x))
     x = (rng.standard_normal(n) * 2.0).astype(np.float16)
     if n > 1:
@@ -41,6 +45,8 @@ def _distributions(rng, n, k):
     out.append(("signed zeros", x))
     res = []
     for name, x in out:
+        if lo:
+            x[:lo] = (x[:lo].astype(np.float32) - 40.0).astype(np.float16)
         order = np.lexsort((np.arange(n), -x.astype(np.float64)))
         res.append((name, x, int(order[min(n - 1, k + 5)])))
     return res
@@ -57,13 +63,17 @@ def _launch(q4, x, k, target):
     return lse.get(np.float32, 1), tlp.get(np.float32, 1), ids.get(np.int32, max(k, 1))[:k], top.get(np.float32, max(k, 1))[:k]
 
 
-@pytest.mark.parametrize("n", [1, 8, 20, 1000, 1027, 32000, 32768, 32776, 40000])
+@pytest.mark.parametrize("n", [1, 8, 20, 1000, 1027, 32000, 32768, 32776, 40000, 128256, 128259])
 def test_kernel_matches_the_reference(q4, n):
+    """(128256 / 128259: Llama-3's vocabulary and one that is no multiple of eight -- sixteen runs of the looping path per thread; q4_logprob_topk admits
+    them up to k = 47, logprobs_size_ok. Every deciding id lies beyond 16 bits there, asserted on the reference's answer.)"""
     rng = np.random.default_rng(1000 + n)
+    lo = HIGH if n > HIGH else 0
+    highest = 0
     for k in (0, 1, 5, 20):
         if k > n:
             continue
-        for name, x, target in _distributions(rng, n, k):
+        for name, x, target in _distributions(rng, n, k, lo):
             what = "n %d k %d %s" % (n, k, name)
             lse, tlp, ids, top = _launch(q4, x, k, target)
             rids, rlp = logprobs_ref.topk(x, k)
@@ -76,10 +86,18 @@ def test_kernel_matches_the_reference(q4, n):
             assert logprobs_ref.within(top, rlp, logprobs_ref.bound(x, x[rids])), "%s: top log-probabilities %s, reference %s" % (what, top, rlp)
             assert logprobs_ref.within(tlp, [all_lp[target]], logprobs_ref.bound(x, x[target])), "%s: target %r, reference %r" % (what, tlp[0], all_lp[target])
             if name == "all equal":
-                assert ids.tolist() == list(range(k)) and logprobs_ref.within(top, np.full(k, -np.log(n)), logprobs_ref.bound(x))
+                assert ids.tolist() == list(range(lo, lo + k))
+                if not lo:
+                    assert logprobs_ref.within(top, np.full(k, -np.log(n)), logprobs_ref.bound(x))
+            if lo:
+                assert target >= lo and int(np.argmax(x.astype(np.float32))) >= lo and (k == 0 or rids.min() >= lo), what
+                with np.errstate(invalid="ignore"):
+                    assert np.flatnonzero(x.astype(np.float32) == x.astype(np.float32).max()).min() >= lo, what
+                highest = max(highest, target, int(rids.max()) if k else 0)
             again = _launch(q4, x, k, target)
             for a, b in zip((lse, tlp, ids, top), again):
                 assert a.tobytes() == b.tobytes(), what + ": a second launch gave other bits"
+    assert not lo or highest > 98304, highest
 
 
 def test_kernel_without_a_target_and_argument_checks(q4):

@@ -81,6 +81,19 @@ def _row(rng, kind, n, k):
     return x
 
 
+HIGH = 65536          # a vocabulary beyond 16 bits of token id
+
+
+def _row_beyond_16_bits(rng, kind, n, k):
+    """_row on the ids HIGH .. n - 1; below them the same scale 40 down (all -inf: NaN, which ranks behind everything), so the maximum, its ties and the
+    top k ids all lie at ids >= HIGH"""
+    x = ((rng.standard_normal(n) * 3.0).astype(np.float32) - 40.0).astype(np.float16)
+    if kind == "all -inf":
+        x[:] = np.nan
+    x[HIGH:] = _row(rng, kind, n - HIGH, k)
+    return x
+
+
 def _one(q4, row, k, target):
     """q4_logprob_topk on one contiguous row: the bytes of lse, target_logprob, top_ids, top_logprobs"""
     n = row.shape[0]
@@ -111,8 +124,10 @@ def _rows(q4, x, n, k, targets):
     return out
 
 
-# n: 8 (one chunk), 513 (ld 520: the tail element), 32000, 32768 (the register path's limit), 40000 (the looping path); ld: n rounded up to 8, and that + 64
-SIZES = [(8, 8), (8, 72), (513, 520), (513, 584), (32000, 32000), (32000, 32064), (32768, 32768), (32768, 32832), (40000, 40000), (40000, 40064)]
+# n: 8 (one chunk), 513 (ld 520: the tail element), 32000, 32768 (the register path's limit), 40000 (the looping path), 128256 (Llama-3's vocabulary: sixteen
+# loop runs, ids beyond 16 bits); ld: n rounded up to 8, and that + 64
+SIZES = [(8, 8), (8, 72), (513, 520), (513, 584), (32000, 32000), (32000, 32064), (32768, 32768), (32768, 32832), (40000, 40000), (40000, 40064),
+         (128256, 128256), (128256, 128320)]
 
 
 @pytest.mark.parametrize("n_rows,top_k", [(1, 1), (3, 0), (3, 20), (8, 20), (8, 1)])
@@ -124,10 +139,12 @@ def test_rows_equal_the_one_block_launch(q4, n, ld, n_rows, top_k):
     kinds = [KINDS[(r + shift) % len(KINDS)] for r in range(n_rows)]
     x = np.empty((n_rows, ld), dtype=np.float16)
     pad = np.where(np.arange(ld - n) % 2 == 0, np.float16(np.nan), np.float16(np.inf)).astype(np.float16)
+    lo = HIGH if n > HIGH else 0                          # there every id that decides a record lies beyond 16 bits: asserted on the one-block launch's answer
     for r in range(n_rows):
-        x[r, :n] = _row(rng, kinds[r], n, k)
+        x[r, :n] = _row_beyond_16_bits(rng, kinds[r], n, k) if lo else _row(rng, kinds[r], n, k)
         x[r, n:] = pad                                    # NaN and +inf between n and ld: never read, never written
-    targets = [(int(rng.integers(n)), -1, n, int(rng.integers(n)), n + 5, 0, n - 1, -7)[r] for r in range(n_rows)]
+    targets = [(100003 if lo else int(rng.integers(n)), -1, n, int(rng.integers(lo, n)), n + 5, lo, n - 1, -7)[r] for r in range(n_rows)]
+    highest = 0
     lse, tlp, ids, top, after = _rows(q4, x, n, k, targets)
     assert after.tobytes() == x.view(np.uint16).tobytes(), "the logits (padding included) were written"
     for r in range(n_rows):
@@ -139,6 +156,14 @@ def test_rows_equal_the_one_block_launch(q4, n, ld, n_rows, top_k):
             assert np.isnan(tlp[r:r + 1].view(np.float32)[0]), what + ": a target outside [0, n) gives NaN"
         if k:
             assert ids[r].min() >= 0 and ids[r].max() < n, what
+        if lo:
+            ref_ids = want[2]
+            assert k == 0 or ref_ids.min() >= lo, "%s: a record id below 65536: %s" % (what, ref_ids)
+            with np.errstate(invalid="ignore"):
+                row = x[r, :n].astype(np.float32)
+                assert np.isnan(row).all() or np.flatnonzero(row == np.nanmax(row)).min() >= lo, what
+            highest = max(highest, int(ref_ids.max()) if k else 0, targets[r] if 0 <= targets[r] < n else 0)
+    assert not lo or highest > 98304, highest
 
 
 def test_rows_do_not_see_each_other(q4):

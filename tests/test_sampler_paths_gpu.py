@@ -1,6 +1,6 @@
 """topp_sample_kernel (csrc/q4_sampling.hip) on distributions with holes -- a few, a few hundred or a few thousand finite logits, -inf everywhere
-else: what top-k, typical-p, top-n-sigma and a guide hand the sampler -- at fourteen vocabulary sizes (E = ceil(n / 1024) from 1 to 40, both sides of
-every threshold between two forms), token for token against the restatement (oracle/q4_oracle.c orc_sample_topp) with the same coin stream.
+else: what top-k, typical-p, top-n-sigma and a guide hand the sampler -- at sixteen vocabulary sizes (E = ceil(n / 1024) from 1 to 126, both sides of
+every threshold between two forms, and Llama-3's 128256 with every finite logit at an id beyond 16 bits), token for token against the restatement (oracle/q4_oracle.c orc_sample_topp) with the same coin stream.
 tests/sampler_paths_ref.py crafts the inputs and names the branch each should take (inferred from restated probabilities, not observed on the device);
 tests/test_sampler_paths_host.py holds every reachable branch to at least eight of these trials. Then the same supports inside captured sampled
 steps: top_k of 1 .. 3000 through the real step, every token against the restated sampler over the reference's processed logits."""
@@ -29,16 +29,19 @@ class SamplerStruct(C.Structure):
 def paths(tmp_path_factory):
     d = tmp_path_factory.mktemp("paths")
     out = {}
-    for name in ("small", "v32k", "v40k"):
+    for name in ("small", "v32k"):
         out[name] = str(d / (name + ".bin"))
         synth.write_model(out[name], name, seed=5)
+    # v128k's body with eight more vocabulary rows: its logits buffer and embedding table hold the largest size, 128259, and every id below it
+    out["host"] = str(d / "host.bin")
+    synth.write_model(out["host"], synth.GEOMETRIES["v128k"][:5] + (128264,) + synth.GEOMETRIES["v128k"][6:], seed=5)
     return out
 
 
 @pytest.fixture(scope="module")
 def host(q4, paths):
     """one model whose logits buffer holds every size: q4_sample reads the SAMPLER's vocab_size, and the kernel writes logits[0 .. n)"""
-    t = q4.Transformer(paths["v40k"])
+    t = q4.Transformer(paths["host"])
     assert t.config.vocab_size >= max(ref.SIZES)
     yield t
     t.close()
@@ -69,6 +72,7 @@ def test_sampler_matches_the_restatement_on_every_branch(q4, orc, host, n):
             got = int(t.token(1))
             label = ref.classify(x, n, T, topp, coin)
             labels[label] = labels.get(label, 0) + 1
+            assert want >= ref.low_id(n), name                   # (sizes beyond 16 bits of id: the restatement's token lies there)
             if got != want or not np.isfinite(np.float32(x[got])):      # (a -inf logit has probability 0: never the sample)
                 bad.append("%s [%s] coin %.9g: token %d, restatement %d" % (name, label, coin, got, want))
     finally:

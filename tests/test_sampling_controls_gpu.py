@@ -14,7 +14,7 @@ import sampling_controls_ref as ref
 import teacher_forced
 from conftest import GOLDEN, ROOT
 from llama_cu_awq_amd import synth
-from test_logprobs_gpu import _distributions
+from test_logprobs_gpu import HIGH, _distributions
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +29,11 @@ def _bits(a):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 1. the op against the reference
-def _windows(rng, n):
-    """(name, ring, pos, last_n): empty, 1, 64 and 1024 entries; few distinct tokens (heavy repeats) and ids outside [0, n)"""
+def _windows(rng, n, lo=0):
+    """(name, ring, pos, last_n): empty, 1, 64 and 1024 entries; few distinct tokens (heavy repeats) and ids outside [0, n). lo: the least valid id"""
     out = []
     for name, last_n, pos in (("empty", 0, 5), ("1", 1, 0), ("64", 64, 100), ("1024", 1024, 1500)):
-        ring = rng.integers(0, min(n, 50), pos + 4).astype(np.int32)
+        ring = (lo + rng.integers(0, min(n - lo, 50), pos + 4)).astype(np.int32)
         if pos > 8:
             ring[rng.choice(pos + 1, size=(pos + 1) // 8, replace=False)] = rng.choice([-5, n, n + 7, 2 ** 31 - 1, -2 ** 31], size=(pos + 1) // 8)
             ring[pos - 3:pos + 1] = ring[pos]                    # the newest token four times over
@@ -41,13 +41,13 @@ def _windows(rng, n):
     return out
 
 
-def _biases(rng, n):
-    """{id: bias} of 0, 1 and 256 entries (as many as the vocabulary has), -inf among them, ids that are in the windows among them"""
+def _biases(rng, n, lo=0):
+    """{id: bias} of 0, 1 and 256 entries (as many as the vocabulary has), -inf among them, ids that are in the windows among them. lo: the least id"""
     out = [{}]
     for count in (1, 256):
         count = min(count, n)
-        ids = set(range(min(count // 2, n))) | set(int(i) for i in rng.choice(n, size=count, replace=False))
-        ids = sorted(ids)[:count] if count > 1 else [int(rng.integers(min(n, 50)))]
+        ids = set(range(lo, lo + min(count // 2, n - lo))) | set(lo + int(i) for i in rng.choice(n - lo, size=count, replace=False))
+        ids = (sorted(ids)[:count // 2] + sorted(ids)[-(count - count // 2):] if lo else sorted(ids)[:count]) if count > 1 else [lo + int(rng.integers(min(n - lo, 50)))]
         b = {i: float(np.float32(rng.standard_normal() * 3.0)) for i in ids}
         if count > 1:
             for i in ids[::5]:
@@ -66,23 +66,34 @@ def _process(q4, x, ring=None, pos=None, logit_bias=None, **kw):
     return dl.get(np.float16, x.shape[0])
 
 
-def _with_nan(rng, n):
+def _with_nan(rng, n, lo=0):
+    """lo > 0: as _distributions -- the entries below id lo 40 down, the NaN at a fixed id above it"""
     x = (rng.standard_normal(n) * 2.0).astype(np.float16)
-    x[int(rng.integers(n))] = np.nan
+    if lo:
+        x[:lo] = (x[:lo].astype(np.float32) - 40.0).astype(np.float16)
+        x[100003] = np.nan
+    else:
+        x[int(rng.integers(n))] = np.nan
     return x
 
 
-@pytest.mark.parametrize("n", [1, 8, 20, 1000, 1027, 32000, 32768, 32776, 40000])
+@pytest.mark.parametrize("n", [1, 8, 20, 1000, 1027, 32000, 32768, 32776, 40000, 128256, 128259])
 def test_op_matches_the_reference_bit_for_bit(q4, n):
+    """(128256 / 128259: beyond 16 bits of token id. There every penalised id, every biased id, the maximum and the entries a top-k keeps sit at ids >= 65536,
+    some beyond 98304: asserted on the reference's answer.)"""
     rng = np.random.default_rng(2000 + n)
-    windows, biases = _windows(rng, n), _biases(rng, n)
+    lo = HIGH if n > HIGH else 0
+    windows, biases = _windows(rng, n, lo), _biases(rng, n, lo)
+    if lo:
+        assert all(min(b) >= lo for b in biases if b) and max(max(b) for b in biases if b) > 98304
+        assert all(((r >= lo) | (r < 0)).all() for _, r, _, _ in windows)
     combos = [(w, b) for w in range(len(windows)) for b in range(len(biases))]
-    case = 0
+    case = highest = 0
     seen = set()
     for k in (0, 1, 40, n):
         if k > n:
             continue
-        dists = [(name, x) for name, x, _ in _distributions(rng, n, k)] + [("one NaN", _with_nan(rng, n))]
+        dists = [(name, x) for name, x, _ in _distributions(rng, n, k, lo)] + [("one NaN", _with_nan(rng, n, lo))]
         for name, x in dists:
             wi, bi = combos[case % len(combos)]                  # every (window, bias list) pair comes round for every n
             case += 1
@@ -96,9 +107,18 @@ def test_op_matches_the_reference_bit_for_bit(q4, n):
             assert bad.size == 0, "%s: %d entries differ, first %d: got %04x, reference %04x (input %04x)" % (
                 what, bad.size, bad[0], _bits(got)[bad[0]], _bits(want)[bad[0]], _bits(x)[bad[0]])
             assert got.size == n
+            if lo:                                               # on the reference's output: the maximum (its lowest index) and what a top-k keeps, beyond 16 bits
+                w32 = want.astype(np.float32)
+                with np.errstate(invalid="ignore"):
+                    assert int(np.flatnonzero(w32 == np.nanmax(w32)).min()) >= lo, what
+                if 0 < k < n:
+                    kept = np.flatnonzero(~np.isneginf(w32))
+                    assert kept.size >= 1 and kept.min() >= lo, (what, kept[:4])
+                    highest = max(highest, int(kept.max()))
             again = _process(q4, x, ring, pos, biases[bi], **kw)
             assert again.tobytes() == got.tobytes(), what + ": a second launch gave other bytes"
     assert seen == set(combos)
+    assert not lo or highest > 98304, highest
 
 
 def test_op_window_shorter_than_last_n_and_no_ring(q4):

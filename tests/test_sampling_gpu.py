@@ -46,7 +46,7 @@ def test_sample_matches_restatement(q4, orc, model, temperature, topp):
 def big_vocab_models(tmp_path_factory):
     d = tmp_path_factory.mktemp("v")
     out = {}
-    for name in ("v32k", "v40k"):
+    for name in ("v32k", "v40k", "v128k"):
         out[name] = str(d / (name + ".bin"))
         synth.write_model(out[name], name, seed=5)
     return out
@@ -75,12 +75,13 @@ def _logit_case(rng, vocab, trial):
     return x.astype(np.float16)
 
 
-@pytest.mark.parametrize("name", ["v32k", "v40k"])
+@pytest.mark.parametrize("name", ["v32k", "v40k", "v128k"])
 @pytest.mark.parametrize("temperature,topp", [(0.5, 0.6), (1.0, 0.9), (0.8, 1.0), (1.3, 0.0), (0.3, 0.95), (0.05, 0.9),
                                               (0.12, 0.6)])
 def test_sample_matches_restatement_at_production_vocab(q4, orc, big_vocab_models, name, temperature, topp):
     """sample() sampler.h:51-81 where the CLI runs it: vocab 32000 (32 register-resident keys per thread, packed ranks,
-    transposed LDS layout) and vocab 40000 (> 32768: the same passes through global memory), 105 trials per (T, p)
+    transposed LDS layout), vocab 40000 (> 32768: the same passes through global memory) and Llama-3's 128256 (four loop
+    runs of that form, token ids beyond 16 bits), 105 trials per (T, p)
     over ordinary / flat / tied distributions, token-exact against the restatement with the same coin stream."""
     L = q4.lib()
     t = q4.Transformer(big_vocab_models[name], temperature=temperature, topp=topp, seed=99)
@@ -99,6 +100,49 @@ def test_sample_matches_restatement_at_production_vocab(q4, orc, big_vocab_model
         assert t.pos() == 1
         if t.token(1) != ref:
             bad.append((trial, trial % 7, int(t.token(1)), ref, coin))
+    assert not bad, bad[:8]
+    t.close()
+
+
+HIGH_IDS = (70001, 100003, 128255)                                   # planted entries: beyond 16 bits, two of them beyond 98304
+HIGH_TIES = (65536, 70001, 81920, 98305, 100003, 114688, 120000, 128255)
+
+
+def test_sample_where_every_likely_token_has_an_id_beyond_16_bits(q4, orc, big_vocab_models):
+    """Vocabulary 128256 with the entries that decide the draw at ids >= 65536: one dominant entry, an eight-way tie at the maximum (the sorted order
+    among equal keys is by index), and an ordinary distribution whose lower half is out of reach. A sampler that keeps an id, or a rank beside an id,
+    in 16 bits answers with an id below 65536. The condition is asserted on the restatement's answer."""
+    L = q4.lib()
+    temperature, topp = 0.8, 0.9
+    t = q4.Transformer(big_vocab_models["v128k"], temperature=temperature, topp=topp, seed=99)
+    vocab = t.config.vocab_size
+    assert vocab == 128256
+    rng = np.random.default_rng(128256)
+    state = C.c_ulonglong(99)
+    bad, refs = [], []
+    for trial in range(21):
+        kind = trial % 3
+        if kind == 0:
+            x = rng.standard_normal(vocab)
+            x[HIGH_IDS[(trial // 3) % 3]] = 12.0
+        elif kind == 1:
+            x = rng.standard_normal(vocab)
+            x[list(HIGH_TIES)] = 12.0
+        else:
+            x = rng.standard_normal(vocab) * 2.0
+            x[:65536] -= 40.0
+        logits = x.astype(np.float16)
+        t.reset([1])
+        q4.check(L.q4_memcpy_h2d(t.state.contents.logits, logits.ctypes.data, logits.nbytes))
+        q4.check(L.q4_sample(t.sampler, t.state, 1))
+        q4.synchronize()
+        coin = L.random_f32(C.byref(state))
+        ref = orc.lib().orc_sample_topp(orc.f16_bits(logits.copy()), vocab, temperature, topp, coin)
+        refs.append(int(ref))
+        if t.token(1) != ref:
+            bad.append((trial, kind, int(t.token(1)), ref, coin))
+    assert min(refs) >= 65536 and max(refs) > 98304, refs
+    assert len(set(refs[1::3])) > 1, refs[1::3]                      # (the tie is not always resolved to the same entry)
     assert not bad, bad[:8]
     t.close()
 
