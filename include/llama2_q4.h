@@ -367,6 +367,21 @@ int q4_get_logprobs(const Transformer* t, int first_pos, int n, float* token_log
  * the logits are those of the per-token run, byte for byte. Q4_ERR_ARG / 0: a Transformer the library did not build. */
 int q4_set_pass_logprobs(Transformer* t, int on);
 int q4_get_pass_logprobs(const Transformer* t);   /* 1: on; 0: off, or not a Transformer the library built */
+/* Prompt and verify passes for the grouped-query 4096-wide shape (Mistral-7B, Llama-3-8B): per model, off by default -- a grouped-query model then runs
+ * per-token steps everywhere, as before, and no decision, launch or counter changes. On, q4_set_prompt_ingest's passes, the verify passes of
+ * q4_set_speculative (greedy and, where the vocabulary admits it, q4_set_speculative_sampled), passes with records (q4_set_pass_logprobs) and
+ * q4_score_ids through passes also admit a model with: dim 4096 and 128-wide heads; n_heads = 4 * n_kv_heads (K / V rows dim / 4 wide); a hidden size
+ * whose down projection the step runs as the two-part K split with three whole k-slots and a shared last slot of at most 32 units per part (hidden
+ * 14336: 448 units, 224 = 3 x 64 + 32 per part) -- and only while q4_set_ksplit / q4_set_half_tail of the profiling build leave that form in force;
+ * and everything a pass requires of a multi-head model (a rotation table, an fp16 K / V cache, an unmasked stream, fusion level >= 3, the position, bin,
+ * record, guide, adaptive and context-shift rules of q4_set_prompt_ingest and q4_verify_tokens). Other ratios, other head sizes, the FP8 cache and 13B
+ * stay on steps. A multi-head model behaves with the switch on exactly as with it off. K / V rows, tokens, logits, records and rng_state are the
+ * per-token run's, byte for byte; q4_verify_covers, q4_verify_covers_sampled and q4_prompt_passes report the admissions. Q4_ERR_ARG / 0: a Transformer
+ * the library did not build. */
+int q4_set_pass_gqa(Transformer* t, int on);
+int q4_get_pass_gqa(const Transformer* t);        /* 1: on; 0: off, or not a Transformer the library built */
+/* The CLI's Q4_PASS_GQA: "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
+int q4_parse_pass_gqa(const char* text, int* on);
 
 /* The classifier of a greedy step without streaming every fp16 row of wcls (csrc/cls_screen.h): where the classifier runs as strips (dim 4096 or
  * 5120, at least 64 vocabulary rows per CU, an unmasked stream) q4_build_transformer derives a per-row-scaled int8 copy of wcls (vocab x dim bytes: 131 MB
@@ -387,7 +402,8 @@ int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* t
  * consecutive prompt-only positions -- those in front of num_prompt_tokens - 1, the step that generates -- as ONE pass over the weights: every launch reads
  * its weights once and multiplies all the positions' activations. The K / V rows, the generated tokens and the final logits are the per-token steps', bit
  * for bit; a pass runs no classifier, so RunState::logits is not written by the positions it covers. Taken only where the result is the same and nothing
- * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits), fusion level
+ * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits; with
+ * q4_set_pass_gqa on also the grouped-query shape described there), fusion level
  * >= 3, an fp16 K / V cache, positions below the bound of q4_set_pass_context (256 unless raised), log-probability records off or q4_set_pass_logprobs on, no guide, no adaptive truncation, no context-shift offset, an unmasked
  * stream; everything else -- and q4_run_transformer*, q4_score_ids (unless q4_set_pass_logprobs is on), q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
  * clamped to 8, the default. q4_prompt_passes: passes run since the library was loaded. */

@@ -57,4 +57,7 @@ inline void build_transformer(Transformer* t, char* checkpoint_path, bool perple
     if (rc) exit(rc == Q4_ERR_IO ? 1 : EXIT_FAILURE);
 }
 inline void free_transformer(Transformer* t) { q4_free_transformer(t); }                                    // :428
+// not in the reference: prompt and verify passes for the grouped-query 4096-wide shape (q4_set_pass_gqa)
+inline void set_pass_gqa(Transformer* t, bool on) { die_on(q4_set_pass_gqa(t, on ? 1 : 0)); }
+inline bool pass_gqa(const Transformer* t) { return q4_get_pass_gqa(t) != 0; }
 }  // namespace llama2_q4

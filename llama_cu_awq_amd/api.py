@@ -208,7 +208,7 @@ SYMBOLS = [
     "q4_verify_tokens", "q4_verify_covers", "q4_set_speculative", "q4_get_speculative", "q4_parse_speculative", "q4_set_drafter", "q4_spec_draft",
     "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept", "q4_set_speculative_sampled", "q4_get_speculative_sampled", "q4_verify_tokens_sampled",
     "q4_verify_covers_sampled", "q4_verify_sample_rows", "q4_verify_accept_tokens", "q4_parse_speculative_sampled",
-    "q4_logprob_topk_rows", "q4_set_pass_logprobs", "q4_get_pass_logprobs",
+    "q4_logprob_topk_rows", "q4_set_pass_logprobs", "q4_get_pass_logprobs", "q4_set_pass_gqa", "q4_get_pass_gqa", "q4_parse_pass_gqa",
 ]
 
 _lib = None
@@ -343,6 +343,10 @@ def lib():
         L.q4_logprob_topk_rows.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp]
         L.q4_set_pass_logprobs.argtypes = [vp, i]
         L.q4_get_pass_logprobs.argtypes = [vp]
+    if hasattr(L, "q4_set_pass_gqa"):              # (older builds under tools/ab.py do not have it)
+        L.q4_set_pass_gqa.argtypes = [vp, i]
+        L.q4_get_pass_gqa.argtypes = [vp]
+        L.q4_parse_pass_gqa.argtypes = [C.c_char_p, C.POINTER(i)]
     if hasattr(L, "q4_set_greedy_screen"):         # (older builds under tools/ab.py do not have it)
         L.q4_set_greedy_screen.argtypes = [i]
         L.q4_set_greedy_screen.restype = None
@@ -822,7 +826,7 @@ class Transformer:
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
                  logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None,
-                 pass_logprobs=False):
+                 pass_logprobs=False, pass_gqa=False):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -873,6 +877,8 @@ class Transformer:
                 self.set_logprobs(logprobs)
             if pass_logprobs:
                 self.set_pass_logprobs(True)
+            if pass_gqa:
+                self.set_pass_gqa(True)
             if sampling is not None:
                 self.set_sampling(**sampling)
             if logit_bias is not None:
@@ -1215,6 +1221,15 @@ class Transformer:
     def pass_logprobs(self):
         """q4_get_pass_logprobs"""
         return bool(lib().q4_get_pass_logprobs(self.h))
+
+    def set_pass_gqa(self, on):
+        """q4_set_pass_gqa: prompt and verify passes also for the grouped-query 4096-wide shape (dim 4096, 128-wide heads, four query heads per K / V
+        head, hidden 14336: Mistral-7B, Llama-3-8B); off by default. Tokens, K / V rows, logits and records are the per-token run's, byte for byte."""
+        check(lib().q4_set_pass_gqa(self.h, 1 if on else 0))
+
+    def pass_gqa(self):
+        """q4_get_pass_gqa"""
+        return bool(lib().q4_get_pass_gqa(self.h))
 
     def logprobs_k(self):
         return lib().q4_get_logprobs_k(self.h)

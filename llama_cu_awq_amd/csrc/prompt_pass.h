@@ -10,6 +10,9 @@ constexpr int PASS_CONTEXT_MIN = 256;   // q4_set_pass_context: the default boun
 
 // The geometry part of the admission (q4_passes.hip decides the rest): Llama-2-7B's shape -- dim 4096, multi-head, 128-wide heads, a hidden size the
 // three-phase FFN launch admits (its down projection is the two-part K split in three k-slots), a rotation table, an fp16 cache, an unmasked stream.
+// With the model's q4_set_pass_gqa switch on also the grouped-query shape of Mistral-7B / Llama-3-8B: dim 4096, 128-wide heads, n_heads = 4 * n_kv_heads,
+// a hidden size whose down projection the step runs as the two-part K split with three whole k-slots and a shared half slot per part (14336) -- while
+// the profiling knobs g_ksplit / g_half_tail leave the step that form. A multi-head model is judged as with the switch off.
 bool prompt_pass_covers(const Config* p, const Model* m);
 // Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_passes.hip, the admission's one place): for every position the
 // form of the step's attention -> o-proj launch (attention_oproj_form of the bin argument the step would hand to run_network there) is either a V-slice

@@ -5,6 +5,8 @@
 // leaves RunState::x and the position words as the per-token steps would. No launch waits for another block: every dependency is a launch boundary.
 // With log-probability records on (q4_set_pass_logprobs): the verify pass's classifier over the n rows and the row form of the record launch in front of
 // that last launch (run_prompt_pass).
+// Grouped-query models of Mistral-7B's / Llama-3-8B's shape (q4_set_pass_gqa; DESIGN.md 3.7 "Grouped-query shapes"): the q/k/v launch with per-matrix
+// widths (GQA), both attention launches with kv_mul query heads per K / V head, the down projection in the step's shared-half-slot form (HALF).
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
 // parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
@@ -21,6 +23,14 @@
 namespace q4 {
 
 constexpr int PP_WAVES = 16;           // waves per block: four per SIMD hide each other's issue latency (a wave alone issues a VALU instruction every ~5 cycles)
+#ifndef Q4_PP_QKV_GQA_WAVES            // (make exp EXPFLAGS=-DQ4_PP_QKV_GQA_WAVES=12: the other grid, for tools/bench_pass_gqa.py --variant-libs)
+#define Q4_PP_QKV_GQA_WAVES 6
+#endif
+#ifndef Q4_PP_DOWN_HALF_G              // (... -DQ4_PP_DOWN_HALF_G=2: two staged tokens per group behind an LDS opt-in)
+#define Q4_PP_DOWN_HALF_G 1
+#endif
+constexpr int PP_QKV_GQA_WAVES = Q4_PP_QKV_GQA_WAVES;    // grouped-query q/k/v (kv_dim = dim / 4): 1024 + 2 x 256 column groups = 256 blocks of six waves, one per CU (twelve-wave blocks: 128, half of the CUs idle -- a 250-token ingest 169.9 ms against 165.3)
+constexpr int PP_DOWN_HALF_G = Q4_PP_DOWN_HALF_G;      // tokens staged per group by the shared-half-slot down launch: nine LDS rows of 64 units (39 KB) per token, two exceed 64 KB (behind an opt-in they measured 0.45 % faster over an ingest: not taken)
 constexpr int PP_QKV_WAVES = 12;       // q/k/v: 3 x 1024 column groups = 256 blocks of twelve waves, one per CU (sixteen-wave blocks: 192, a quarter of the CUs idle)
 
 // One wave owns COLS columns (KS = 2: one of the two k-parts of them); W / ZW / SC stay in registers while the tokens pass. Token t reads x + t * K and
@@ -30,9 +40,15 @@ constexpr size_t prompt_gemv_lds() {      // G tokens' permuted x and x-only sum
     using L = LdsLayout<SLOTS, KS>;
     return (size_t)G * (L::XS + L::SX + (NORM ? (size_t)L::NUNITS * 4 : 0)) + 1024 + 16;
 }
-template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW>
+// GQA (q/k/v): k and v have a.N_kv < a.N columns each; the three matrices' column groups are still dealt as one range, N / 4 groups of q and then
+// N_kv / 4 of k and of v, every matrix with its own width in the descriptors, the clamp and the row addressing.
+// HALF (plain, K split): gemv_q4_body's shared half slot -- a k-part's last slot holds at most 32 units, lanes 0 - 31 take it for the even column of the
+// wave's pair and lanes 32 - 63 for the odd one, its term is added as a product and a sum and the other half of the wave adds 0.f.
+template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false>
 __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, const int ntok) {
     constexpr int NMAT = ModeTraits<MODE>::NMAT;
+    static_assert(!GQA || MODE == MODE_QKV, "per-matrix widths: q/k/v");
+    static_assert(!HALF || (MODE == MODE_PLAIN && KS == 2 && COLS == 2), "shared half slot: one column pair per wave, K split");
     static_assert(G >= 1 && G <= 8, "exchange slots");
     static_assert(KS == 1 || (KS == 2 && MODE == MODE_PLAIN && !NORM), "K split: plain GEMV");
     static_assert(COLS >= 1 && COLS <= 4 && (MODE != MODE_QKV || COLS == 4), "one reduce4_q4 row per column; q/k/v: two RoPE pairs per wave");
@@ -52,13 +68,15 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
     // q/k/v: the three matrices' column groups are dealt as one range (N / 4 groups each), so the grid divides by any block width
     const int gidx = blockIdx.x * (nw / KS) + wave / KS;
     const int gpm = MODE == MODE_QKV ? a.N / COLS : 1;       // column groups per matrix
-    const int mat0 = MODE == MODE_QKV ? __builtin_amdgcn_readfirstlane(gidx / gpm) : 0;
-    const int wg = MODE == MODE_QKV ? gidx - mat0 * gpm : gidx;
+    const int gkv = GQA ? a.N_kv / COLS : gpm;               // ... of k and of v
+    const int mat_g = gidx < gpm ? 0 : 1 + (gidx - gpm) / gkv;   // (a wave past the last group -- the host launches none -- lands on v past its columns: clamped loads, no store)
+    const int mat0 = MODE == MODE_QKV ? __builtin_amdgcn_readfirstlane(GQA ? (mat_g < 2 ? mat_g : 2) : gidx / gpm) : 0;
+    const int wg = MODE == MODE_QKV ? (GQA ? (mat0 == 0 ? gidx : gidx - gpm - (mat0 - 1) * gkv) : gidx - mat0 * gpm) : gidx;
     const int khalf = wave % KS;
     const unsigned ubase = KS > 1 ? (unsigned)(khalf * a.ku) : 0u;
     const unsigned uend = KS > 1 ? (ubase + (unsigned)a.ku < (unsigned)a.pw4 ? ubase + (unsigned)a.ku : (unsigned)a.pw4) : (unsigned)a.pw4;
     const unsigned nchunks = (unsigned)a.K >> 3;
-    const int N = a.N;
+    const int N = GQA && mat0 != 0 ? a.N_kv : a.N;
 
     int col[COLS];
     if (MODE == MODE_QKV) {
@@ -116,8 +134,18 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
         rz[m] = __builtin_amdgcn_make_buffer_rsrc((void*)M.z, 0, N * a.pzh * 4, 0x00020000);
         rs[m] = __builtin_amdgcn_make_buffer_rsrc((void*)M.s, 0, N * a.sh * 2, 0x00020000);
     }
+    const bool upper = lane >= 32u;
 #pragma unroll
     for (int s = 0; s < SLOTS; s++) {
+        if (HALF && s == SLOTS - 1) {                        // the shared half slot: the column offset per lane, kept in the pair's first entries
+            const unsigned jh = ubase + s * 64 + (lane & 31u);
+            const unsigned jj = jh < uend ? jh : uend - 1;
+            const unsigned cw = upper ? (unsigned)colc[COLS - 1] : (unsigned)colc[0];
+            ZW[0][s][0] = __builtin_amdgcn_raw_buffer_load_b32(rz[0], (jj >> 5) * 4 + cw * a.pzh * 4, 0, Q4_ZS_AUX);
+            SC[0][s][0] = __builtin_amdgcn_raw_buffer_load_b16(rs[0], (jj >> 2) * 2 + cw * a.sh * 2, 0, Q4_ZS_AUX);
+            W[0][s][0] = __builtin_amdgcn_raw_buffer_load_b128(rw[0], jj * 16 + cw * a.pw4 * 16, 0, Q4_W_AUX);
+            continue;
+        }
         const unsigned j = ubase + s * 64 + lane;
         const unsigned jj = j < uend ? j : uend - 1;        // tail lanes re-read the part's last unit
 #pragma unroll
@@ -224,7 +252,8 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
 #pragma unroll
                 for (int s = 0; s < SLOTS; s++)
 #pragma unroll
-                    for (int c = 0; c < COLS; c++) asm volatile("" : "+v"(W[m][s][c]));
+                    for (int c = 0; c < COLS; c++)
+                        if (!(HALF && s == SLOTS - 1 && c > 0)) asm volatile("" : "+v"(W[m][s][c]));
             // ---- 4. consume in slot order
             float colsum[NMAT][4];
 #pragma unroll
@@ -233,18 +262,27 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
                 for (int c = 0; c < 4; c++) colsum[m][c] = 0.f;
 #pragma unroll
             for (int s = 0; s < SLOTS; s++) {
-                unsigned j = ubase + s * 64 + lane;
+                const bool hs = HALF && s == SLOTS - 1;      // both halves of the wave read the slot's units 0 - 31
+                const unsigned lu = hs ? (lane & 31u) : lane;
+                unsigned j = ubase + s * 64 + lu;
                 unsigned jx = j;
                 if (KS > 1) {                                // past the part's end: the all-zero row
                     jx = j < uend ? j : (unsigned)((TS - 1) * 64);
                     j = j < uend ? j : uend - 1;
                 }
                 u32x4 X[4];
-                const unsigned xrow = KS > 1 ? ((jx >> 6) << 8) + (jx & 63u) : (unsigned)((s * 4) << 6) + lane;
+                const unsigned xrow = KS > 1 ? ((jx >> 6) << 8) + (jx & 63u) : (unsigned)((s * 4) << 6) + lu;
 #pragma unroll
                 for (int d = 0; d < 4; d++) X[d] = xst[xrow + (d << 6)];
-                const float corr = sxt[KS > 1 ? jx : (unsigned)(s * 64) + lane];
+                const float corr = sxt[KS > 1 ? jx : (unsigned)(s * 64) + lu];
                 const unsigned zsh = ((j >> 2) & 7u) * 4u;
+                if (hs) {                                    // gemv_q4_body's half slot, word for word: lanes 0 - 31 worked for column 0, lanes 32 - 63 for column 1
+                    const float tt = q4_dot_unit(W[0][s][0], X, ZW[0][s][0], zsh, corr);
+                    const float v = h2f(SC[0][s][0]) * tt;
+                    colsum[0][0] += upper ? 0.f : v;
+                    colsum[0][COLS - 1] += upper ? v : 0.f;
+                    continue;
+                }
 #pragma unroll
                 for (int m = 0; m < NMAT; m++)
 #pragma unroll
@@ -330,7 +368,7 @@ struct PassSplitArgs {
     const q4_half* key_cache;    // already offset to the layer
     const q4_half* value_cache;
     const int* pos;              // [ntok], ascending
-    int ntok, dim, kv_dim, nsp;
+    int ntok, dim, kv_dim, kv_mul, nsp;   // kv_mul query heads read the rows of K / V head h / kv_mul (rows kv_dim wide)
     size_t tok_stride;           // floats between two tokens' record areas
     float alpha;
 };
@@ -358,8 +396,8 @@ __global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(c
         if ((int)tid < ntok) neutral((int)tid);
         return;
     }
-    const q4_half* kh = a.key_cache + (size_t)h * HS + sub * 8;
-    const q4_half* vh = a.value_cache + (size_t)h * HS + sub * 8;
+    const q4_half* kh = a.key_cache + (size_t)(h / a.kv_mul) * HS + sub * 8;
+    const q4_half* vh = a.value_cache + (size_t)(h / a.kv_mul) * HS + sub * 8;
     u32x4 kv[U], vv[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -540,10 +578,25 @@ static void fill_geom(GemvArgs& a, int K, int N) {
     a.loff = -1;
 }
 
+// The down projection of a hidden size the FFN pair launch does not take, as the step runs it (launch_gemv_plain): the two-part K split whose parts fill
+// three whole k-slots and a last one of at most 32 units -- the shared half slot, gemv_q4_kernel<MODE_PLAIN, 4, 4, false, 0, 2, true> or its strips
+// form -- which the step takes only with the K split and the half slot on (q4_set_ksplit 0 / 4 and q4_set_half_tail(0) select other arithmetic: no pass).
+// Hidden 14336: 448 units, ku = 224 = 3 x 64 + 32.
+static bool pass_down_half_covers(int dim, int hidden) {
+    if ((hidden & 31) || ffn_pair_covers(dim, hidden)) return false;
+    if (!g_ksplit || g_ksplit == 4 || !g_half_tail || g_ablate != 0) return false;
+    const QGeom g = make_geom(hidden, dim);
+    const int ku = (divUp(g.pw4, 2) + 3) & ~3;
+    return g.nslots >= 5 && g.nslots <= 8 && divUp(ku, 64) == 4 && ku - 192 <= 32 && ku * 2 >= g.pw4;
+}
 bool prompt_pass_covers(const Config* p, const Model* m) {
     if (!p || !m || !m->rope_table || !m->sync || m->kv_format != Q4_KV_FP16) return false;
     const int dim = p->dim, hidden = p->hidden_dim;
-    if (dim != 4096 || p->n_heads != p->n_kv_heads || p->n_heads * 128 != dim || (hidden & 31)) return false;
+    if (dim != 4096 || p->n_heads * 128 != dim || (hidden & 31)) return false;
+    if (p->n_heads != p->n_kv_heads) {      // grouped-query: q4_set_pass_gqa, four query heads per K / V head and the half-slot down form (Mistral-7B, Llama-3-8B: what the tests run)
+        if (!m->pass_gqa || p->n_kv_heads < 1 || p->n_heads != 4 * p->n_kv_heads) return false;
+        return pass_down_half_covers(dim, hidden) && stream_cu_count() == cu_count();
+    }
     if (!ffn_pair_covers(dim, hidden)) return false;
     const QGeom g = make_geom(hidden, dim);
     const int ku = (divUp(g.pw4, 2) + 3) & ~3;
@@ -558,6 +611,8 @@ bool prompt_pass_covers(const Config* p, const Model* m) {
 int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
+    const int kv_mul = p->n_heads / p->n_kv_heads, kv_dim = dim / kv_mul;
+    const bool down_half = !ffn_pair_covers(dim, hidden);    // (prompt_pass_covers: then the shared-half-slot form)
     Q4_TRY(prompt_pass_rows(m, p));
     PassScratch* const b = &m->pass;
     PassAttention plan = {};
@@ -572,13 +627,28 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     }
     constexpr int TB = PP_WAVES * 64;
     constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
-    static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024, "no LDS opt-in");
+    constexpr size_t SMEM_DOWN_HALF = prompt_gemv_lds<4, 2, false, PP_DOWN_HALF_G>();
+    static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024 && (SMEM_DOWN_HALF <= 64 * 1024 || PP_DOWN_HALF_G > 1), "no LDS opt-in in the shipped form");
+    if (SMEM_DOWN_HALF > 64 * 1024)     // (an experiment build only)
+        Q4_TRY(lds_opt_in((const void*)prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>, SMEM_DOWN_HALF));
     const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
     const unsigned natt = (unsigned)p->n_heads * 4u;
     for (int l = 0; l < p->n_layers; l++) {
         const PerLayerWeight* L = &w->layers[l];
-        const long long loff = (long long)l * p->seq_len * dim;
-        {   // rmsnorm + q/k/v + RoPE + K/V rows
+        const long long loff = (long long)l * p->seq_len * kv_dim;
+        if (kv_mul > 1) {   // ... grouped-query: 1024 column groups of q, then 256 of k and of v, in six-wave blocks
+            GemvArgs a = {};
+            fill_geom(a, dim, dim);
+            a.N_kv = kv_dim;
+            fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
+            a.out[0] = b->q; a.out[1] = s->key_cache; a.out[2] = s->value_cache;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff;
+            a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
+            const int groups = (dim + 2 * kv_dim) / 4;
+            if (groups % PP_QKV_GQA_WAVES) return Q4_ERR_ARG;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_GQA_WAVES, true>), dim3(groups / PP_QKV_GQA_WAVES), dim3(PP_QKV_GQA_WAVES * 64), SMEM_NORM, a, n);
+            Q4_LAUNCH_CHECK();
+        } else {   // rmsnorm + q/k/v + RoPE + K/V rows
             GemvArgs a = {};
             fill_geom(a, dim, dim);
             fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
@@ -589,7 +659,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             Q4_LAUNCH_CHECK();
         }
         if (split) {   // attention in the split-context bins: one block per (head, chunk) loops over the tokens, then the step's merge per (head, token)
-            const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, dim, plan.nsp, tok_stride, alpha};
+            const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, kv_dim, kv_mul, plan.nsp, tok_stride, alpha};
             const dim3 grid((unsigned)p->n_heads, (unsigned)plan.nsp);
             if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a);
             else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a);
@@ -599,7 +669,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
                       plan.nsp, tok_stride, plan.nsp_of_bin, plan.chunk);
             Q4_LAUNCH_CHECK();
         } else {   // attention below bin 512: the V-slice units
-            const AttArgs a = {b->xb, b->q, s->key_cache + loff, s->value_cache + loff, head_size, 1, dim, b->pos, alpha, 256, nullptr};
+            const AttArgs a = {b->xb, b->q, s->key_cache + loff, s->value_cache + loff, head_size, kv_mul, kv_dim, b->pos, alpha, 256, nullptr};
             Q4_LAUNCH(prompt_attention_kernel, dim3((unsigned)n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, (u32x2v*)b->sink, (unsigned)b->sink_stride,
                       (unsigned)p->n_heads, natt, dim);
             Q4_LAUNCH_CHECK();
@@ -620,7 +690,15 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         }
-        {   // down projection + residual: two k-parts, part 0 then part 1
+        if (down_half) {   // down projection + residual, the shared-half-slot form: two k-parts of three slots and a shared one, a column pair per wave
+            GemvArgs a = {};
+            fill_geom(a, hidden, dim);
+            fill_mat(a.m[0], &L->wq_down);
+            a.ku = (divUp(a.pw4, 2) + 3) & ~3;
+            a.out[0] = b->x; a.x = b->hb; a.accum = 1;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN_HALF, a, n);
+            Q4_LAUNCH_CHECK();
+        } else {   // down projection + residual: two k-parts, part 0 then part 1
             GemvArgs a = {};
             fill_geom(a, hidden, dim);
             fill_mat(a.m[0], &L->wq_down);

@@ -587,6 +587,15 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and passes for the grouped-query 4096-wide shape (q4_set_pass_gqa): Q4_PASS_GQA=1
+    const char* pass_gqa = getenv("Q4_PASS_GQA");
+    if (pass_gqa && *pass_gqa) {
+        int on = 0;
+        if (q4_parse_pass_gqa(pass_gqa, &on) || q4_set_pass_gqa(&transformer, on)) {
+            fprintf(stderr, "Q4_PASS_GQA: cannot use '%s' (0 or 1: prompt and verify passes also for grouped-query models of dim 4096, e.g. Mistral-7B, Llama-3-8B)\n", pass_gqa);
+            exit(EXIT_FAILURE);
+        }
+    }
     // ... and how far prompt and verify passes go (q4_set_pass_context): Q4_PASS_CONTEXT=2048; values up to 256 are the default
     const char* pass_context = getenv("Q4_PASS_CONTEXT");
     if (pass_context && *pass_context) {

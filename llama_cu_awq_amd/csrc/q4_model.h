@@ -42,6 +42,7 @@ struct Model {
     float* lp_top = nullptr;        // [seq_len][K]
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
     bool pass_logprobs = false;     // q4_set_pass_logprobs: prompt and verify passes (and q4_score_ids through prompt passes) also while the records are on
+    bool pass_gqa = false;          // q4_set_pass_gqa: prompt and verify passes also for the grouped-query 4096-wide shape (prompt_pass_covers)
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
     const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model
     int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)

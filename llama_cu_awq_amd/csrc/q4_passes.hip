@@ -249,6 +249,22 @@ int q4_get_pass_logprobs(const Transformer* t) {
     const Model* m = t ? model_of(&t->state) : nullptr;
     return m && m->pass_logprobs ? 1 : 0;
 }
+// Passes for the grouped-query 4096-wide shape (prompt_pass_covers): per model, off by default. No captured graph contains a pass: nothing to drop.
+int q4_set_pass_gqa(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->pass_gqa = on != 0;
+    return Q4_OK;
+}
+int q4_get_pass_gqa(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->pass_gqa ? 1 : 0;
+}
+int q4_parse_pass_gqa(const char* text, int* on) {     // the CLI's Q4_PASS_GQA: "0" or "1", nothing else
+    if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
+    *on = text[0] - '0';
+    return Q4_OK;
+}
 int q4_get_speculative_sampled(const Transformer* t) {
     const Model* m = t ? model_of(&t->state) : nullptr;
     return m && m->spec_sampled ? 1 : 0;
