@@ -382,6 +382,20 @@ int q4_set_pass_gqa(Transformer* t, int on);
 int q4_get_pass_gqa(const Transformer* t);        /* 1: on; 0: off, or not a Transformer the library built */
 /* The CLI's Q4_PASS_GQA: "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
 int q4_parse_pass_gqa(const char* text, int* on);
+/* Passes while a logit stage is on (csrc/spec_verify.h, DESIGN.md 3.8 "Under the logit stages"): per model, off by default -- off, a guide, DRY, the
+ * sampling controls or the adaptive truncation switch every verify pass off and a guide or the adaptive truncation every prompt pass, as before, and
+ * nothing else changes. On: a verify pass is admitted with a guide, DRY and the sampling controls on -- greedy and, with q4_set_speculative_sampled, under
+ * the sampler --: between the classifier and the sampler / accept launch each stage rewrites the pass's logit rows through its row form, row r at position
+ * p + r reading its tokens from a device view of the ring plus the drafts (an unverified token still never enters the ring). It keeps refusing the adaptive
+ * truncation (typical-p, top-n-sigma, Mirostat), any stage together with log-probability records, and everything it refused before. A prompt pass is
+ * admitted with a guide or the adaptive truncation on and puts their state by position to NONE over its positions, as prompt steps do. The library's token
+ * loops then draft the guide's forced tokens first (q4_guide_forced_run) and ask the model's drafter only where that run is empty. Tokens, K / V rows,
+ * logits, rng_state and the guide's state ring below the position are the per-token run's, byte for byte; states of rejected drafts lie at or above the
+ * position and are rewritten by what runs there next. Q4_ERR_ARG / 0: a Transformer the library did not build. */
+int q4_set_pass_stages(Transformer* t, int on);
+int q4_get_pass_stages(const Transformer* t);     /* 1: on; 0: off, or not a Transformer the library built */
+/* The CLI's Q4_PASS_STAGES: "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
+int q4_parse_pass_stages(const char* text, int* on);
 
 /* The classifier of a greedy step without streaming every fp16 row of wcls (csrc/cls_screen.h): where the classifier runs as strips (dim 4096 or
  * 5120, at least 64 vocabulary rows per CU, an unmasked stream) q4_build_transformer derives a per-row-scaled int8 copy of wcls (vocab x dim bytes: 131 MB
@@ -442,7 +456,10 @@ int q4_greedy_screen_op(const q4_half* x, const q4_half* w, int n, int d, const 
 /* The primitive, at the current position (synchronises before and after): out_tokens receives the *n_accepted + 1 tokens the pass emitted (room for
  * n_draft + 1), the first *n_accepted of them equal to draft[]. Q4_ERR_ARG before any launch: a null pointer, n_draft outside 1 .. Q4_SPEC_MAX_DRAFT, an id
  * outside [0, vocab), a Transformer the library did not build. Q4_NOT_ADMITTED, nothing done: the model, the settings or the position do not admit a pass
- * (q4_verify_covers). The caller owns the sequence (q4_reset_sequence, then steps or passes); greedy, whatever a Sampler says. */
+ * (q4_verify_covers). The caller owns the sequence (q4_reset_sequence, then steps or passes); greedy, whatever a Sampler says.
+ * Logit stages: the greedy primitive has no Sampler, so of the stages it knows the model's guide alone -- admitted with q4_set_pass_stages on, and the rows
+ * are then masked as the guided greedy step masks them. DRY and the sampling controls live beside a Sampler: a host that wants them inside a pass hands
+ * that Sampler to q4_verify_tokens_sampled (temperature above 0) or runs the library's token loop, whose greedy passes take the stages of the loop's Sampler. */
 int q4_verify_tokens(Transformer* t, const int* draft, int n_draft, int* out_tokens, int* n_accepted);
 int q4_verify_covers(const Transformer* t, int pos, int n_draft);      /* 1: q4_verify_tokens at position pos with n_draft drafts would run; else 0 */
 /* The library's token loops (q4_generate, q4_generate_ids, q4_generate_ids_from): at a generating position whose pass is admitted the loop asks the model's
@@ -466,6 +483,8 @@ int q4_set_drafter(Transformer* t, q4_drafter_fn fn, void* ctx);
 int q4_spec_draft(const int* tokens, int n_tokens, int max_draft, int ngram_max, int ngram_min, int* draft_out);
 /* Verify passes run with this model, the drafts they carried and the drafts accepted, since the model was built. Any pointer may be NULL. */
 int q4_spec_stats(const Transformer* t, long long* passes, long long* drafted, long long* accepted);
+/* Of those drafts, the ones the guide's forced run gave the token loop (q4_set_pass_stages) and how many of them were accepted. Any pointer may be NULL. */
+int q4_spec_stats_forced(const Transformer* t, long long* drafted, long long* accepted);
 /* Op-level forms of the pass's two launches for tests and tools, on the q4 stream; device pointers unless said otherwise.
  * q4_verify_classifier: logits [n_rows][vocab] = wcls . rmsnorm(x[r], rms_w), x [n_rows][dim], 1 <= n_rows <= 8; every row holds the bits q4_rmsnorm +
  * q4_matmul_f16 give for that row alone. dim 4096 and a vocabulary that is a multiple of 8, else Q4_ERR_UNSUPPORTED_SIZE.
@@ -563,6 +582,11 @@ int q4_parse_sampling_controls(const char* text, q4_sampling_controls* out);
  * Q4_ERR_ARG without touching the GPU. */
 int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias,
                       const int* tokens, const int* pPos);
+/* The row form (a verify pass with q4_set_pass_stages on): rows r < n_rows of logits, `ld` halves apart, row r rewritten at position pos_rows_dev[r] with
+ * its window read from tokens_view_dev (device, tokens by absolute position) -- byte for byte what q4_process_logits writes for that row alone at that
+ * position; halves between n and ld are neither read nor written. Also Q4_ERR_ARG: n_rows outside 1 .. 8, ld < n, ld not a multiple of 8. */
+int q4_process_logits_rows(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias, int ld,
+                           int n_rows, const int* tokens_view_dev, const int* pos_rows_dev);
 
 /* ---- DRY and no-repeat-n-gram penalties (q4_dry.hip; not in the reference) ----------------------
  * The two controls of a completion API against loops: DRY ("don't repeat yourself") penalises only the token that would extend a repeated sequence, the
@@ -615,6 +639,11 @@ int q4_dry_penalty_table(const q4_dry_controls* controls, float out[65]);
  * both may be NULL: no window --, breaker_ids a host array. Anything the setters refuse, or a breaker id >= n: Q4_ERR_ARG without touching the GPU. */
 int q4_dry_penalty(q4_half* logits, int n, const q4_dry_controls* controls, const int* breaker_ids, int n_breakers, const int* tokens,
                    const int* pPos);
+/* The row form (a verify pass with q4_set_pass_stages on): rows r < n_rows of logits, `ld` halves apart, row r rewritten at position pos_rows_dev[r] with
+ * its window read from tokens_view_dev (device, tokens by absolute position) -- byte for byte what q4_dry_penalty writes for that row alone at that
+ * position; halves between n and ld are neither read nor written. Also Q4_ERR_ARG: n_rows outside 1 .. 8, ld < n, ld not a multiple of 8. */
+int q4_dry_penalty_rows(q4_half* logits, int n, const q4_dry_controls* controls, const int* breaker_ids, int n_breakers, int ld, int n_rows,
+                        const int* tokens_view_dev, const int* pos_rows_dev);
 
 /* ---- typical-p, top-n-sigma and Mirostat v2 (q4_adaptive.hip; not in the reference) -------------
  * Three truncation rules of completion APIs that take their threshold from a statistic of the whole distribution. With one of them on, every GENERATING
@@ -704,6 +733,16 @@ int q4_get_guide_states(const Transformer* t, int first_pos, int n, int* out);  
  * a position outside [0, Q4_MAX_SEQ_LEN) does nothing. For one device and one stream: the op keeps one small parameter block for the life of the
  * process, on the device that was current at its first call, and (like q4_guide_delete) orders itself against the current q4 stream only. */
 int q4_guide_mask(q4_half* logits, int n, const q4_guide* g, int* state_ring, const int* tokens, const int* pPos);
+/* The row form (a verify pass with q4_set_pass_stages on): rows r < n_rows of logits, `ld` halves apart, at positions pos_rows_dev[r] = pos_rows_dev[0] + r,
+ * tokens read from tokens_view_dev (device, tokens by absolute position). Block r walks the automaton from state_ring[pos_rows_dev[0] - 1] over the view's
+ * tokens up to its own position, stores state_ring[pos_rows_dev[r]] and masks row r with it: rows and states are byte for byte what n_rows calls of
+ * q4_guide_mask at consecutive positions leave. Halves between n and ld are neither read nor written. Also Q4_ERR_ARG: n_rows outside 1 .. 8, ld < n, ld
+ * not a multiple of 8. */
+int q4_guide_mask_rows(q4_half* logits, int n, const q4_guide* g, int* state_ring, int ld, int n_rows, const int* tokens_view_dev, const int* pos_rows_dev);
+/* Host only: the forced tokens from `state` -- while the state has exactly one live token, that token, and on to the state behind it (a per-state array
+ * built once by q4_guide_new). At most max_draft ids into draft_out; the run ends behind an EOS (token 2), at a state with two or more live tokens, and is
+ * empty for Q4_GUIDE_NONE, Q4_GUIDE_OFFTRACK or a state outside the guide. Returns the number of ids written. */
+int q4_guide_forced_run(const q4_guide* g, int state, int max_draft, int* draft_out);
 
 /* ---- sequence snapshots and prompt-prefix reuse (q4_snapshot.hip, q4_kv_copy.hip; not in the reference) --------------------------
  * Everything a sequence keeps is indexed by position -- the K / V cache [layer][seq_len][kv_dim], the token ring, the coin ring, the guide's state ring,

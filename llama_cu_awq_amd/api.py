@@ -209,6 +209,8 @@ SYMBOLS = [
     "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept", "q4_set_speculative_sampled", "q4_get_speculative_sampled", "q4_verify_tokens_sampled",
     "q4_verify_covers_sampled", "q4_verify_sample_rows", "q4_verify_accept_tokens", "q4_parse_speculative_sampled",
     "q4_logprob_topk_rows", "q4_set_pass_logprobs", "q4_get_pass_logprobs", "q4_set_pass_gqa", "q4_get_pass_gqa", "q4_parse_pass_gqa",
+    "q4_set_pass_stages", "q4_get_pass_stages", "q4_parse_pass_stages", "q4_guide_mask_rows", "q4_dry_penalty_rows", "q4_process_logits_rows",
+    "q4_guide_forced_run", "q4_spec_stats_forced",
 ]
 
 _lib = None
@@ -347,6 +349,15 @@ def lib():
         L.q4_set_pass_gqa.argtypes = [vp, i]
         L.q4_get_pass_gqa.argtypes = [vp]
         L.q4_parse_pass_gqa.argtypes = [C.c_char_p, C.POINTER(i)]
+    if hasattr(L, "q4_set_pass_stages"):           # (older builds under tools/ab.py do not have it)
+        L.q4_set_pass_stages.argtypes = [vp, i]
+        L.q4_get_pass_stages.argtypes = [vp]
+        L.q4_parse_pass_stages.argtypes = [C.c_char_p, C.POINTER(i)]
+        L.q4_guide_mask_rows.argtypes = [vp, i, vp, vp, i, i, vp, vp]
+        L.q4_dry_penalty_rows.argtypes = [vp, i, C.POINTER(DryControls), vp, i, i, i, vp, vp]
+        L.q4_process_logits_rows.argtypes = [vp, i, C.POINTER(SamplingControls), vp, vp, i, i, i, vp, vp]
+        L.q4_guide_forced_run.argtypes = [vp, i, i, vp]
+        L.q4_spec_stats_forced.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     if hasattr(L, "q4_set_greedy_screen"):         # (older builds under tools/ab.py do not have it)
         L.q4_set_greedy_screen.argtypes = [i]
         L.q4_set_greedy_screen.restype = None
@@ -571,6 +582,15 @@ def process_logits(logits, n, controls=None, logit_bias=None, tokens=None, pos=N
                                   pos.ptr if pos else None))
 
 
+def process_logits_rows(logits, n, ld, n_rows, view, pos_rows, controls=None, logit_bias=None, **kw):
+    """q4_process_logits_rows over DevBufs: the row form -- rows r < n_rows of `logits`, ld halves apart, row r at position pos_rows[r] (int32), the window
+    read from `view` (int32 tokens by absolute position: a ring prefix and the drafts behind it)."""
+    c = controls if controls is not None else SamplingControls(**kw)
+    ids, bias = _bias_arrays(logit_bias)
+    check(lib().q4_process_logits_rows(logits.ptr, n, C.byref(c), ids.ctypes.data, bias.ctypes.data, ids.shape[0], ld, n_rows, view.ptr if view else None,
+                                       pos_rows.ptr if pos_rows else None))
+
+
 def parse_dry(text):
     """q4_parse_dry: "multiplier=0.8,base=1.75,allowed=2,last_n=1024,ngram=0" -> DryControls"""
     c = DryControls()
@@ -598,6 +618,15 @@ def dry_penalty(logits, n, controls=None, breakers=None, tokens=None, pos=None, 
     c = controls if controls is not None else DryControls(**kw)
     ids = _breaker_array(breakers)
     check(lib().q4_dry_penalty(logits.ptr, n, C.byref(c), ids.ctypes.data, ids.shape[0], tokens.ptr if tokens else None, pos.ptr if pos else None))
+
+
+def dry_penalty_rows(logits, n, ld, n_rows, view, pos_rows, controls=None, breakers=None, **kw):
+    """q4_dry_penalty_rows over DevBufs: the row form -- rows r < n_rows of `logits`, ld halves apart, row r at position pos_rows[r] (int32), the window
+    read from `view` (int32 tokens by absolute position: a ring prefix and the drafts behind it)."""
+    c = controls if controls is not None else DryControls(**kw)
+    ids = _breaker_array(breakers)
+    check(lib().q4_dry_penalty_rows(logits.ptr, n, C.byref(c), ids.ctypes.data, ids.shape[0], ld, n_rows, view.ptr if view else None,
+                                    pos_rows.ptr if pos_rows else None))
 
 
 def dry_breaker_ids(tokenizer, strings=DRY_BREAKER_STRINGS):
@@ -653,6 +682,13 @@ class Guide:
         check(lib().q4_guide_new(C.byref(h), self.n_states, self.vocab_size, table.ctypes.data))
         self.h = h.value
 
+    def forced_run(self, state, max_draft):
+        """q4_guide_forced_run: the tokens the automaton forces from `state` (each state on the way has exactly one live token), at most max_draft, ending
+        behind an EOS; int32. guide.forced_run is the numpy restatement."""
+        out = np.empty(max(int(max_draft), 1), dtype=np.int32)
+        n = lib().q4_guide_forced_run(self.h, int(state), int(max_draft), out.ctypes.data)
+        return out[:n].copy()
+
     def close(self):
         if getattr(self, "h", None):
             check(lib().q4_guide_delete(self.h))
@@ -669,6 +705,12 @@ def guide_mask(logits, n, guide, state_ring, tokens, pos):
     """q4_guide_mask over DevBufs: one guide launch -- advances the automaton at the position in `pos` (one int32) from state_ring[pos - 1] and the ring
     entry tokens[pos], writes state_ring[pos] and -inf over the logits (n halves) the new state forbids."""
     check(lib().q4_guide_mask(logits.ptr, n, guide.h, state_ring.ptr, tokens.ptr, pos.ptr))
+
+
+def guide_mask_rows(logits, n, ld, n_rows, guide, state_ring, view, pos_rows):
+    """q4_guide_mask_rows over DevBufs: the row form -- rows r < n_rows of `logits`, ld halves apart, at positions pos_rows[r] = pos_rows[0] + r; block r walks
+    the automaton from state_ring[pos_rows[0] - 1] over view[pos_rows[0] .. pos_rows[r]], writes state_ring[pos_rows[r]] and masks row r."""
+    check(lib().q4_guide_mask_rows(logits.ptr, n, guide.h, state_ring.ptr, ld, n_rows, view.ptr, pos_rows.ptr))
 
 
 def copy_runs(dst, src, outer, dst_stride, src_stride, run_bytes, dst_offset=0, src_offset=0):
@@ -826,7 +868,7 @@ class Transformer:
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
                  logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None,
-                 pass_logprobs=False, pass_gqa=False):
+                 pass_logprobs=False, pass_gqa=False, pass_stages=False):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -879,6 +921,8 @@ class Transformer:
                 self.set_pass_logprobs(True)
             if pass_gqa:
                 self.set_pass_gqa(True)
+            if pass_stages:
+                self.set_pass_stages(True)
             if sampling is not None:
                 self.set_sampling(**sampling)
             if logit_bias is not None:
@@ -1230,6 +1274,22 @@ class Transformer:
     def pass_gqa(self):
         """q4_get_pass_gqa"""
         return bool(lib().q4_get_pass_gqa(self.h))
+
+    def set_pass_stages(self, on):
+        """q4_set_pass_stages: verify passes also with a guide, DRY or the sampling controls on (their row forms), prompt passes also with a guide or the
+        adaptive truncation on, and the guide's forced tokens as drafts in the token loop; off by default. Tokens, K / V rows, logits, rng_state and the
+        guide's states below the position are the per-token run's, byte for byte."""
+        check(lib().q4_set_pass_stages(self.h, 1 if on else 0))
+
+    def pass_stages(self):
+        """q4_get_pass_stages"""
+        return bool(lib().q4_get_pass_stages(self.h))
+
+    def spec_stats_forced(self):
+        """(drafted, accepted) of the drafts the guide's forced run gave the token loop (q4_spec_stats_forced); they are part of spec_stats' totals"""
+        a, b = C.c_longlong(), C.c_longlong()
+        check(lib().q4_spec_stats_forced(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def logprobs_k(self):
         return lib().q4_get_logprobs_k(self.h)

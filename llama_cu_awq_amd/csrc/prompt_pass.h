@@ -27,7 +27,9 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // With log-probability records on (admitted only with q4_set_pass_logprobs on): behind the layer loop the verify pass's classifier (spec_verify.h) over the
 // n residual rows, the row form of the record launch (q4_logprobs.hip; the target of row r is the ring's tokens[pos0 + r + 1]) and a copy of the last row
 // to RunState::logits -- records pos0 .. pos0 + n - 1 and the logits are what n prompt steps with records leave, byte for byte -- then the finish launch.
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
+// sampler (q4_set_pass_stages admits the pass with the guide or the adaptive truncation on): what a prompt group of steps does in front of its launches --
+// the guide's state ring and, where the sampler has the adaptive launch on and the model has the rings, Mirostat's mu ring put to NONE at pos0 .. pos0 + n - 1.
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n, const Sampler* sampler = nullptr);
 void pass_release(Model* m);   // q4_free_transformer: the scratch of this model's prompt and verify passes (Model::pass)
 // q4_passes.hip. A prompt pass in place of the token loop's per-token prompt steps from `pos`: how many positions it takes, 0 for none (its comment there)
 int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int num_prompt_tokens, int steps, int off);
@@ -40,6 +42,7 @@ int prompt_pass_rows(Model* m, const Config* p);
 // raw rows of a pass under the sampler with records), each allocated on first use and released by pass_release
 int pass_logit_rows(Model* m, const Config* p);
 int pass_side_rows(Model* m, const Config* p);
+int pass_draft_view(Model* m, const Config* p);   // Model::pass.view, [seq_len] ints: the draft view of a verify pass with logit stages (spec_verify.h)
 int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
 
 }  // namespace q4

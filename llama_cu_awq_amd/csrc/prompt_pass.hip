@@ -512,7 +512,7 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 
 // ---- host ------------------------------------------------------------------------------------------
 void pass_release(Model* m) {
-    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side})
+    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side, (void*)m->pass.view})
         if (d) (void)hipFree(d);
     m->pass = PassScratch{};
 }
@@ -552,6 +552,14 @@ int pass_logit_rows(Model* m, const Config* p) {
 int pass_side_rows(Model* m, const Config* p) {
     if (!m->pass.lp_side && hipMalloc((void**)&m->pass.lp_side, (size_t)PROMPT_PASS_MAX * p->vocab_size * sizeof(q4_half)) != hipSuccess) {
         (void)hipGetLastError(); m->pass.lp_side = nullptr; return Q4_ERR_ALLOC;
+    }
+    return Q4_OK;
+}
+
+// The draft view of a verify pass with logit stages (spec_verify.h): seq_len tokens by absolute position, allocated on first use
+int pass_draft_view(Model* m, const Config* p) {
+    if (!m->pass.view && hipMalloc((void**)&m->pass.view, (size_t)p->seq_len * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError(); m->pass.view = nullptr; return Q4_ERR_ALLOC;
     }
     return Q4_OK;
 }
@@ -711,7 +719,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     return Q4_OK;
 }
 
-int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
+int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n, const Sampler* sampler) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
     const int dim = p->dim;
     const bool records = m->logprobs_k >= 0;               // (admitted with records on: q4_set_pass_logprobs, q4_passes.hip)
@@ -719,6 +727,9 @@ int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, M
     Q4_TRY(prompt_pass_rows(m, p));
     if (records) Q4_TRY(pass_logit_rows(m, p));
     const PassScratch* const b = &m->pass;
+    // q4_set_pass_stages: state by position -- the guide's automaton, Mirostat's mu -- is put to NONE at the pass's positions, in stream order in front of
+    // the pass, as run_transformer_steps_screenable does for a prompt group (prompt_pass_tokens admits either only with the switch on)
+    Q4_TRY(stages_clear_positions(sampler, m, pos0, n));
     Q4_LAUNCH(prompt_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, b->x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens,
               (const int*)s->pos, b->pos);
     Q4_LAUNCH_CHECK();

@@ -430,7 +430,8 @@ void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
 
 }  // namespace
 
-LogitStage q4::adaptive_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
+// (no row form: Mirostat's side buffer belongs to a launch, not to a position)
+LogitStage q4::adaptive_stage = {stage_on, prepare, launch_step, stage_block, stage_forget, nullptr};
 
 namespace q4 {
 

@@ -10,6 +10,9 @@
 //      logit_block.h's finish. One writer per logit: no atomics, no arrival order, the same input gives the same bytes on every launch.
 // The vocabulary is never scanned: the cost does not depend on n. Worst case, a window of one repeated token: 4095 candidates, every M 64, 4095 x 4
 // comparisons per thread over broadcast 16-byte LDS reads. No ring entry or breaker id indexes anything before it has been checked against [0, n).
+// The row form (ROWS; a verify pass with q4_set_pass_stages on, q4_dry_penalty_rows): block r of up to PROMPT_PASS_MAX is row r -- its logits `ld` halves
+// behind row 0's, its position pPos[r], and `tokens` is the pass's draft view (by absolute position: the ring up to the pass's first position, the drafts
+// behind it), not the pinned ring. Everything between those three substitutions is the step's one body.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -22,6 +25,7 @@
 #include "sampler_side.h"
 #include "logit_block.h"
 #include "option_text.h"
+#include "prompt_pass.h"
 #pragma clang fp contract(off)
 using namespace q4;
 
@@ -44,7 +48,8 @@ struct DryParams {
 };
 
 // (finish and the block-wide int reductions: logit_block.h)
-__global__ void __launch_bounds__(LB_T) dry_kernel(q4_half* logits, int n, const DryParams* __restrict__ prm, const int* tokens, const int* pPos) {
+template <bool ROWS = false>
+__global__ void __launch_bounds__(LB_T) dry_kernel(q4_half* logits, int n, const DryParams* __restrict__ prm, const int* tokens, const int* pPos, int ld) {
     __shared__ __attribute__((aligned(16))) int s_win[LB_T * DR_E];      // the window, local index k = ring index - start
     __shared__ __attribute__((aligned(16))) int s_tok[LB_T * DR_E];      // per candidate: the token behind it, -1: outside [0, n)
     __shared__ __attribute__((aligned(16))) int s_key[LB_T * DR_E];      // per candidate: its slot k, then M * 4096 + 4095 - c
@@ -53,7 +58,8 @@ __global__ void __launch_bounds__(LB_T) dry_kernel(q4_half* logits, int n, const
     const int tid = threadIdx.x;
     const int last_n = min(max(prm->last_n, 0), (int)Q4_MAX_DRY_WINDOW);
     if (last_n == 0 || tokens == nullptr || pPos == nullptr) return;   // (block-uniform, like every return below)
-    const int pos = *pPos;
+    const int pos = ROWS ? pPos[blockIdx.x] : *pPos;
+    if (ROWS) logits += (size_t)blockIdx.x * ld;
     if (pos < 1 || pos >= Q4_MAX_SEQ_LEN) return;                      // (position 0: a window of one entry has no candidate)
     const int start = max(0, pos + 1 - last_n);
     const int L = pos + 1 - start;                                     // 1 .. 4096
@@ -234,7 +240,14 @@ SamplerSides<Dry>& sides() {
 DeviceSide g_op;                       // q4_dry_penalty's own block and bitmap
 
 int launch(q4_half* logits, int n, const DryParams* dev, const int* tokens, const int* pPos) {
-    Q4_LAUNCH(dry_kernel, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
+    Q4_LAUNCH(dry_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos, 0);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+// the row form: view the draft view (device), pos_rows the rows' positions (device)
+int launch_rows_of(q4_half* logits, int n, int ld, int n_rows, const DryParams* dev, const int* view, const int* pos_rows) {
+    if (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7)) return Q4_ERR_ARG;
+    Q4_LAUNCH(dry_kernel<true>, dim3(n_rows), dim3(LB_T), 0, logits, n, dev, view, pos_rows, ld);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -260,12 +273,15 @@ bool stage_on(const Sampler* sampler, const Model*) { return sides().on(sampler)
 int launch_step(const void* block, const Model*, const Config* p, RunState* s) {
     return launch(s->logits, p->vocab_size, (const DryParams*)block, &(s->shared_data->tokens[0]), s->pos);
 }
+int launch_rows(const void* block, const Model*, const Config* p, q4_half* rows, int ld, int n_rows, const int* view, const int* pos_rows) {
+    return launch_rows_of(rows, p->vocab_size, ld, n_rows, (const DryParams*)block, view, pos_rows);
+}
 const void* stage_block(const Sampler* sampler) { return sides().block(sampler); }
 void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
 
 }  // namespace
 
-LogitStage q4::dry_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
+LogitStage q4::dry_stage = {stage_on, prepare, launch_step, stage_block, stage_forget, launch_rows};
 
 extern "C" {
 
@@ -331,6 +347,14 @@ int q4_dry_penalty(q4_half* logits, int n, const q4_dry_controls* controls, cons
     if (dry_off(controls) || !tokens || !pPos) return Q4_OK;
     Q4_TRY(upload(g_op, controls, std::vector<int>(breaker_ids, breaker_ids + n_breakers), n));
     return launch(logits, n, g_op.dev, tokens, pPos);
+}
+int q4_dry_penalty_rows(q4_half* logits, int n, const q4_dry_controls* controls, const int* breaker_ids, int n_breakers, int ld, int n_rows,
+                        const int* tokens_view_dev, const int* pos_rows_dev) {
+    if (!logits || n < 1 || !controls || !dry_valid(controls) || !breakers_valid(breaker_ids, n_breakers, n)) return Q4_ERR_ARG;
+    if (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7)) return Q4_ERR_ARG;
+    if (dry_off(controls) || !tokens_view_dev || !pos_rows_dev) return Q4_OK;
+    Q4_TRY(upload(g_op, controls, std::vector<int>(breaker_ids, breaker_ids + n_breakers), n));
+    return launch_rows_of(logits, n, ld, n_rows, g_op.dev, tokens_view_dev, pos_rows_dev);
 }
 
 }  // extern "C"

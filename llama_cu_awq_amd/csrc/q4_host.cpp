@@ -596,6 +596,15 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and passes while logit stages are on, with the guide's forced drafts (q4_set_pass_stages): Q4_PASS_STAGES=1
+    const char* pass_stages = getenv("Q4_PASS_STAGES");
+    if (pass_stages && *pass_stages) {
+        int on = 0;
+        if (q4_parse_pass_stages(pass_stages, &on) || q4_set_pass_stages(&transformer, on)) {
+            fprintf(stderr, "Q4_PASS_STAGES: cannot use '%s' (0 or 1: verify passes also with a guide, DRY or the sampling controls on, prompt passes also with a guide or Mirostat)\n", pass_stages);
+            exit(EXIT_FAILURE);
+        }
+    }
     // ... and how far prompt and verify passes go (q4_set_pass_context): Q4_PASS_CONTEXT=2048; values up to 256 are the default
     const char* pass_context = getenv("Q4_PASS_CONTEXT");
     if (pass_context && *pass_context) {

@@ -18,6 +18,9 @@
 //      float(l_i) - float(m) >= logf(min_p) (the host's logf, a kernel argument); else -inf.
 // No atomics, no arrival order: the same input gives the same bytes on every launch. A NaN or an out-of-range token never faults: the window and the
 // bias ids are checked against [0, n) before they index anything.
+// The row form (ROWS; a verify pass with q4_set_pass_stages on, q4_process_logits_rows): block r of up to PROMPT_PASS_MAX is row r -- its logits `ld` halves
+// behind row 0's, its position pPos[r], and `tokens` is the pass's draft view (by absolute position: the ring up to the pass's first position, the drafts
+// behind it), not the pinned ring. Everything between those three substitutions is the step's one body.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -28,6 +31,7 @@
 #include "sampler_side.h"
 #include "logit_block.h"
 #include "option_text.h"
+#include "prompt_pass.h"
 #pragma clang fp contract(off)
 using namespace q4;
 
@@ -63,9 +67,9 @@ __device__ __forceinline__ int count_eq(const u32x4& k, unsigned T) {
 }
 
 // REG: n <= 32 x 1024, the thread's chunks and their keys stay in registers. tokens / pPos null: no window.
-template <bool REG>
+template <bool REG, bool ROWS = false>
 __global__ void __launch_bounds__(LB_T) logit_process_kernel(q4_half* logits, int n, const LogitParams* __restrict__ prm, const int* tokens,
-                                                             const int* pPos) {
+                                                             const int* pPos, int ld) {
     __shared__ __attribute__((aligned(16))) int s_win[LB_T];
     __shared__ unsigned s_wbias[LB_T];
     __shared__ int red[2][LB_W];
@@ -74,10 +78,12 @@ __global__ void __launch_bounds__(LB_T) logit_process_kernel(q4_half* logits, in
     const int last_n = min(max(prm->last_n, 0), (int)Q4_MAX_PENALTY_WINDOW);
     const float repeat = prm->repeat, presence = prm->presence, frequency = prm->frequency, log_min_p = prm->log_min_p;
 
+    if (ROWS) logits += (size_t)blockIdx.x * ld;
+
     // ---- steps 1 - 3. The window entry of this thread is requested first (pinned host memory) and used last
     int L = 0, w = -1;
     if (last_n > 0 && tokens != nullptr && pPos != nullptr) {
-        const int pos = *pPos;
+        const int pos = ROWS ? pPos[blockIdx.x] : *pPos;
         if (pos >= 0 && pos < Q4_MAX_SEQ_LEN) {
             const int start = max(0, pos + 1 - last_n);
             L = pos + 1 - start;                               // (block-uniform, <= 1024)
@@ -272,8 +278,16 @@ SamplerSides<Controls>& sides() {
 DeviceBlock<LogitParams> g_op;         // q4_process_logits' own block
 
 int launch(q4_half* logits, int n, const LogitParams* dev, const int* tokens, const int* pPos) {
-    if (n <= LB_T * PL_Q * 8) Q4_LAUNCH(logit_process_kernel<true>, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
-    else Q4_LAUNCH(logit_process_kernel<false>, dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos);
+    if (n <= LB_T * PL_Q * 8) Q4_LAUNCH((logit_process_kernel<true, false>), dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos, 0);
+    else Q4_LAUNCH((logit_process_kernel<false, false>), dim3(1), dim3(LB_T), 0, logits, n, dev, tokens, pPos, 0);
+    Q4_LAUNCH_CHECK();
+    return Q4_OK;
+}
+// the row form: view the draft view (device), pos_rows the rows' positions (device); both null: no window, as in the step
+int launch_rows_of(q4_half* logits, int n, int ld, int n_rows, const LogitParams* dev, const int* view, const int* pos_rows) {
+    if (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7)) return Q4_ERR_ARG;
+    if (n <= LB_T * PL_Q * 8) Q4_LAUNCH((logit_process_kernel<true, true>), dim3(n_rows), dim3(LB_T), 0, logits, n, dev, view, pos_rows, ld);
+    else Q4_LAUNCH((logit_process_kernel<false, true>), dim3(n_rows), dim3(LB_T), 0, logits, n, dev, view, pos_rows, ld);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
 }
@@ -299,12 +313,15 @@ bool stage_on(const Sampler* sampler, const Model*) { return sides().on(sampler)
 int launch_step(const void* block, const Model*, const Config* p, RunState* s) {
     return launch(s->logits, p->vocab_size, (const LogitParams*)block, &(s->shared_data->tokens[0]), s->pos);
 }
+int launch_rows(const void* block, const Model*, const Config* p, q4_half* rows, int ld, int n_rows, const int* view, const int* pos_rows) {
+    return launch_rows_of(rows, p->vocab_size, ld, n_rows, (const LogitParams*)block, view, pos_rows);
+}
 const void* stage_block(const Sampler* sampler) { return sides().block(sampler); }
 void stage_forget(const Sampler* sampler) { sides().forget(sampler); }
 
 }  // namespace
 
-LogitStage q4::controls_stage = {stage_on, prepare, launch_step, stage_block, stage_forget};
+LogitStage q4::controls_stage = {stage_on, prepare, launch_step, stage_block, stage_forget, launch_rows};
 
 extern "C" {
 
@@ -372,6 +389,16 @@ int q4_process_logits(q4_half* logits, int n, const q4_sampling_controls* contro
     g_op.dirty = true;
     Q4_TRY(g_op.upload());
     return launch(logits, n, g_op.dev, tokens, pPos);
+}
+int q4_process_logits_rows(q4_half* logits, int n, const q4_sampling_controls* controls, const int* bias_ids, const float* bias, int n_bias, int ld,
+                           int n_rows, const int* tokens_view_dev, const int* pos_rows_dev) {
+    if (!logits || n < 1 || !controls || !controls_valid(controls) || controls->top_k > n || !bias_valid(bias_ids, bias, n_bias, n)) return Q4_ERR_ARG;
+    if (n_rows < 1 || n_rows > PROMPT_PASS_MAX || ld < n || (ld & 7)) return Q4_ERR_ARG;
+    if (controls_neutral(controls) && n_bias == 0) return Q4_OK;
+    fill_params(&g_op.host, controls, bias_ids, bias, n_bias);
+    g_op.dirty = true;
+    Q4_TRY(g_op.upload());
+    return launch_rows_of(logits, n, ld, n_rows, g_op.dev, tokens_view_dev, pos_rows_dev);
 }
 
 }  // extern "C"

@@ -41,6 +41,7 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
         const int start = attempt == 0 ? start_pos : 0;      // the retry after a time-out trusts no row
         int pos = start, queued = start, group_start = start, off = 0;
         int verify_pos = -1, verify_drafts = 0;              // a verify pass queued at verify_pos whose outcome the host has not read yet
+        bool verify_forced = false;                          // ... whose drafts are the guide's forced run (q4_spec_stats_forced)
         Q4_TRY(start == 0 ? q4_reset_sequence(&t->state, prompt_tokens, num_prompt_tokens) : q4_resume_sequence(&t->state, prompt_tokens, num_prompt_tokens, start));
         if (loop->on_attempt) loop->on_attempt(loop->ctx, attempt, start);
         for (int i = 0; i < start; i++) (void)random_f32(&sampler->rng_state);
@@ -53,7 +54,7 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                 const int m = t->state.shared_data->pos - pos;
                 if (m < 0 || m > verify_drafts) return Q4_ERR_HIP;
                 for (int i = 0; i <= m; i++) (void)random_f32(&sampler->rng_state);
-                count_verify_pass(sm, verify_drafts, m);
+                count_verify_pass(sm, verify_drafts, m, verify_forced);
                 queued = pos + m;
                 verify_pos = -1;
             }
@@ -75,8 +76,14 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                     Q4_TRY(q4_wait_pos(&t->state, pos));
                     int room = sm->spec_draft;
                     while (room > 1 && !verify_covers(t, sm, sampler, pos, room, steps, off)) room--;
-                    if (pos == 0 || t->state.shared_data->tokens[pos] != 2)      // (behind an EOS the loop stops: no pass)
-                        nd = ask_drafter(sm, (const int*)t->state.shared_data->tokens, pos + 1, room, t->config.vocab_size, draft);
+                    verify_forced = false;
+                    if (pos == 0 || t->state.shared_data->tokens[pos] != 2) {    // (behind an EOS the loop stops: no pass)
+                        // q4_set_pass_stages with a guide: where the automaton's state behind ring[pos] leaves one live token, the next tokens are known
+                        // before the model runs -- the forced run first, the model's drafter only where it is empty
+                        if (sm->pass_stages && sm->guide) Q4_TRY(guide_forced_draft(sm, (const int*)t->state.shared_data->tokens, pos, room, draft, &nd));
+                        verify_forced = nd > 0;
+                        if (!nd) nd = ask_drafter(sm, (const int*)t->state.shared_data->tokens, pos + 1, room, t->config.vocab_size, draft);
+                    }
                 }
                 const int k = np ? np : nd ? 1 : q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);
                 group_start = pos;
@@ -87,12 +94,12 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                     Sampler* const vs = sampler->temperature != 0.0f ? sampler : nullptr;
                     const float* coins = nullptr;
                     if (vs) Q4_TRY(stage_pass_coins(vs, &t->config, pos, nd, &coins));
-                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, pos, draft, nd, vs, coins));
+                    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, sm, pos, draft, nd, vs, coins, sampler));
                     verify_pos = pos;
                     verify_drafts = nd;
                 } else if (np) {      // the prompt-only positions pos .. pos + np - 1 in one pass over the weights; one coin per position, as the steps draw them
                     for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
-                    Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, pos - off, np));
+                    Q4_TRY(run_prompt_pass(&t->config, &t->state, &t->weights, sm, pos - off, np, sampler));
                     g_prompt_passes++;
                 } else {
                     Q4_TRY(run_transformer_steps_screenable(pos - off, k, pos >= num_prompt_tokens - 1, &t->config, &t->state, &t->weights, 0, sampler, group_may_screen(pos - off, k, steps - off)));
@@ -226,7 +233,7 @@ int q4_score_ids(Transformer* t, Sampler* sampler, const int* tokens_with_bos, i
             const int np = m->pass_logprobs ? prompt_pass_tokens(t, m, sampler, pos, num_tokens + 1, num_tokens, 0) : 0;
             if (np >= 2) {
                 for (int i = 0; i < np; i++) (void)random_f32(&sampler->rng_state);
-                rc = run_prompt_pass(config, state, &t->weights, m, pos, np);
+                rc = run_prompt_pass(config, state, &t->weights, m, pos, np, sampler);
                 g_prompt_passes++;
                 pos += np;
                 continue;

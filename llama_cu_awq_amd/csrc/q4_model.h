@@ -11,8 +11,9 @@ namespace q4 {
 
 // The scratch of the prompt and verify passes (prompt_pass.h, spec_verify.h), each allocation made on first use and released by pass_release. slab: the rows x / q / xb
 // / hb, their positions and the attention launch's sink (u32x2v granules); records: the split passes' flash-decode records; logit_rows: the logits of a verify pass or of a
-// prompt pass with records (pass_logit_rows) and the tokens behind them; lp_side: [PROMPT_PASS_MAX][vocab] raw rows of a verify pass under the sampler with records (pass_side_rows)
-struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; q4_half* lp_side; };
+// prompt pass with records (pass_logit_rows) and the tokens behind them; lp_side: [PROMPT_PASS_MAX][vocab] raw rows of a verify pass under the sampler with records (pass_side_rows);
+// view: [seq_len] the draft view of a verify pass with logit stages (pass_draft_view; q4_set_pass_stages): tokens by absolute position, the ring up to the pass's first position and its drafts behind
+struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; q4_half* lp_side; int* view; };
 // every Transformer owns two HBM slabs (weights, run state) instead of ~750 small allocations: layers sit
 // back to back in HBM in the order the token loop streams them. ONE record per model: q4_build_transformer registers it as soon as its
 // first allocation exists, q4_free_transformer is the only place that releases and forgets it.
@@ -43,6 +44,7 @@ struct Model {
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
     bool pass_logprobs = false;     // q4_set_pass_logprobs: prompt and verify passes (and q4_score_ids through prompt passes) also while the records are on
     bool pass_gqa = false;          // q4_set_pass_gqa: prompt and verify passes also for the grouped-query 4096-wide shape (prompt_pass_covers)
+    bool pass_stages = false;       // q4_set_pass_stages: verify passes also with a guide, DRY or the sampling controls on (their row forms), prompt passes also with a guide or the adaptive truncation on
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
     const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model
     int* guide_state = nullptr;     // [guide_len = seq_len] the automaton's state by position (Q4_GUIDE_NONE / Q4_GUIDE_OFFTRACK)
@@ -60,6 +62,7 @@ struct Model {
     q4_drafter_fn drafter = nullptr;  // q4_set_drafter: null, the built-in drafter (q4_spec_draft)
     void* drafter_ctx = nullptr;
     long long spec_passes = 0, spec_drafted = 0, spec_accepted = 0;   // q4_spec_stats
+    long long forced_drafted = 0, forced_accepted = 0;                // q4_spec_stats_forced: of those, the drafts the guide's forced run gave and how many were accepted
     PassScratch pass = {};          // nothing until the model's first prompt or verify pass
     bool rows_suspect = false;      // q4_handoff_status reported a time-out and no q4_reset_sequence has followed: the K / V rows below the position are not to be reused (q4_common_prefix)
 };
@@ -88,6 +91,11 @@ int run_network(const int* pPos, const Config* p, RunState* s, const Transformer
 void drop_graphs_of(const RunState* s);   // the model's captured graphs, after the launch stream has drained
 void drop_logprob_graphs_of(const RunState* s);   // ... those that contain the log-probability launch only
 bool any_stage_on(const Sampler* sampler, const Model* m);        // a logit stage of the table below is on for this sampler and model
+bool stages_take_rows(const Sampler* sampler, const Model* m);    // ... and every stage that is on has a row form (LogitStage::launch_rows)
+// The stages that are on, in table order, over the n_rows logit rows of a verify pass (`ld` halves apart): prepare (never inside a capture: no graph holds a
+// pass), then the row form. view: the pass's draft view, pos_rows: the rows' positions (both device). Q4_ERR_ARG where a stage that is on has no row form
+int launch_stage_rows(const Sampler* sampler, Model* m, const Config* p, q4_half* rows, int ld, int n_rows, const int* view, const int* pos_rows);
+int stages_clear_positions(const Sampler* sampler, const Model* m, int pos, int n);   // a prompt pass's positions: state by position to NONE, as a prompt group of steps does
 int graph_bin(int seq_len, const Config* p, int* seq_len_bin_out);   // the graph bin of a step whose sequence length is seq_len: its index, and its size
 // q4_logprobs.hip. The record launch of a step (in front of the sampler: reads the position before it advances) and the chosen token's look-up behind
 // the sampler of a sampled step
@@ -112,6 +120,10 @@ struct LogitStage {
     // that block are gone and the stream has drained. Both null for a stage that lives with the model
     const void* (*block)(const Sampler* sampler);
     void (*forget)(const Sampler* sampler);
+    // The row form, for a verify pass with q4_set_pass_stages on: block r of n_rows <= PROMPT_PASS_MAX rewrites rows + r * ld at position pos_rows[r] and reads
+    // its tokens from the draft view (device, by absolute position) instead of the pinned ring; what row r receives is byte for byte what `launch` writes for
+    // that row alone at that position. Null: the stage has no row form and a pass is not admitted while it is on (the adaptive truncation)
+    int (*launch_rows)(const void* block, const Model* m, const Config* p, q4_half* rows, int ld, int n_rows, const int* view, const int* pos_rows);
 };
 // q4_step.hip's table, in launch order: the guide's mask (q4_guide.hip; per model), DRY (q4_dry.hip), the sampling controls (q4_logit_process.hip:
 // top-k counts what both left), the adaptive truncation (q4_adaptive.hip: typical-p and Mirostat see what top-k and min-p left)
@@ -129,6 +141,10 @@ void adaptive_release(Model* m);
 int guide_clear_positions(const Model* m, int pos, int nsteps);
 int guide_clear_ring(const Model* m);
 void guide_release(Model* m);
+// The token loop's forced drafts (q4_set_pass_stages; the device has published position `pos`, so the guide launch of the step in front has run): the state
+// behind ring[pos] -- state[pos - 1] read back with one 4-byte copy (NONE at pos 0), then the kernel's rule 2 on the host, its table entry one 2-byte copy --
+// and from it q4_guide_forced_run's tokens, at most max_draft, into draft; *n_out how many
+int guide_forced_draft(const Model* m, const int* ring, int pos, int max_draft, int* draft, int* n_out);
 // q4_kv_copy.hip. One launch that copies up to KV_COPY_MAX_RUNS strided runs on the launch stream: run r of an entry moves run_bytes bytes from
 // src + r * src_stride to dst + r * dst_stride, r < outer. Q4_ERR_ARG without a launch: a null pointer, a negative field, run_bytes above a stride when
 // outer > 1, source and destination ranges that overlap

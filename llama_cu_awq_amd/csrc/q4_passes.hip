@@ -54,7 +54,7 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // (pass_attention_plan: the V-slice forms 5 / 6, or one split-context form 4 / 2 / 3) -- so never the level-1 redo after a time-out --; the geometry
 // prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps`, below the bound of q4_set_pass_context and inside
 // the bin of `pos`; no log-probability records (they describe prompt steps' logits) or q4_set_pass_logprobs on (pass_records_ok: the pass then runs the
-// classifier and writes the records); neither the guide nor the adaptive truncation on (their state by
+// classifier and writes the records); neither the guide nor the adaptive truncation on unless the model's q4_set_pass_stages switch is (their state by
 // position is put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.) q4_score_ids asks too, with that
 // switch on: there every position is prompt-only (num_prompt_tokens = steps + 1).
 // Records and passes: records off, nothing to ask. On, a pass is taken only with the model's q4_set_pass_logprobs switch on and a shape that the pass's
@@ -72,24 +72,25 @@ int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* samp
     if (n > steps - pos) n = steps - pos;
     if (n > pass_bin_end(pos) - pos) n = pass_bin_end(pos) - pos;
     if (n > pass_bound(p) - pos) n = pass_bound(p) - pos;
-    if (n < 2 || guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m) || !prompt_pass_covers(p, m)) return 0;
+    // (state by position: the steps put it to NONE per prompt group; with q4_set_pass_stages on run_prompt_pass does the same)
+    if (n < 2 || (!m->pass_stages && (guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m))) || !prompt_pass_covers(p, m)) return 0;
     PassAttention plan;
     return pass_attention_plan(p, &t->state, pos, n, &plan) ? n : 0;
 }
 
 // A verify pass (spec_verify.h) at position `pos` with n_draft drafts, positions pos .. pos + n_draft: what a prompt pass requires -- the
 // fusion level in force >= 3 with an attention form the pass reproduces at every position (pass_attention_plan), prompt_pass_covers' geometry (fp16 cache,
-// unmasked stream), no log-probability records or q4_set_pass_logprobs on (pass_records_ok), no guide, no context-shift offset, every position inside the bin of `pos`, below the bound of
+// unmasked stream), no log-probability records or q4_set_pass_logprobs on (pass_records_ok), no guide unless q4_set_pass_stages is on, no context-shift offset, every position inside the bin of `pos`, below the bound of
 // q4_set_pass_context and inside seq_len -- plus a classifier shape the pass's launch
 // takes. A token loop adds (sampler non-null): temperature 0 -- or, with the model's spec_sampled switch on, a sampler the row form of the sampling
-// launches takes (sample_rows_covers) --, no logit stage on, every position inside `steps`. With all of that off a greedy generating
+// launches takes (sample_rows_covers) --, no logit stage on (q4_set_pass_stages: none without a row form, and none together with records), every position inside `steps`. With all of that off a greedy generating
 // step leaves, by position: its K / V rows, ring[pos + 1], the two position words; and, not by position: RunState::logits, RunState::x (un-normalised
 // behind the strips classifier; what the pass writes), the scratch vectors xb / hb / q / att (rewritten by every step before it reads them), the hand-off
 // epoch (never rewound; a pass does not advance it, as a prompt pass does not), the screen's tallies (q4_screen_candidates counts screened steps: a pass
 // screens nothing). Guide states, Mirostat's mu, the coin ring and logits_array are written only by what the admission excludes; the record rings by the
 // pass itself where q4_set_pass_logprobs admits it with records on (spec_verify.h: records p .. p + D, those of rejected drafts at or above the position).
 bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off) {
-    if (g_fusion < 3 || off != 0 || !m || !pass_records_ok(&t->config, m) || m->guide || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
+    if (g_fusion < 3 || off != 0 || !m || !pass_records_ok(&t->config, m) || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
     const Config* p = &t->config;
     if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps) return false;
     if (sampler && sampler->temperature != 0.0f) {
@@ -97,7 +98,9 @@ bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler,
         // a negative one keeps the one-block softmax of the step) and a vocabulary that is the model's
         if (!m->spec_sampled || sampler->vocab_size != p->vocab_size || !sample_rows_covers(sampler)) return false;
     }
-    if (sampler && any_stage_on(sampler, m)) return false;
+    // Logit stages (the guide is on with or without a sampler): only with q4_set_pass_stages on, every stage that is on with a row form (not the adaptive
+    // truncation) and no log-probability records (a stage step keeps the raw logits aside and looks its token up behind the argmax: no row form of that)
+    if (any_stage_on(sampler, m) && (!m->pass_stages || !stages_take_rows(sampler, m) || m->logprobs_k >= 0)) return false;
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return false;
     PassAttention plan;
     return pass_attention_plan(p, &t->state, pos, n_draft + 1, &plan);
@@ -110,7 +113,10 @@ int ask_drafter(const Model* m, const int* ring, int n_tokens, int max_draft, in
         if (draft[i] < 0 || draft[i] >= vocab) { n = i; break; }
     return n < 0 ? 0 : n;
 }
-void count_verify_pass(Model* m, int n_draft, int accepted) { m->spec_passes++; m->spec_drafted += n_draft; m->spec_accepted += accepted; }
+void count_verify_pass(Model* m, int n_draft, int accepted, bool forced) {
+    m->spec_passes++; m->spec_drafted += n_draft; m->spec_accepted += accepted;
+    if (forced) { m->forced_drafted += n_draft; m->forced_accepted += accepted; }
+}
 
 // The one host side of q4_verify_tokens and q4_verify_tokens_sampled (sampler null: the greedy form, which draws no coin). Argument errors in front of the
 // synchronise, Q4_NOT_ADMITTED from rows_suspect or the admission, Q4_ERR_HIP for an advance outside [0, n_draft].
@@ -124,7 +130,7 @@ static int verify_tokens(Transformer* t, Sampler* sampler, const int* draft, int
     if (m->rows_suspect || !(sampler ? q4_verify_covers_sampled(t, sampler, pos, n_draft) : q4_verify_covers(t, pos, n_draft))) return Q4_NOT_ADMITTED;
     const float* coins = nullptr;
     if (sampler) Q4_TRY(stage_pass_coins(sampler, &t->config, pos, n_draft, &coins));
-    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, pos, draft, n_draft, sampler, coins));
+    Q4_TRY(run_verify_pass(&t->config, &t->state, &t->weights, m, pos, draft, n_draft, sampler, coins, sampler));
     Q4_HIP(hipStreamSynchronize(g_stream));
     const int acc = t->state.shared_data->pos - (pos + 1);
     if (acc < 0 || acc > n_draft) return Q4_ERR_HIP;
@@ -263,6 +269,30 @@ int q4_get_pass_gqa(const Transformer* t) {
 int q4_parse_pass_gqa(const char* text, int* on) {     // the CLI's Q4_PASS_GQA: "0" or "1", nothing else
     if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
     *on = text[0] - '0';
+    return Q4_OK;
+}
+// Passes while a logit stage is on (verify passes: the guide, DRY, the sampling controls through their row forms; prompt passes: the guide, the adaptive
+// truncation) and the guide's forced drafts in the token loop: per model, off by default. No captured graph contains a pass: nothing to drop.
+int q4_set_pass_stages(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->pass_stages = on != 0;
+    return Q4_OK;
+}
+int q4_get_pass_stages(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->pass_stages ? 1 : 0;
+}
+int q4_parse_pass_stages(const char* text, int* on) {     // the CLI's Q4_PASS_STAGES: "0" or "1", nothing else
+    if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
+    *on = text[0] - '0';
+    return Q4_OK;
+}
+int q4_spec_stats_forced(const Transformer* t, long long* drafted, long long* accepted) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    if (drafted) *drafted = m->forced_drafted;
+    if (accepted) *accepted = m->forced_accepted;
     return Q4_OK;
 }
 int q4_get_speculative_sampled(const Transformer* t) {

@@ -87,6 +87,32 @@ bool any_stage_on(const Sampler* sampler, const Model* m) {
         if (st->on(sampler, m)) return true;
     return false;
 }
+bool stages_take_rows(const Sampler* sampler, const Model* m) {
+    bool any = false;
+    for (const LogitStage* st : STAGES)
+        if (st->on(sampler, m)) {
+            if (!st->launch_rows) return false;
+            any = true;
+        }
+    return any;
+}
+int launch_stage_rows(const Sampler* sampler, Model* m, const Config* p, q4_half* rows, int ld, int n_rows, const int* view, const int* pos_rows) {
+    for (const LogitStage* st : STAGES)
+        if (st->on(sampler, m)) {
+            const void* block = nullptr;
+            if (!st->launch_rows) return Q4_ERR_ARG;
+            Q4_TRY(st->prepare(sampler, m, p, &block));
+            Q4_TRY(st->launch_rows(block, m, p, rows, ld, n_rows, view, pos_rows));
+        }
+    return Q4_OK;
+}
+// What a prompt group does to state by position in front of its launches (run_transformer_steps_screenable below), for a prompt pass: the guide's ring
+// while the model has a guide, Mirostat's while the sampler has the adaptive launch on and the model has the rings, to NONE over [pos, pos + n)
+int stages_clear_positions(const Sampler* sampler, const Model* m, int pos, int n) {
+    if (guide_stage.on(sampler, m)) Q4_TRY(guide_clear_positions(m, pos, n));
+    if (m && m->adaptive_mu && adaptive_stage.on(sampler, m)) Q4_TRY(adaptive_clear_positions(m, pos, n));
+    return Q4_OK;
+}
 static bool step_screens(const Model* m, bool may_screen, int gen_token, bool greedy, int copyLogits, const Sampler* sampler) {
     return may_screen && g_greedy_screen && gen_token && greedy && !copyLogits && g_fusion >= 1 && m && m->logprobs_k < 0 && m->screen.base &&
            !any_stage_on(sampler, m) && cls_screen_shape(m->screen.n, m->screen.d);

@@ -22,6 +22,14 @@
 // in front of the sampler's row form and a row form of the look-up fills token_logprob behind it from the rows' tokens. Records p .. p + m are what m + 1
 // steps write. Records p + m + 1 .. p + D describe rejected drafts: they lie at or above the device position and are rewritten by whatever runs there
 // next -- the same contract as the K / V rows of rejected drafts.
+//
+// Under the logit stages (admitted only with q4_set_pass_stages on): between the record launch's place and the sampler's row form / the accept launch every
+// stage that is on rewrites the rows in place through its row form (LogitStage::launch_rows), block r at position p + r, exactly as the step at that position
+// would. A stage reads tokens by position, and rows behind the first stand on drafts, which never enter the ring: one launch in front of the stage rows fills
+// the model's draft view (PassScratch::view, seq_len ints by absolute position) -- view[lo .. p] from the ring, view[p + 1 .. p + D] from the kernel
+// argument, lo = max(0, p + 1 - Q4_MAX_DRY_WINDOW): the lowest entry any stage's step form reads at a position p .. p + D (DRY's window of at most 4096
+// entries, whose walk-back stays inside it; the penalties' of at most 1024; the guide's tokens[p + r]). The guide's state ring receives p .. p + D; the
+// states of rejected drafts lie at or above the device position and are rewritten by whatever runs there next -- the K / V rows' contract.
 #pragma once
 #include "prompt_pass.h"
 
@@ -57,12 +65,14 @@ void sample_rows_release(const Sampler* sampler);
 // The whole pass at the device position, which the caller knows to be pos0 (q4_passes.hip's verify_covers has admitted it there). On the launch stream;
 // nothing is waited for. sampler null: greedy. Else the pass under that sampler: behind the classifier the rows are sampled (coins: the device coin ring by
 // position, entries pos0 .. pos0 + n_draft drawn by the caller) and the accept launch takes those tokens.
+// stages: the Sampler whose logit stages (and the model's guide) rewrite the rows in front of that -- also a greedy one's; null: the model's guide alone (the greedy primitive). The caller's
+// admission has found every stage that is on to have a row form.
 int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler = nullptr,
-                    const float* coins = nullptr);
+                    const float* coins = nullptr, const Sampler* stages = nullptr);
 // q4_passes.hip. The admission of a pass at `pos` (sampler null: the primitive's greedy form); the drafter's answer for ring[0 .. n_tokens); q4_spec_stats' counters
 bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off);
 int ask_drafter(const Model* m, const int* ring, int n_tokens, int max_draft, int vocab, int* draft);
-void count_verify_pass(Model* m, int n_draft, int accepted);
+void count_verify_pass(Model* m, int n_draft, int accepted, bool forced = false);
 // q4_step.hip (the coin ring lives there). The coins of positions pos .. pos + n_draft into the sampler's device ring, the sampler's stream put back
 int stage_pass_coins(Sampler* sampler, const Config* p, int pos, int n_draft, const float** coins_dev);
 

@@ -205,8 +205,18 @@ __global__ void verify_embed_kernel(q4_half* xs, const q4_half* table, int dim, 
     reinterpret_cast<u32x4*>(xs + (size_t)t * dim)[u] = reinterpret_cast<const u32x4*>(table + (size_t)token * dim)[u];
 }
 
+// The draft view (spec_verify.h): view[lo .. p] from the ring, view[p + 1 .. p + d.n] from the argument, p = *pPos, lo = max(0, p + 1 - window). A grid of
+// divUp(window + PROMPT_PASS_MAX, 256) blocks covers it; nothing outside [0, len) is touched.
+__global__ void verify_view_kernel(int* view, int len, const int* tokens, const VerifyDrafts d, const int* pPos, int window) {
+    const int p = *pPos;
+    const int lo = p + 1 - window > 0 ? p + 1 - window : 0;
+    const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p < 0 || i > p + d.n || i >= len) return;
+    view[i] = i <= p ? tokens[i] : d.tok[i - p - 1];
+}
+
 int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, const int* draft, int n_draft, Sampler* sampler,
-                    const float* coins) {
+                    const float* coins, const Sampler* stages) {
     if (sampler && (!coins || sampler->vocab_size != p->vocab_size)) return Q4_ERR_ARG;
     if (sampler) Q4_TRY(sample_rows_prepare(sampler));       // (scratch on first use and the LDS opt-in: in front of the pass's first launch)
     if (!prompt_pass_covers(p, m) || !verify_cls_covers(p->dim, p->vocab_size)) return Q4_ERR_ARG;
@@ -219,6 +229,9 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, M
     if (records && !m->pass_logprobs) return Q4_ERR_ARG;
     Q4_TRY(pass_logit_rows(m, p));                           // (behind the rows: the PROMPT_PASS_MAX tokens the row form of the sampler leaves for the accept launch)
     if (records && sampler) Q4_TRY(pass_side_rows(m, p));
+    const bool staged = m->pass_stages && any_stage_on(stages, m);      // (admitted: q4_set_pass_stages, every stage that is on has a row form, no records)
+    if (staged && (records || !stages_take_rows(stages, m) || pos0 + n_draft >= p->seq_len)) return Q4_ERR_ARG;
+    if (staged) Q4_TRY(pass_draft_view(m, p));
     Q4_LAUNCH(verify_embed_kernel, dim3(divUp(dim >> 3, 256), n), dim3(256), 0, rows.x, w->token_embedding_table, dim, (const int*)s->shared_data->tokens, d,
               (const int*)s->pos, rows.pos);
     Q4_LAUNCH_CHECK();
@@ -227,6 +240,13 @@ int run_verify_pass(const Config* p, RunState* s, const TransformerWeights* w, M
     // Records p .. p + D, in front of the accept launch (it advances the position): a greedy row's token_logprob is entry 0; under the sampler the raw rows go
     // aside in front of the sampler's row form, which normalises them in place, and the rows' tokens are looked up behind it -- the order of the sampled step
     if (records) Q4_TRY(launch_logprobs_rows(m, p, s, rows.logit_rows, p->vocab_size, n, sampler ? LP_SAMPLED : LP_GREEDY));
+    // The logit stages that are on, in table order, each row at its own position; in front of them the draft view their row forms read in place of the ring
+    if (staged) {
+        Q4_LAUNCH(verify_view_kernel, dim3(divUp(Q4_MAX_DRY_WINDOW + PROMPT_PASS_MAX, 256)), dim3(256), 0, rows.view, p->seq_len, (const int*)s->shared_data->tokens, d,
+                  (const int*)s->pos, (int)Q4_MAX_DRY_WINDOW);
+        Q4_LAUNCH_CHECK();
+        Q4_TRY(launch_stage_rows(stages, m, p, rows.logit_rows, p->vocab_size, n, rows.view, rows.pos));
+    }
     int* win = nullptr;
     if (sampler) {      // each row sampled in place with its own position's coin, as the step at that position would; then the accept on those tokens
         win = reinterpret_cast<int*>(rows.logit_rows + (size_t)PROMPT_PASS_MAX * p->vocab_size);

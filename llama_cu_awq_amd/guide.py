@@ -5,6 +5,7 @@ A table is a uint16 array [S, V]: table[s, i] is the state behind token i in sta
     from_choices(sequences, vocab_size)   "answer with one of these token sequences"
     from_regex(pattern, pieces)           a regular expression over the BYTES of the generated text, lifted to the tokenizer's pieces
     walk(table, tokens)                   the states a token sequence passes through (what the device keeps by position)
+    forced_run(table, state, max_draft)   the tokens the automaton forces from a state: what the token loop drafts with q4_set_pass_stages on
 
 Both compilers end a match with EOS: a state where the text may end allows `eos_id`, which leads to a last state END that allows only EOS.
 """
@@ -30,6 +31,24 @@ def walk(table, tokens, start=0):
             s = e if e != DEAD else OFFTRACK
         out[j + 1] = s
     return out
+
+
+def forced_run(table, state, max_draft, eos_id=2):
+    """The restatement of q4_guide_forced_run: while the state has exactly ONE live token, that token, and on to the state behind it. At most max_draft
+    tokens; the run ends behind an EOS, at a state with zero, two or more live tokens, and is empty for NONE, OFFTRACK or a state outside the table."""
+    table = np.asarray(table)
+    out = []
+    s = int(state)
+    while len(out) < max_draft and 0 <= s < table.shape[0]:
+        live = np.flatnonzero(table[s] != DEAD)
+        if live.shape[0] != 1:
+            break
+        t = int(live[0])
+        out.append(t)
+        if t == eos_id:
+            break
+        s = int(table[s, t])
+    return np.asarray(out, dtype=np.int32)
 
 
 def from_choices(sequences, vocab_size, eos_id=2):
