@@ -131,8 +131,18 @@ __device__ __forceinline__ void kv8_append(const Kv8Args& a, const int kvh, cons
 }
 
 // ---- the short bins: ONE block per head, attention_kernel's three passes (scores -> LDS, softmax statistics, P . V) ------------------------------
-template <int LPR, int U = 4, int NW = ATT_NW>
-__global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a) {
+// One kernel, two instantiations -- one statement of the arithmetic:
+//  * ROW false, the step's launch: block h is head h at position *a.pPos; this position's row is quantised from the staging rows, used from registers
+//    (`cur`) and appended behind the head's output.
+//  * ROW true, the row form of a prompt or verify pass (prompt_pass_kv8.hip): block b is (token b / n_heads, head b % n_heads) of rows `dim` halves
+//    apart in a.q / a.output with positions a.pPos[token]; the launch in front has appended the tokens' rows, so every row up to and including the
+//    position comes from the cache -- the bytes and exponents the step holds in registers -- and nothing is stored but the output. a.k_row / a.v_row
+//    are not read.
+// Either way the resource ends where the block's own rows end: what lies above reads as zeros. (The flag is a kernel template argument and not a
+// __device__ body called by two kernels: moving the body behind a function boundary changed the step kernel's register allocation and address
+// arithmetic; this way the step's instruction stream is what it was before the flag existed.)
+template <int LPR, int U = 4, int NW = ATT_NW, bool ROW = false>
+__global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a0) {
     static_assert(LPR == 4 || LPR == 8 || LPR == 16, "head sizes 64, 128, 256");
     constexpr int R = 64 / LPR;                              // positions per wave instruction
     constexpr int stride = NW * R, group = stride * U;
@@ -140,23 +150,38 @@ __global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a)
     float* red_max = reinterpret_cast<float*>(smem);         // [16]
     float* red_sum = red_max + 16;                           // [16]
     float* outp = red_sum + 16;                              // [NW][head_size] output partials
-    float* sc = outp + NW * a.head_size;                     // [lds_scores] scores, then exps
-    const int h = blockIdx.x, head_size = a.head_size, kv_dim = a.kv_dim, kvh = h / a.kv_mul;
+    float* sc = outp + NW * a0.head_size;                    // [lds_scores] scores, then exps
+    Kv8Args a = a0;
+    int h = blockIdx.x;
+    if constexpr (ROW) {
+        const int n_heads = a0.kv_dim / a0.head_size * a0.kv_mul, tok = blockIdx.x / n_heads;
+        h = blockIdx.x - tok * n_heads;
+        a.pPos = a0.pPos + tok;
+        a.q = a0.q + (size_t)tok * n_heads * a0.head_size;
+        a.output = a0.output + (size_t)tok * n_heads * a0.head_size;
+    }
+    const int head_size = a.head_size, kv_dim = a.kv_dim, kvh = h / a.kv_mul;
     const unsigned tid = threadIdx.x, lane = tid & 63u;
     const int wave = tid >> 6, row = lane / LPR, sub = lane % LPR;
     const size_t hoff = (size_t)kvh * head_size + sub * 16;  // this lane's 16-byte slice inside a cache row
     if (NW < 16 && tid >= NW && tid < 16) { red_max[tid] = -INFINITY; red_sum[tid] = 0.f; }
     const int pos = __builtin_amdgcn_readfirstlane(*a.pPos);
     const int size = pos + 1;
+    const int cached = ROW ? size : pos;                     // rows the cache holds for this block
     const u32x4 q0 = *reinterpret_cast<const u32x4*>(a.q + (size_t)h * head_size + sub * 16);
     const u32x4 q1 = *reinterpret_cast<const u32x4*>(a.q + (size_t)h * head_size + sub * 16 + 8);
     u32x4 kq, vq;
     int ke, ve;
-    kv8_quantise<LPR>(a.k_row + hoff, kq, ke);
-    kv8_quantise<LPR>(a.v_row + hoff, vq, ve);
-    // bounded at `pos` rows: a row at or past the position comes back as zeros without a memory request
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)a.k8, 0, (unsigned)pos * (unsigned)kv_dim, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)a.v8, 0, (unsigned)pos * (unsigned)kv_dim, 0x00020000);
+    if constexpr (ROW) {
+        kq = vq = (u32x4){0u, 0u, 0u, 0u};
+        ke = ve = 0;
+    } else {
+        kv8_quantise<LPR>(a.k_row + hoff, kq, ke);
+        kv8_quantise<LPR>(a.v_row + hoff, vq, ve);
+    }
+    // bounded at `cached` rows: a row at or past the bound comes back as zeros without a memory request
+    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)a.k8, 0, (unsigned)cached * (unsigned)kv_dim, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)a.v8, 0, (unsigned)cached * (unsigned)kv_dim, 0x00020000);
     const int8_t* kex = a.k_exp + (size_t)kvh * a.exp_stride;
     const int8_t* vex = a.v_exp + (size_t)kvh * a.exp_stride;
 
@@ -169,12 +194,12 @@ __global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a)
         for (int u = 0; u < U; u++) {
             const int t = g0 + wave * R + row + u * stride;
             kb[u] = __builtin_amdgcn_raw_buffer_load_b128(rk, (unsigned)t * (unsigned)kv_dim + (unsigned)hoff, 0, 0);
-            ex[u] = t < pos ? (int)kex[t] : 0;
+            ex[u] = t < cached ? (int)kex[t] : 0;
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int t = g0 + wave * R + row + u * stride;
-            const bool cur = t == pos;
+            const bool cur = !ROW && t == pos;
             float s = row_sum<LPR>(kv8_dot16(cur ? kq : kb[u], q0, q1));
             s = round_h(s * kv8_pow2(cur ? ke : ex[u]) * a.alpha);     // the exponent: an exact scaling; then attention.h's rounding point
             if (t < size) {
@@ -213,12 +238,12 @@ __global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a)
         for (int u = 0; u < U; u++) {
             const int t = g0 + wave * R + row + u * stride;
             vb[u] = __builtin_amdgcn_raw_buffer_load_b128(rv, (unsigned)t * (unsigned)kv_dim + (unsigned)hoff, 0, 0);
-            ex[u] = t < pos ? (int)vex[t] : 0;
+            ex[u] = t < cached ? (int)vex[t] : 0;
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int t = g0 + wave * R + row + u * stride;
-            const bool cur = t == pos;
+            const bool cur = !ROW && t == pos;
             const float p = t < size ? round_h(sc[t] * inv_sum) * kv8_pow2(cur ? ve : ex[u]) : 0.f;
             kv8_axpy16(acc, cur ? vq : vb[u], p);
         }
@@ -234,7 +259,9 @@ __global__ void __launch_bounds__(NW * 64) attention_kv8_kernel(const Kv8Args a)
         for (int w = 0; w < NW; w++) s += part[w];
         a.output[(size_t)h * head_size + n] = f2h(s);
     }
-    if (h % a.kv_mul == 0) kv8_append<LPR>(a, kvh, pos, tid, hoff, kq, ke, vq, ve);
+    if constexpr (!ROW) {
+        if (h % a.kv_mul == 0) kv8_append<LPR>(a, kvh, pos, tid, hoff, kq, ke, vq, ve);
+    }
 }
 
 // ---- long contexts: one block per (head, chunk of NW * (64 / LPR) * U positions), attention_split_kernel's flash-decode records in the same layout, so

@@ -8,6 +8,18 @@ namespace q4 {
 
 bool kv8_head_size_ok(int head_size) { return head_size == 64 || head_size == 128 || head_size == 256; }
 
+// Which form the launch below takes for a bin argument (its one place; the plan of a prompt or verify pass asks too, q4_passes.hip): split-context from
+// g_att_split_min up where the scratch holds the records -- 256 positions per block, or 128 for a 128-wide head up to bin 1024 (the fp16 launch's
+// choice) --, else the one-pass form.
+Kv8Form attention_kv8_form(int num_heads, int head_size, int max_seq_len, bool have_scratch, size_t scratch_bytes) {
+    Kv8Form f;
+    f.chunk = head_size == 128 && max_seq_len <= 1024 ? 128 : 256;
+    f.nsp = divUp(max_seq_len, f.chunk);
+    f.split = max_seq_len >= g_att_split_min && have_scratch &&
+              (size_t)num_heads * f.nsp * (head_size + ATT_REC_PAD) * sizeof(float) <= scratch_bytes;
+    return f;
+}
+
 // exp_stride: positions per kv head in the exponent arrays (the model's seq_len; the public entry's max_seq_len). scratch / arrive: as launch_attention
 int launch_attention_kv8(q4_half* output, const q4_half* q, uint8_t* k8, uint8_t* v8, int8_t* k_exp, int8_t* v_exp, const q4_half* k_row,
                          const q4_half* v_row, int num_heads, int head_size, int kv_mul, int max_seq_len, int exp_stride, const int* pPos,
@@ -21,12 +33,9 @@ int launch_attention_kv8(q4_half* output, const q4_half* q, uint8_t* k8, uint8_t
     const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
     Kv8Args a = {output, q, k8, v8, k_exp, v_exp, k_row, v_row, head_size, kv_mul, kv_dim, exp_stride, pPos, alpha, max_seq_len, scratch, arrive};
     const dim3 block(ATT_NW * 64);
-    // positions per block of the split-context form: 256, or 128 for a 128-wide head up to bin 1024 (the fp16 launch's choice)
-    const int chunk = head_size == 128 && max_seq_len <= 1024 ? 128 : 256;
-    const int nsp = divUp(max_seq_len, chunk);
-    const bool split = max_seq_len >= g_att_split_min && scratch != nullptr &&
-                       (size_t)num_heads * nsp * (head_size + ATT_REC_PAD) * sizeof(float) <= scratch_bytes;
-    if (split) {
+    const Kv8Form form = attention_kv8_form(num_heads, head_size, max_seq_len, scratch != nullptr, scratch_bytes);
+    const int chunk = form.chunk, nsp = form.nsp;
+    if (form.split) {
         const size_t smem = (size_t)(32 + ATT_NW * head_size) * 4;
         const dim3 grid(num_heads, nsp);
         if (head_size == 64) Q4_LAUNCH((attention_kv8_split_kernel<4, 1>), grid, block, smem, a);          // 16 waves x 16 rows

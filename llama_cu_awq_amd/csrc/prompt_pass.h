@@ -13,12 +13,15 @@ constexpr int PASS_CONTEXT_MIN = 256;   // q4_set_pass_context: the default boun
 // With the model's q4_set_pass_gqa switch on also the grouped-query shape of Mistral-7B / Llama-3-8B: dim 4096, 128-wide heads, n_heads = 4 * n_kv_heads,
 // a hidden size whose down projection the step runs as the two-part K split with three whole k-slots and a shared half slot per part (14336) -- while
 // the profiling knobs g_ksplit / g_half_tail leave the step that form. A multi-head model is judged as with the switch off.
+// With the model's q4_set_pass_kv8 switch on also either shape with the FP8 cache (prompt_pass_kv8.h): 128-wide heads, both exponent arrays in place.
 bool prompt_pass_covers(const Config* p, const Model* m);
 // Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_passes.hip, the admission's one place): for every position the
 // form of the step's attention -> o-proj launch (attention_oproj_form of the bin argument the step would hand to run_network there) is either a V-slice
 // form (5 / 6: form = 5, prompt_attention_kernel) or ONE split-context form for all of them (form = 4 / 2 / 3, chunk = 64 / 128 / 256 positions:
 // prompt_split_attention_kernel + prompt_merge_kernel). nsp: chunks per head the pass launches and lays its records out by; nsp_of_bin: the chunk count
 // the step's launch merges in that bin, or 0 where the step is handed its own size (no graphs): ceil((position + 1) / chunk). False: no pass.
+// A model with the FP8 cache: the form launch_attention_kv8 takes at every position (attention_kv8_form) -- the one-pass form with a bin argument of at most
+// 256 (form = 5: attention_kv8_kernel<.., ROW>) or ONE split-context form (form = 2 / 3, chunk = 128 / 256: pass_kv8_split_kernel + prompt_merge_kernel).
 struct PassAttention { int form, chunk, nsp, nsp_of_bin; };
 bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, PassAttention* out);
 // Positions pos0 = *s->pos .. + n - 1 (2 <= n <= PROMPT_PASS_MAX, all inside one bin and below the bound of q4_set_pass_context, all prompt-only) on the

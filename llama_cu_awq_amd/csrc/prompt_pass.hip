@@ -7,6 +7,8 @@
 // that last launch (run_prompt_pass).
 // Grouped-query models of Mistral-7B's / Llama-3-8B's shape (q4_set_pass_gqa; DESIGN.md 3.7 "Grouped-query shapes"): the q/k/v launch with per-matrix
 // widths (GQA), both attention launches with kv_mul query heads per K / V head, the down projection in the step's shared-half-slot form (HALF).
+// Models with the FP8 K / V cache (q4_set_pass_kv8; DESIGN.md 3.7 "FP8 cache"): the q/k/v launch leaves K / V in fp16 staging rows (STAGE), one launch
+// appends them to the byte caches and attention reads every row from there (prompt_pass_kv8.hip) -- six launches per layer, seven in the split bins.
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
 // parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
@@ -18,6 +20,7 @@
 #include <math.h>
 #include "layer_attn.h"
 #include "prompt_pass.h"
+#include "prompt_pass_kv8.h"
 #include "spec_verify.h"
 
 namespace q4 {
@@ -44,10 +47,13 @@ constexpr size_t prompt_gemv_lds() {      // G tokens' permuted x and x-only sum
 // N_kv / 4 of k and of v, every matrix with its own width in the descriptors, the clamp and the row addressing.
 // HALF (plain, K split): gemv_q4_body's shared half slot -- a k-part's last slot holds at most 32 units, lanes 0 - 31 take it for the even column of the
 // wave's pair and lanes 32 - 63 for the odd one, its term is added as a product and a sum and the other half of the wave adds 0.f.
-template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false>
+// STAGE (q/k/v of a model with the FP8 cache, GemvArgs::kv_stage): out[1] / out[2] are the pass's fp16 staging rows [ntok][N] -- token t's K / V row goes
+// to row t, not into a cache at loff + pos * N (prompt_pass_kv8.h appends them). A template flag: the fp16 instantiations are the code they were.
+template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false, bool STAGE = false>
 __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, const int ntok) {
     constexpr int NMAT = ModeTraits<MODE>::NMAT;
     static_assert(!GQA || MODE == MODE_QKV, "per-matrix widths: q/k/v");
+    static_assert(!STAGE || MODE == MODE_QKV, "staging rows: q/k/v");
     static_assert(!HALF || (MODE == MODE_PLAIN && KS == 2 && COLS == 2), "shared half slot: one column pair per wave, K split");
     static_assert(G >= 1 && G <= 8, "exchange slots");
     static_assert(KS == 1 || (KS == 2 && MODE == MODE_PLAIN && !NORM), "K split: plain GEMV");
@@ -316,6 +322,9 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
             } else {                                         // MODE_QKV: rows = pair0 first, pair1 first, pair0 second, pair1 second
                 const int pos = p0 + t;
                 q4_half* out = mat0 == 0 ? a.out[0] + (size_t)t * N : a.out[mat0] + (size_t)a.loff + (size_t)pos * N;
+                if constexpr (STAGE) {
+                    if (mat0 != 0) out = a.out[mat0] + (size_t)t * N;
+                }
                 const float mine = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
                 float r = mine;
                 if (mat0 < 2) {
@@ -512,7 +521,7 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 
 // ---- host ------------------------------------------------------------------------------------------
 void pass_release(Model* m) {
-    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side, (void*)m->pass.view})
+    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side, (void*)m->pass.view, (void*)m->pass.kv_stage})
         if (d) (void)hipFree(d);
     m->pass = PassScratch{};
 }
@@ -564,6 +573,15 @@ int pass_draft_view(Model* m, const Config* p) {
     return Q4_OK;
 }
 
+// The staging rows of a pass over the FP8 cache (prompt_pass_kv8.h): [2][PROMPT_PASS_MAX][kv_dim] halves, the tokens' K rows and behind them their V
+// rows between the q/k/v launch and the append launch, allocated on first use
+static int pass_kv_stage_rows(Model* m, int kv_dim) {
+    if (!m->pass.kv_stage && hipMalloc((void**)&m->pass.kv_stage, (size_t)2 * PROMPT_PASS_MAX * kv_dim * sizeof(q4_half)) != hipSuccess) {
+        (void)hipGetLastError(); m->pass.kv_stage = nullptr; return Q4_ERR_ALLOC;
+    }
+    return Q4_OK;
+}
+
 // The split passes' flash-decode records: the pass's own buffer (never RunState::att, whose words are validated by tag), allocated on the first split
 // pass of the model for the longest context it can meet -- PROMPT_PASS_MAX tokens x heads x chunks x (head_size + ATT_REC_PAD) floats.
 static int pass_records_of(PassScratch* b, size_t floats) {
@@ -598,7 +616,10 @@ static bool pass_down_half_covers(int dim, int hidden) {
     return g.nslots >= 5 && g.nslots <= 8 && divUp(ku, 64) == 4 && ku - 192 <= 32 && ku * 2 >= g.pw4;
 }
 bool prompt_pass_covers(const Config* p, const Model* m) {
-    if (!p || !m || !m->rope_table || !m->sync || m->kv_format != Q4_KV_FP16) return false;
+    if (!p || !m || !m->rope_table || !m->sync) return false;
+    if (m->kv_format != Q4_KV_FP16) {       // the FP8 cache: q4_set_pass_kv8, and a head the append and attention launches of prompt_pass_kv8.hip take (128, checked below)
+        if (m->kv_format != Q4_KV_FP8 || !m->pass_kv8 || !m->k_exp || !m->v_exp || !kv8_head_size_ok(p->n_heads > 0 ? p->dim / p->n_heads : 0)) return false;
+    }
     const int dim = p->dim, hidden = p->hidden_dim;
     if (dim != 4096 || p->n_heads * 128 != dim || (hidden & 31)) return false;
     if (p->n_heads != p->n_kv_heads) {      // grouped-query: q4_set_pass_gqa, four query heads per K / V head and the half-slot down form (Mistral-7B, Llama-3-8B: what the tests run)
@@ -626,6 +647,16 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     PassAttention plan = {};
     if (!pass_attention_plan(p, s, pos0, n, &plan)) return Q4_ERR_ARG;
     const bool split = att_is_split(plan.form);
+    // The FP8 cache (q4_set_pass_kv8; prompt_pass_kv8.h): q/k/v into the staging rows, the append launch, attention over the byte caches
+    const bool kv8 = m->kv_format == Q4_KV_FP8;
+    q4_half* k_stage = nullptr;
+    q4_half* v_stage = nullptr;
+    if (kv8) {
+        if (head_size != 128 || pos0 < 0 || pos0 + n > p->seq_len || (!split && pos0 + n > PASS_CONTEXT_MIN)) return Q4_ERR_ARG;   // (the one-pass row form keeps 256 scores)
+        Q4_TRY(pass_kv_stage_rows(m, kv_dim));
+        k_stage = m->pass.kv_stage;
+        v_stage = k_stage + (size_t)PROMPT_PASS_MAX * kv_dim;
+    }
     const int rec = head_size + ATT_REC_PAD;
     const size_t tok_stride = (size_t)p->n_heads * plan.nsp * rec;
     if (split) {
@@ -649,24 +680,39 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             fill_geom(a, dim, dim);
             a.N_kv = kv_dim;
             fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
-            a.out[0] = b->q; a.out[1] = s->key_cache; a.out[2] = s->value_cache;
-            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff;
+            a.out[0] = b->q; a.out[1] = kv8 ? k_stage : s->key_cache; a.out[2] = kv8 ? v_stage : s->value_cache;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff; a.kv_stage = kv8 ? 1 : 0;
             a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
             const int groups = (dim + 2 * kv_dim) / 4;
             if (groups % PP_QKV_GQA_WAVES) return Q4_ERR_ARG;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_GQA_WAVES, true>), dim3(groups / PP_QKV_GQA_WAVES), dim3(PP_QKV_GQA_WAVES * 64), SMEM_NORM, a, n);
+            if (kv8) Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_GQA_WAVES, true, false, true>), dim3(groups / PP_QKV_GQA_WAVES), dim3(PP_QKV_GQA_WAVES * 64), SMEM_NORM, a, n);
+            else Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_GQA_WAVES, true>), dim3(groups / PP_QKV_GQA_WAVES), dim3(PP_QKV_GQA_WAVES * 64), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         } else {   // rmsnorm + q/k/v + RoPE + K/V rows
             GemvArgs a = {};
             fill_geom(a, dim, dim);
             fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
-            a.out[0] = b->q; a.out[1] = s->key_cache; a.out[2] = s->value_cache;
-            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff;
+            a.out[0] = b->q; a.out[1] = kv8 ? k_stage : s->key_cache; a.out[2] = kv8 ? v_stage : s->value_cache;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff; a.kv_stage = kv8 ? 1 : 0;
             a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
+            if (kv8) Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES, false, false, true>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
+            else Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         }
-        if (split) {   // attention in the split-context bins: one block per (head, chunk) loops over the tokens, then the step's merge per (head, token)
+        if (kv8) {   // the FP8 cache: the tokens' rows appended (bytes and exponents, also those of a verify pass's drafts), then attention over rows [0, pos[t]] of the byte caches
+            const size_t eoff = (size_t)l * p->n_kv_heads * p->seq_len;
+            const PassKv8 c = {(uint8_t*)s->key_cache + loff, (uint8_t*)s->value_cache + loff, m->k_exp + eoff, m->v_exp + eoff, p->n_heads, head_size, kv_mul, kv_dim,
+                               p->seq_len, b->pos, n};
+            Q4_TRY(launch_pass_kv8_append(c, k_stage, v_stage));
+            if (split) {
+                Q4_TRY(launch_pass_kv8_split(c, b->records, tok_stride, b->q, dim, alpha, plan.chunk, plan.nsp));
+                Q4_LAUNCH(prompt_merge_kernel, dim3((unsigned)p->n_heads, (unsigned)n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
+                          plan.nsp, tok_stride, plan.nsp_of_bin, plan.chunk);
+                Q4_LAUNCH_CHECK();
+            } else {
+                Q4_TRY(launch_pass_kv8_attention(c, b->xb, b->q, dim, alpha));
+            }
+        } else if (split) {   // attention in the split-context bins: one block per (head, chunk) loops over the tokens, then the step's merge per (head, token)
             const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, kv_dim, kv_mul, plan.nsp, tok_stride, alpha};
             const dim3 grid((unsigned)p->n_heads, (unsigned)plan.nsp);
             if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a);

@@ -596,6 +596,15 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and passes for a model with the FP8 K / V cache (q4_set_pass_kv8): Q4_PASS_KV8=1
+    const char* pass_kv8 = getenv("Q4_PASS_KV8");
+    if (pass_kv8 && *pass_kv8) {
+        int on = 0;
+        if (q4_parse_pass_kv8(pass_kv8, &on) || q4_set_pass_kv8(&transformer, on)) {
+            fprintf(stderr, "Q4_PASS_KV8: cannot use '%s' (0 or 1: prompt and verify passes also with Q4_KV_CACHE=fp8)\n", pass_kv8);
+            exit(EXIT_FAILURE);
+        }
+    }
     // ... and passes while logit stages are on, with the guide's forced drafts (q4_set_pass_stages): Q4_PASS_STAGES=1
     const char* pass_stages = getenv("Q4_PASS_STAGES");
     if (pass_stages && *pass_stages) {

@@ -84,6 +84,9 @@ int launch_attention(q4_half* output, const q4_half* q, const q4_half* key_cache
                      size_t scratch_bytes, unsigned* arrive);   // arrive: n_heads zeroed counters (split-context merge by the last block) or null
 // attention over the FP8 (e4m3) K / V cache, appending the staging rows (attention_kv8.h); exp_stride: positions per kv head in the exponent arrays
 bool kv8_head_size_ok(int head_size);
+// the form launch_attention_kv8 takes for a bin argument: split-context (chunk positions per block, nsp chunks per head) or the one-pass form
+struct Kv8Form { bool split; int chunk, nsp; };
+Kv8Form attention_kv8_form(int num_heads, int head_size, int max_seq_len, bool have_scratch, size_t scratch_bytes);
 int launch_attention_kv8(q4_half* output, const q4_half* q, uint8_t* k8, uint8_t* v8, int8_t* k_exp, int8_t* v_exp, const q4_half* k_row,
                          const q4_half* v_row, int num_heads, int head_size, int kv_mul, int max_seq_len, int exp_stride, const int* pPos,
                          float* scratch, size_t scratch_bytes, unsigned* arrive);

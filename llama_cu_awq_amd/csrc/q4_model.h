@@ -12,8 +12,9 @@ namespace q4 {
 // The scratch of the prompt and verify passes (prompt_pass.h, spec_verify.h), each allocation made on first use and released by pass_release. slab: the rows x / q / xb
 // / hb, their positions and the attention launch's sink (u32x2v granules); records: the split passes' flash-decode records; logit_rows: the logits of a verify pass or of a
 // prompt pass with records (pass_logit_rows) and the tokens behind them; lp_side: [PROMPT_PASS_MAX][vocab] raw rows of a verify pass under the sampler with records (pass_side_rows);
+// kv_stage: [2][PROMPT_PASS_MAX][kv_dim] the fp16 K and V staging rows of a pass over the FP8 cache (prompt_pass_kv8.h; q4_set_pass_kv8);
 // view: [seq_len] the draft view of a verify pass with logit stages (pass_draft_view; q4_set_pass_stages): tokens by absolute position, the ring up to the pass's first position and its drafts behind
-struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; q4_half* lp_side; int* view; };
+struct PassScratch { void* slab; q4_half* x; q4_half* q; q4_half* xb; q4_half* hb; int* pos; unsigned* sink; size_t sink_stride; float* records; size_t record_floats; q4_half* logit_rows; q4_half* lp_side; int* view; q4_half* kv_stage; };
 // every Transformer owns two HBM slabs (weights, run state) instead of ~750 small allocations: layers sit
 // back to back in HBM in the order the token loop streams them. ONE record per model: q4_build_transformer registers it as soon as its
 // first allocation exists, q4_free_transformer is the only place that releases and forgets it.
@@ -44,6 +45,7 @@ struct Model {
     q4_half* lp_side = nullptr;     // [vocab] raw logits of a sampled step, kept for the look-up behind the sampler
     bool pass_logprobs = false;     // q4_set_pass_logprobs: prompt and verify passes (and q4_score_ids through prompt passes) also while the records are on
     bool pass_gqa = false;          // q4_set_pass_gqa: prompt and verify passes also for the grouped-query 4096-wide shape (prompt_pass_covers)
+    bool pass_kv8 = false;          // q4_set_pass_kv8: prompt and verify passes also for a model with the FP8 cache (prompt_pass_covers; prompt_pass_kv8.h)
     bool pass_stages = false;       // q4_set_pass_stages: verify passes also with a guide, DRY or the sampling controls on (their row forms), prompt passes also with a guide or the adaptive truncation on
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
     const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model

@@ -32,9 +32,19 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
     if (pos < 0 || n < 1 || pos + n > p->seq_len || p->n_heads < 1) return false;
     const int head_size = p->dim / p->n_heads, kv_dim = (p->dim * p->n_kv_heads) / p->n_heads;
     int kind = -1, arg = -1, form = -1;
+    const Model* m = model_of(s);
+    const bool kv8 = m && m->kv_format == Q4_KV_FP8;
     for (int i = 0; i < n; i++) {
         const int arg_i = step_bin_arg(p, pos + i);
-        if (arg_i != arg) form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, arg_i, s->att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
+        if (kv8) {
+            // The FP8 cache: the form launch_attention_kv8 takes at this position (its own predicate), in this plan's terms -- the one-pass form up to bin
+            // argument 256 (the row form keeps 256 scores) as 5, the split-context form by its chunk as 2 (128 positions) or 3 (256); a one-pass step above
+            // 256 (no graphs: arguments 257 .. 511; records that do not fit the scratch) has no row form
+            if (arg_i != arg) {
+                const Kv8Form f = attention_kv8_form(p->n_heads, head_size, arg_i, s->att != nullptr, att_buffer_bytes(p));
+                form = f.split ? (f.chunk == 128 ? 2 : 3) : arg_i <= PASS_CONTEXT_MIN ? 5 : -1;
+            }
+        } else if (arg_i != arg) form = attention_oproj_form(p->dim, kv_dim, head_size, p->n_heads, arg_i, s->att != nullptr, att_buffer_bytes(p), g_att_split_min, g_att_chunk);
         const int kind_i = form == 5 || form == 6 ? 5 : form >= 2 && form <= 4 ? form : -1;   // V-slice forms mix (prompt_attention_kernel picks per token); a split form stands alone
         if (kind_i < 0 || (i > 0 && kind_i != kind)) return false;
         if (kind_i != 5 && g_use_graphs && i > 0 && arg_i != arg) return false;               // split tokens of one pass share the step's launch shape
@@ -52,7 +62,7 @@ bool pass_attention_plan(const Config* p, const RunState* s, int pos, int n, Pas
 // loop asks (the per-step entry points, scoring and perplexity keep their steps), and only where the pass computes what the steps would and nothing reads
 // what it leaves out: the switch on; the fusion level in force >= 3 with an attention form the pass reproduces at every position it touches
 // (pass_attention_plan: the V-slice forms 5 / 6, or one split-context form 4 / 2 / 3) -- so never the level-1 redo after a time-out --; the geometry
-// prompt_pass_covers admits (fp16 cache, unmasked stream); every position prompt-only, inside `steps`, below the bound of q4_set_pass_context and inside
+// prompt_pass_covers admits (fp16 cache, or the FP8 cache with q4_set_pass_kv8 on; unmasked stream); every position prompt-only, inside `steps`, below the bound of q4_set_pass_context and inside
 // the bin of `pos`; no log-probability records (they describe prompt steps' logits) or q4_set_pass_logprobs on (pass_records_ok: the pass then runs the
 // classifier and writes the records); neither the guide nor the adaptive truncation on unless the model's q4_set_pass_stages switch is (their state by
 // position is put to NONE per prompt step); no context-shift offset. (copyLogits: a token loop never asks for it.) q4_score_ids asks too, with that
@@ -267,6 +277,22 @@ int q4_get_pass_gqa(const Transformer* t) {
     return m && m->pass_gqa ? 1 : 0;
 }
 int q4_parse_pass_gqa(const char* text, int* on) {     // the CLI's Q4_PASS_GQA: "0" or "1", nothing else
+    if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
+    *on = text[0] - '0';
+    return Q4_OK;
+}
+// Passes for a model with the FP8 cache (prompt_pass_covers; prompt_pass_kv8.h): per model, off by default. No captured graph contains a pass: nothing to drop.
+int q4_set_pass_kv8(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->pass_kv8 = on != 0;
+    return Q4_OK;
+}
+int q4_get_pass_kv8(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->pass_kv8 ? 1 : 0;
+}
+int q4_parse_pass_kv8(const char* text, int* on) {     // the CLI's Q4_PASS_KV8: "0" or "1", nothing else
     if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
     *on = text[0] - '0';
     return Q4_OK;

@@ -10,6 +10,9 @@
 // the next step or pass at those positions writes them again. Drafts travel by value in a kernel argument: an unconfirmed token never enters the ring or
 // pinned memory. Every dependency is a launch boundary: the pass waits on nothing in-launch and touches neither the model's hand-off words nor its
 // granules (the attention launch writes the prompt pass's own sink).
+// A model with the FP8 cache (q4_set_pass_kv8; prompt_pass_kv8.h): the layer loop's append launch writes the e4m3 bytes and both row exponents of rows
+// p .. p + D, those of rejected drafts included -- they too lie at or above the device position and are rewritten (bytes and exponents) by the step or the
+// pass that runs there next, as on the fp16 cache.
 //
 // Under the temperature / top-p sampler (q4_set_speculative_sampled): a sampled step is a function of its logits and one coin, and the coin is a function
 // of (seed, position) that reaches the device through the coin ring by position. So between the classifier and the accept launch every row is sampled in
