@@ -375,7 +375,7 @@ int q4_get_pass_logprobs(const Transformer* t);   /* 1: on; 0: off, or not a Tra
  * 14336: 448 units, 224 = 3 x 64 + 32 per part) -- and only while q4_set_ksplit / q4_set_half_tail of the profiling build leave that form in force;
  * and everything a pass requires of a multi-head model (a rotation table, an fp16 K / V cache, an unmasked stream, fusion level >= 3, the position, bin,
  * record, guide, adaptive and context-shift rules of q4_set_prompt_ingest and q4_verify_tokens). Other ratios, other head sizes, the FP8 cache (unless q4_set_pass_kv8
- * admits it) and 13B stay on steps. A multi-head model behaves with the switch on exactly as with it off. K / V rows, tokens, logits, records and rng_state are the
+ * admits it) and 13B (q4_set_pass_13b, below) stay on steps. A multi-head model behaves with the switch on exactly as with it off. K / V rows, tokens, logits, records and rng_state are the
  * per-token run's, byte for byte; q4_verify_covers, q4_verify_covers_sampled and q4_prompt_passes report the admissions. Q4_ERR_ARG / 0: a Transformer
  * the library did not build. */
 int q4_set_pass_gqa(Transformer* t, int on);
@@ -397,6 +397,21 @@ int q4_set_pass_kv8(Transformer* t, int on);
 int q4_get_pass_kv8(const Transformer* t);        /* 1: on; 0: off, or not a Transformer the library built */
 /* The CLI's Q4_PASS_KV8: "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
 int q4_parse_pass_kv8(const char* text, int* on);
+/* Prompt and verify passes for Llama-2-13B's shape (DESIGN.md 3.7 "13B"): per model, off by default -- a 5120-wide model then runs per-token steps
+ * everywhere, as before, and no decision, launch or counter changes. On, q4_set_prompt_ingest's passes, the verify passes of q4_set_speculative (greedy
+ * and q4_set_speculative_sampled), passes with records (q4_set_pass_logprobs), with logit stages (q4_set_pass_stages) and q4_score_ids through passes
+ * also admit a model with: dim 5120 as 128-wide heads, multi-head (n_heads = n_kv_heads = 40); hidden 13824, whose down projection the step runs as
+ * the two-part K split with three whole k-slots and a shared last slot per part (432 units, 216 = 3 x 64 + 24 per part); an fp16 K / V cache; the
+ * step's K = 5120 launches on their shipped forms (two whole k-slots and the shared half slot: the profiling build's q4_set_half_tail(0),
+ * q4_set_ksplit(0 | 4), ablations and any GEMV form but the product's keep the steps); and everything a pass requires of a 4096-wide model (a rotation
+ * table, an unmasked stream, fusion level >= 3, the position, bin, record, guide, adaptive and context-shift rules of q4_set_prompt_ingest and
+ * q4_verify_tokens). Grouped-query models of this width, the FP8 cache (also with q4_set_pass_kv8 on) and other hidden sizes stay on steps. A model of
+ * another width behaves with the switch on exactly as with it off. K / V rows, tokens, logits, records and rng_state are the per-token run's, byte for
+ * byte; q4_verify_covers, q4_verify_covers_sampled and q4_prompt_passes report the admissions. Q4_ERR_ARG / 0: a Transformer the library did not build. */
+int q4_set_pass_13b(Transformer* t, int on);
+int q4_get_pass_13b(const Transformer* t);        /* 1: on; 0: off, or not a Transformer the library built */
+/* The CLI's Q4_PASS_13B: "1" on, "0" off; anything else Q4_ERR_ARG and *on untouched. */
+int q4_parse_pass_13b(const char* text, int* on);
 /* Passes while a logit stage is on (csrc/spec_verify.h, DESIGN.md 3.8 "Under the logit stages"): per model, off by default -- off, a guide, DRY, the
  * sampling controls or the adaptive truncation switch every verify pass off and a guide or the adaptive truncation every prompt pass, as before, and
  * nothing else changes. On: a verify pass is admitted with a guide, DRY and the sampling controls on -- greedy and, with q4_set_speculative_sampled, under
@@ -432,7 +447,7 @@ int q4_screen_candidates(const Transformer* t, int* last, int* max, long long* t
  * its weights once and multiplies all the positions' activations. The K / V rows, the generated tokens and the final logits are the per-token steps', bit
  * for bit; a pass runs no classifier, so RunState::logits is not written by the positions it covers. Taken only where the result is the same and nothing
  * reads what a pass leaves out: Llama-2-7B's geometry (dim 4096, multi-head, 128-wide heads, a hidden size the three-phase FFN launch admits; with
- * q4_set_pass_gqa on also the grouped-query shape described there), fusion level
+ * q4_set_pass_gqa on also the grouped-query shape described there, with q4_set_pass_13b on also Llama-2-13B's), fusion level
  * >= 3, an fp16 K / V cache (the FP8 cache with q4_set_pass_kv8 on), positions below the bound of q4_set_pass_context (256 unless raised), log-probability records off or q4_set_pass_logprobs on, no guide, no adaptive truncation, no context-shift offset, an unmasked
  * stream; everything else -- and q4_run_transformer*, q4_score_ids (unless q4_set_pass_logprobs is on), q4_perplexity_ids, q4_chat -- runs per token as before. max_tokens: 0 (or 1) off,
  * clamped to 8, the default. q4_prompt_passes: passes run since the library was loaded. */

@@ -63,6 +63,9 @@ inline bool pass_gqa(const Transformer* t) { return q4_get_pass_gqa(t) != 0; }
 // not in the reference: prompt and verify passes for a model with the FP8 K / V cache (q4_set_pass_kv8)
 inline void set_pass_kv8(Transformer* t, bool on) { die_on(q4_set_pass_kv8(t, on ? 1 : 0)); }
 inline bool pass_kv8(const Transformer* t) { return q4_get_pass_kv8(t) != 0; }
+// not in the reference: prompt and verify passes for Llama-2-13B's shape, dim 5120 / hidden 13824 (q4_set_pass_13b)
+inline void set_pass_13b(Transformer* t, bool on) { die_on(q4_set_pass_13b(t, on ? 1 : 0)); }
+inline bool pass_13b(const Transformer* t) { return q4_get_pass_13b(t) != 0; }
 // not in the reference: passes while a guide, DRY, the sampling controls (verify) or the adaptive truncation (prompt) are on, forced drafts (q4_set_pass_stages)
 inline void set_pass_stages(Transformer* t, bool on) { die_on(q4_set_pass_stages(t, on ? 1 : 0)); }
 inline bool pass_stages(const Transformer* t) { return q4_get_pass_stages(t) != 0; }

@@ -209,7 +209,7 @@ SYMBOLS = [
     "q4_spec_stats", "q4_verify_classifier", "q4_verify_accept", "q4_set_speculative_sampled", "q4_get_speculative_sampled", "q4_verify_tokens_sampled",
     "q4_verify_covers_sampled", "q4_verify_sample_rows", "q4_verify_accept_tokens", "q4_parse_speculative_sampled",
     "q4_logprob_topk_rows", "q4_set_pass_logprobs", "q4_get_pass_logprobs", "q4_set_pass_gqa", "q4_get_pass_gqa", "q4_parse_pass_gqa",
-    "q4_set_pass_kv8", "q4_get_pass_kv8", "q4_parse_pass_kv8",
+    "q4_set_pass_kv8", "q4_get_pass_kv8", "q4_parse_pass_kv8", "q4_set_pass_13b", "q4_get_pass_13b", "q4_parse_pass_13b",
     "q4_set_pass_stages", "q4_get_pass_stages", "q4_parse_pass_stages", "q4_guide_mask_rows", "q4_dry_penalty_rows", "q4_process_logits_rows",
     "q4_guide_forced_run", "q4_spec_stats_forced",
 ]
@@ -350,6 +350,10 @@ def lib():
         L.q4_set_pass_gqa.argtypes = [vp, i]
         L.q4_get_pass_gqa.argtypes = [vp]
         L.q4_parse_pass_gqa.argtypes = [C.c_char_p, C.POINTER(i)]
+    if hasattr(L, "q4_set_pass_13b"):              # (older builds under tools/ab.py do not have it)
+        L.q4_set_pass_13b.argtypes = [vp, i]
+        L.q4_get_pass_13b.argtypes = [vp]
+        L.q4_parse_pass_13b.argtypes = [C.c_char_p, C.POINTER(i)]
     if hasattr(L, "q4_set_pass_kv8"):              # (older builds under tools/ab.py do not have it)
         L.q4_set_pass_kv8.argtypes = [vp, i]
         L.q4_get_pass_kv8.argtypes = [vp]
@@ -873,7 +877,7 @@ class Transformer:
 
     def __init__(self, path, perplexity=False, temperature=0.0, topp=0.9, seed=1, quiet=True, kv="fp16", logprobs=None, sampling=None,
                  logit_bias=None, guide=None, context_shift=None, rope_scaling=None, dry=None, dry_breakers=None, tokenizer=None, adaptive=None, speculative=None,
-                 pass_logprobs=False, pass_gqa=False, pass_stages=False, pass_kv8=False):
+                 pass_logprobs=False, pass_gqa=False, pass_stages=False, pass_kv8=False, pass_13b=False):
         L = lib()
         L.q4_set_quiet(1 if quiet else 0)
         st = C.c_int()
@@ -928,6 +932,8 @@ class Transformer:
                 self.set_pass_gqa(True)
             if pass_kv8:
                 self.set_pass_kv8(True)
+            if pass_13b:
+                self.set_pass_13b(True)
             if pass_stages:
                 self.set_pass_stages(True)
             if sampling is not None:
@@ -1289,6 +1295,15 @@ class Transformer:
     def pass_kv8(self):
         """q4_get_pass_kv8"""
         return bool(lib().q4_get_pass_kv8(self.h))
+
+    def set_pass_13b(self, on):
+        """q4_set_pass_13b: prompt and verify passes also for Llama-2-13B's shape (dim 5120, forty 128-wide heads, multi-head, hidden 13824, fp16
+        cache); off by default. Tokens, K / V rows, logits and records are the per-token run's, byte for byte."""
+        check(lib().q4_set_pass_13b(self.h, 1 if on else 0))
+
+    def pass_13b(self):
+        """q4_get_pass_13b"""
+        return bool(lib().q4_get_pass_13b(self.h))
 
     def set_pass_stages(self, on):
         """q4_set_pass_stages: verify passes also with a guide, DRY or the sampling controls on (their row forms), prompt passes also with a guide or the

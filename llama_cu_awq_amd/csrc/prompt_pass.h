@@ -14,7 +14,16 @@ constexpr int PASS_CONTEXT_MIN = 256;   // q4_set_pass_context: the default boun
 // a hidden size whose down projection the step runs as the two-part K split with three whole k-slots and a shared half slot per part (14336) -- while
 // the profiling knobs g_ksplit / g_half_tail leave the step that form. A multi-head model is judged as with the switch off.
 // With the model's q4_set_pass_kv8 switch on also either shape with the FP8 cache (prompt_pass_kv8.h): 128-wide heads, both exponent arrays in place.
+// With the model's q4_set_pass_13b switch on also Llama-2-13B's shape: dim 5120 as forty 128-wide heads, multi-head, hidden 13824, an fp16 cache -- K =
+// 5120 as two whole k-slots and the step's shared half slot in q/k/v, o-proj and gate/up, the down projection in the K split's shared-half-slot form --
+// while the step runs the product's GEMV forms with the half slot and the K split in force (g_gemv_form, g_half_tail, g_ksplit, g_ablate). Grouped-query
+// models of this width, the FP8 cache (also with q4_set_pass_kv8) and other hidden sizes keep their steps.
 bool prompt_pass_covers(const Config* p, const Model* m);
+// The fewest positions a pass of this shape takes (prompt passes; verify passes: drafts + 1): the smallest n at which ONE pass measured faster than n
+// steps at positions 30, 300 and 2000 alike (profiles/pass_13b_bench.json). 2 at width 4096; 4 at
+// Llama-2-13B's shape, where a pass of two costs 4.26 ms against 3.63 for two steps and a pass of three 5.36 against 5.27 at position 30. The kernels
+// take any 2 <= n <= PROMPT_PASS_MAX (prompt_pass_layers); the admission (q4_passes.hip) and the token loop's drafts (q4_loops.hip) keep to this.
+int prompt_pass_min(const Config* p);
 // Which attention launch the layers of a pass over positions pos .. pos + n - 1 take (q4_passes.hip, the admission's one place): for every position the
 // form of the step's attention -> o-proj launch (attention_oproj_form of the bin argument the step would hand to run_network there) is either a V-slice
 // form (5 / 6: form = 5, prompt_attention_kernel) or ONE split-context form for all of them (form = 4 / 2 / 3, chunk = 64 / 128 / 256 positions:

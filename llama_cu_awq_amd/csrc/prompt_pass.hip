@@ -9,6 +9,9 @@
 // widths (GQA), both attention launches with kv_mul query heads per K / V head, the down projection in the step's shared-half-slot form (HALF).
 // Models with the FP8 K / V cache (q4_set_pass_kv8; DESIGN.md 3.7 "FP8 cache"): the q/k/v launch leaves K / V in fp16 staging rows (STAGE), one launch
 // appends them to the byte caches and attention reads every row from there (prompt_pass_kv8.hip) -- six launches per layer, seven in the split bins.
+// Llama-2-13B's shape (q4_set_pass_13b; DESIGN.md 3.7 "13B"): K = dim = 5120 is two whole k-slots and the step's shared half slot (HALF without a K
+// split) in the q/k/v, o-proj and gate/up launches -- a column pair per wave in the latter two --, the norm over 640 chunk partials and 128 zeros, the
+// down projection in the K split's shared-half-slot form as for the grouped-query shape.
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
 // parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
@@ -35,6 +38,16 @@ constexpr int PP_WAVES = 16;           // waves per block: four per SIMD hide ea
 constexpr int PP_QKV_GQA_WAVES = Q4_PP_QKV_GQA_WAVES;    // grouped-query q/k/v (kv_dim = dim / 4): 1024 + 2 x 256 column groups = 256 blocks of six waves, one per CU (twelve-wave blocks: 128, half of the CUs idle -- a 250-token ingest 169.9 ms against 165.3)
 constexpr int PP_DOWN_HALF_G = Q4_PP_DOWN_HALF_G;      // tokens staged per group by the shared-half-slot down launch: nine LDS rows of 64 units (39 KB) per token, two exceed 64 KB (behind an opt-in they measured 0.45 % faster over an ingest: not taken)
 constexpr int PP_QKV_WAVES = 12;       // q/k/v: 3 x 1024 column groups = 256 blocks of twelve waves, one per CU (sixteen-wave blocks: 192, a quarter of the CUs idle)
+// dim 5120 (q4_set_pass_13b): every K = 5120 launch stages three 64-unit rows per token, so a normalising launch holds three tokens per group (four are
+// 16 bytes over the 64 KB that need no opt-in)
+#ifndef Q4_PP_FFN13_WAVES              // (make exp EXPFLAGS=-DQ4_PP_FFN13_WAVES=9: the other grid of gate/up at N = 13824, for tools/bench_pass_13b.py --variant-libs)
+#define Q4_PP_FFN13_WAVES 12
+#endif
+constexpr int PP13_G = 3;              // tokens per group of the normalising gate/up launch
+constexpr int PP13_QKV_G = 2;          // ... of q/k/v, whose wave holds ten weight registers of four columns: three tokens spill 8 bytes at 168 registers
+constexpr int PP13_QKV_WAVES = 12;     // q/k/v: 3 x 1280 column groups = 320 blocks of twelve waves (fifteen-wave blocks, one per CU, are held to 128 registers and spill 164 bytes)
+constexpr int PP13_O_WAVES = 10;       // o-proj: 2560 column pairs = 256 blocks of ten waves, one per CU
+constexpr int PP13_FFN_WAVES = Q4_PP_FFN13_WAVES;   // gate/up: 6912 column pairs = 576 blocks of twelve waves, one resident per CU at 138 registers -- a 250-token ingest 314.1 ms against 318.7 with 768 blocks of nine waves (three per CU, 158 registers: also one resident), byte-equal; sixteen-wave blocks are held to 128 registers and spill
 
 // One wave owns COLS columns (KS = 2: one of the two k-parts of them); W / ZW / SC stay in registers while the tokens pass. Token t reads x + t * K and
 // writes out + t * N (q/k/v: q + t * N, cache rows p0 + t), p0 = *pPos -- the device position, which no launch of the pass but the last one moves.
@@ -45,8 +58,11 @@ constexpr size_t prompt_gemv_lds() {      // G tokens' permuted x and x-only sum
 }
 // GQA (q/k/v): k and v have a.N_kv < a.N columns each; the three matrices' column groups are still dealt as one range, N / 4 groups of q and then
 // N_kv / 4 of k and of v, every matrix with its own width in the descriptors, the clamp and the row addressing.
-// HALF (plain, K split): gemv_q4_body's shared half slot -- a k-part's last slot holds at most 32 units, lanes 0 - 31 take it for the even column of the
-// wave's pair and lanes 32 - 63 for the odd one, its term is added as a product and a sum and the other half of the wave adds 0.f.
+// HALF: gemv_q4_body's shared half slot -- the last slot (of a k-part: plain, K split; of the column: K = 5120, any mode) holds at most 32 units, lanes
+// 0 - 31 take it for the even column of each of the wave's pairs (c, c + 1) and lanes 32 - 63 for the odd one, its term is added as a product and a sum
+// and the other half of the wave adds 0.f. The pairs are the step's: q/k/v (col[0], col[1]) and (col[2], col[3]) -- the two first and the two second
+// halves of two adjacent RoPE pairs, columns i, i + 1 of a head --, o-proj and gate/up columns 2 wg and 2 wg + 1 of one matrix (an even column's terms
+// in lanes 0 - 31 in every step kernel: gemv_q4_body, attention_oproj16_kernel's o-proj role, both strips kernels).
 // STAGE (q/k/v of a model with the FP8 cache, GemvArgs::kv_stage): out[1] / out[2] are the pass's fp16 staging rows [ntok][N] -- token t's K / V row goes
 // to row t, not into a cache at loff + pos * N (prompt_pass_kv8.h appends them). A template flag: the fp16 instantiations are the code they were.
 template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false, bool STAGE = false>
@@ -54,7 +70,7 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
     constexpr int NMAT = ModeTraits<MODE>::NMAT;
     static_assert(!GQA || MODE == MODE_QKV, "per-matrix widths: q/k/v");
     static_assert(!STAGE || MODE == MODE_QKV, "staging rows: q/k/v");
-    static_assert(!HALF || (MODE == MODE_PLAIN && KS == 2 && COLS == 2), "shared half slot: one column pair per wave, K split");
+    static_assert(!HALF || (COLS % 2 == 0 && (KS == 1 || (MODE == MODE_PLAIN && COLS == 2))), "shared half slot: column pairs; with the K split one pair per wave");
     static_assert(G >= 1 && G <= 8, "exchange slots");
     static_assert(KS == 1 || (KS == 2 && MODE == MODE_PLAIN && !NORM), "K split: plain GEMV");
     static_assert(COLS >= 1 && COLS <= 4 && (MODE != MODE_QKV || COLS == 4), "one reduce4_q4 row per column; q/k/v: two RoPE pairs per wave");
@@ -143,13 +159,25 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
     const bool upper = lane >= 32u;
 #pragma unroll
     for (int s = 0; s < SLOTS; s++) {
-        if (HALF && s == SLOTS - 1) {                        // the shared half slot: the column offset per lane, kept in the pair's first entries
+        if (HALF && s == SLOTS - 1) {                        // the shared half slot: the column offset per lane, kept in each pair's first entries
             const unsigned jh = ubase + s * 64 + (lane & 31u);
             const unsigned jj = jh < uend ? jh : uend - 1;
-            const unsigned cw = upper ? (unsigned)colc[COLS - 1] : (unsigned)colc[0];
-            ZW[0][s][0] = __builtin_amdgcn_raw_buffer_load_b32(rz[0], (jj >> 5) * 4 + cw * a.pzh * 4, 0, Q4_ZS_AUX);
-            SC[0][s][0] = __builtin_amdgcn_raw_buffer_load_b16(rs[0], (jj >> 2) * 2 + cw * a.sh * 2, 0, Q4_ZS_AUX);
-            W[0][s][0] = __builtin_amdgcn_raw_buffer_load_b128(rw[0], jj * 16 + cw * a.pw4 * 16, 0, Q4_W_AUX);
+            if constexpr (KS == 2) {                         // (one pair, one matrix: the statements the K split's instantiation was compiled from)
+                const unsigned cw = upper ? (unsigned)colc[COLS - 1] : (unsigned)colc[0];
+                ZW[0][s][0] = __builtin_amdgcn_raw_buffer_load_b32(rz[0], (jj >> 5) * 4 + cw * a.pzh * 4, 0, Q4_ZS_AUX);
+                SC[0][s][0] = __builtin_amdgcn_raw_buffer_load_b16(rs[0], (jj >> 2) * 2 + cw * a.sh * 2, 0, Q4_ZS_AUX);
+                W[0][s][0] = __builtin_amdgcn_raw_buffer_load_b128(rw[0], jj * 16 + cw * a.pw4 * 16, 0, Q4_W_AUX);
+            } else {
+#pragma unroll
+                for (int m = 0; m < NMAT; m++)
+#pragma unroll
+                    for (int c = 0; c < COLS; c += 2) {
+                        const unsigned cw = upper ? (unsigned)colc[c + 1] : (unsigned)colc[c];
+                        ZW[m][s][c] = __builtin_amdgcn_raw_buffer_load_b32(rz[m], (jj >> 5) * 4 + cw * a.pzh * 4, 0, Q4_ZS_AUX);
+                        SC[m][s][c] = __builtin_amdgcn_raw_buffer_load_b16(rs[m], (jj >> 2) * 2 + cw * a.sh * 2, 0, Q4_ZS_AUX);
+                        W[m][s][c] = __builtin_amdgcn_raw_buffer_load_b128(rw[m], jj * 16 + cw * a.pw4 * 16, 0, Q4_W_AUX);
+                    }
+            }
             continue;
         }
         const unsigned j = ubase + s * 64 + lane;
@@ -259,7 +287,7 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
                 for (int s = 0; s < SLOTS; s++)
 #pragma unroll
                     for (int c = 0; c < COLS; c++)
-                        if (!(HALF && s == SLOTS - 1 && c > 0)) asm volatile("" : "+v"(W[m][s][c]));
+                        if (!(HALF && s == SLOTS - 1 && (c & 1))) asm volatile("" : "+v"(W[m][s][c]));
             // ---- 4. consume in slot order
             float colsum[NMAT][4];
 #pragma unroll
@@ -282,11 +310,23 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
                 for (int d = 0; d < 4; d++) X[d] = xst[xrow + (d << 6)];
                 const float corr = sxt[KS > 1 ? jx : (unsigned)(s * 64) + lu];
                 const unsigned zsh = ((j >> 2) & 7u) * 4u;
-                if (hs) {                                    // gemv_q4_body's half slot, word for word: lanes 0 - 31 worked for column 0, lanes 32 - 63 for column 1
-                    const float tt = q4_dot_unit(W[0][s][0], X, ZW[0][s][0], zsh, corr);
-                    const float v = h2f(SC[0][s][0]) * tt;
-                    colsum[0][0] += upper ? 0.f : v;
-                    colsum[0][COLS - 1] += upper ? v : 0.f;
+                if (hs) {                                    // gemv_q4_body's half slot, word for word: lanes 0 - 31 worked for column c, lanes 32 - 63 for column c + 1
+                    if constexpr (KS == 2) {
+                        const float tt = q4_dot_unit(W[0][s][0], X, ZW[0][s][0], zsh, corr);
+                        const float v = h2f(SC[0][s][0]) * tt;
+                        colsum[0][0] += upper ? 0.f : v;
+                        colsum[0][COLS - 1] += upper ? v : 0.f;
+                    } else {
+#pragma unroll
+                        for (int m = 0; m < NMAT; m++)
+#pragma unroll
+                            for (int c = 0; c < COLS; c += 2) {
+                                const float tt = q4_dot_unit(W[m][s][c], X, ZW[m][s][c], zsh, corr);
+                                const float v = h2f(SC[m][s][c]) * tt;
+                                colsum[m][c] += upper ? 0.f : v;
+                                colsum[m][c + 1] += upper ? v : 0.f;
+                            }
+                    }
                     continue;
                 }
 #pragma unroll
@@ -615,8 +655,30 @@ static bool pass_down_half_covers(int dim, int hidden) {
     const int ku = (divUp(g.pw4, 2) + 3) & ~3;
     return g.nslots >= 5 && g.nslots <= 8 && divUp(ku, 64) == 4 && ku - 192 <= 32 && ku * 2 >= g.pw4;
 }
+// Llama-2-13B's shape (q4_set_pass_13b): dim 5120 as forty 128-wide heads, multi-head, hidden 13824, an fp16 cache -- and the step on the forms the pass
+// restates: the K = 5120 matrices in strip_k5120's geometry (160 units, 40 scales and 5 zero words per column: two whole k-slots and the shared half
+// slot), the product's GEMV forms (every K = 5120 form of GEMV_PRODUCT puts an even column's half-slot terms in lanes 0 - 31; the profiling library's
+// other forms are not restated here: no pass), the half slot and the K split in force (pass_down_half_covers: q4_set_half_tail(0) moves q/k/v, o-proj,
+// gate/up AND down to other arithmetic, q4_set_ksplit(0 | 4) the down projection). Grouped-query, the FP8 cache (also with q4_set_pass_kv8 on) and other
+// hidden sizes at this width keep their steps: admit what is tested.
+static bool pass_13b_covers(const Config* p, const Model* m) {
+    const int dim = p->dim, hidden = p->hidden_dim;
+    if (!m->pass_13b || m->kv_format != Q4_KV_FP16 || dim != 5120 || p->n_heads * 128 != dim || p->n_heads != p->n_kv_heads || hidden != 13824) return false;
+    if (g_gemv_form != GEMV_PRODUCT || !pass_down_half_covers(dim, hidden)) return false;
+    for (const int n : {dim, hidden}) {
+        const QGeom g = make_geom(dim, n);
+        if (g.pw4 != 160 || g.sh != 40 || g.pzh != 5 || g.nslots != 3) return false;
+    }
+    return (3 * dim / 4) % PP13_QKV_WAVES == 0 && (dim / 2) % PP13_O_WAVES == 0 && (hidden / 2) % PP13_FFN_WAVES == 0 && dim % PP_WAVES == 0 &&
+           stream_cu_count() == cu_count();
+}
+#ifndef Q4_PP13_MIN                    // (make exp EXPFLAGS=-DQ4_PP13_MIN=2: passes of two and three positions at dim 5120 too, for tools/bench_pass_13b.py's section b)
+#define Q4_PP13_MIN 4
+#endif
+int prompt_pass_min(const Config* p) { return p->dim == 5120 ? Q4_PP13_MIN : 2; }
 bool prompt_pass_covers(const Config* p, const Model* m) {
     if (!p || !m || !m->rope_table || !m->sync) return false;
+    if (p->dim == 5120) return pass_13b_covers(p, m);
     if (m->kv_format != Q4_KV_FP16) {       // the FP8 cache: q4_set_pass_kv8, and a head the append and attention launches of prompt_pass_kv8.hip take (128, checked below)
         if (m->kv_format != Q4_KV_FP8 || !m->pass_kv8 || !m->k_exp || !m->v_exp || !kv8_head_size_ok(p->n_heads > 0 ? p->dim / p->n_heads : 0)) return false;
     }
@@ -642,6 +704,7 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
     const int kv_mul = p->n_heads / p->n_kv_heads, kv_dim = dim / kv_mul;
     const bool down_half = !ffn_pair_covers(dim, hidden);    // (prompt_pass_covers: then the shared-half-slot form)
+    const bool k13 = dim == 5120;                            // (prompt_pass_covers: q4_set_pass_13b's shape, K = 5120 in two k-slots and the shared half slot)
     Q4_TRY(prompt_pass_rows(m, p));
     PassScratch* const b = &m->pass;
     PassAttention plan = {};
@@ -668,6 +731,8 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
     constexpr size_t SMEM_DOWN_HALF = prompt_gemv_lds<4, 2, false, PP_DOWN_HALF_G>();
     static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024 && (SMEM_DOWN_HALF <= 64 * 1024 || PP_DOWN_HALF_G > 1), "no LDS opt-in in the shipped form");
+    constexpr size_t SMEM_NORM13 = prompt_gemv_lds<3, 1, true, PP13_G>(), SMEM_QKV13 = prompt_gemv_lds<3, 1, true, PP13_QKV_G>(), SMEM_O13 = prompt_gemv_lds<3, 1, false, 4>();
+    static_assert(SMEM_NORM13 <= 64 * 1024 && SMEM_O13 <= 64 * 1024, "no LDS opt-in in the shipped form");
     if (SMEM_DOWN_HALF > 64 * 1024)     // (an experiment build only)
         Q4_TRY(lds_opt_in((const void*)prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>, SMEM_DOWN_HALF));
     const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
@@ -675,7 +740,16 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
     for (int l = 0; l < p->n_layers; l++) {
         const PerLayerWeight* L = &w->layers[l];
         const long long loff = (long long)l * p->seq_len * kv_dim;
-        if (kv_mul > 1) {   // ... grouped-query: 1024 column groups of q, then 256 of k and of v, in six-wave blocks
+        if (k13) {   // rmsnorm + q/k/v + RoPE + K/V rows at K = 5120: 3 x 1280 column groups, the step's pairs (i, i + 1 of a head) on the half slot
+            GemvArgs a = {};
+            fill_geom(a, dim, dim);
+            fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
+            a.out[0] = b->q; a.out[1] = s->key_cache; a.out[2] = s->value_cache;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = s->pos; a.loff = loff;
+            a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
+            Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 3, 4, true, 1, PP13_QKV_G, PP13_QKV_WAVES, false, true>), dim3(3 * dim / (PP13_QKV_WAVES * 4)), dim3(PP13_QKV_WAVES * 64), SMEM_QKV13, a, n);
+            Q4_LAUNCH_CHECK();
+        } else if (kv_mul > 1) {   // ... grouped-query: 1024 column groups of q, then 256 of k and of v, in six-wave blocks
             GemvArgs a = {};
             fill_geom(a, dim, dim);
             a.N_kv = kv_dim;
@@ -728,20 +802,22 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
                       (unsigned)p->n_heads, natt, dim);
             Q4_LAUNCH_CHECK();
         }
-        {   // o-proj + residual
+        {   // o-proj + residual (K = 5120: a column pair per wave, the shared half slot)
             GemvArgs a = {};
             fill_geom(a, dim, dim);
             fill_mat(a.m[0], &L->wq_o);
             a.out[0] = b->x; a.x = b->xb; a.accum = 1;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 2, 1, false, 1, 4, PP_WAVES>), dim3(dim / PP_WAVES), dim3(TB), SMEM_O, a, n);
+            if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 1, 4, PP13_O_WAVES, false, true>), dim3(dim / (PP13_O_WAVES * 2)), dim3(PP13_O_WAVES * 64), SMEM_O13, a, n);
+            else Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 2, 1, false, 1, 4, PP_WAVES>), dim3(dim / PP_WAVES), dim3(TB), SMEM_O, a, n);
             Q4_LAUNCH_CHECK();
         }
-        {   // rmsnorm + gate/up + SiLU
+        {   // rmsnorm + gate/up + SiLU (K = 5120: a column pair of gate and of up per wave, the strips' pair units)
             GemvArgs a = {};
             fill_geom(a, dim, hidden);
             fill_mat(a.m[0], &L->wq_gate); fill_mat(a.m[1], &L->wq_up);
             a.out[0] = b->hb; a.x = b->x; a.rms_w = L->rms_ffn_weight;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
+            if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 3, 2, true, 1, PP13_G, PP13_FFN_WAVES, false, true>), dim3(hidden / (PP13_FFN_WAVES * 2)), dim3(PP13_FFN_WAVES * 64), SMEM_NORM13, a, n);
+            else Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         }
         if (down_half) {   // down projection + residual, the shared-half-slot form: two k-parts of three slots and a shared one, a column pair per wave

@@ -605,6 +605,15 @@ int q4_main(int argc, char** argv) {
             exit(EXIT_FAILURE);
         }
     }
+    // ... and passes for Llama-2-13B's shape (q4_set_pass_13b): Q4_PASS_13B=1
+    const char* pass_13b = getenv("Q4_PASS_13B");
+    if (pass_13b && *pass_13b) {
+        int on = 0;
+        if (q4_parse_pass_13b(pass_13b, &on) || q4_set_pass_13b(&transformer, on)) {
+            fprintf(stderr, "Q4_PASS_13B: cannot use '%s' (0 or 1: prompt and verify passes also for models of dim 5120 and hidden 13824, e.g. Llama-2-13B)\n", pass_13b);
+            exit(EXIT_FAILURE);
+        }
+    }
     // ... and passes while logit stages are on, with the guide's forced drafts (q4_set_pass_stages): Q4_PASS_STAGES=1
     const char* pass_stages = getenv("Q4_PASS_STAGES");
     if (pass_stages && *pass_stages) {

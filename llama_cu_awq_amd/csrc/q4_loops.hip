@@ -72,17 +72,21 @@ int q4_token_loop(Transformer* t, Sampler* sampler, const int* prompt_tokens, in
                 // entry `pos` -- everything queued so far -- and asks the drafter. The entry itself is looked at below, like any other: an EOS there stops the
                 // loop, and the pass queued behind it is surplus, as surplus steps are. No draft: the steps below, and the question again behind them.
                 int nd = 0, draft[VERIFY_MAX_DRAFT];
-                if (!np && sm && sm->spec_draft > 0 && pos >= num_prompt_tokens - 1 && verify_covers(t, sm, sampler, pos, 1, steps, off)) {
+                // (dmin: the fewest drafts a verify pass of this shape takes -- prompt_pass_min rows, 1 draft but for Llama-2-13B's shape; a shorter draft runs steps)
+                const int dmin = prompt_pass_min(&t->config) - 1;
+                if (!np && sm && sm->spec_draft >= dmin && pos >= num_prompt_tokens - 1 && verify_covers(t, sm, sampler, pos, dmin, steps, off)) {
                     Q4_TRY(q4_wait_pos(&t->state, pos));
                     int room = sm->spec_draft;
-                    while (room > 1 && !verify_covers(t, sm, sampler, pos, room, steps, off)) room--;
+                    while (room > dmin && !verify_covers(t, sm, sampler, pos, room, steps, off)) room--;
                     verify_forced = false;
                     if (pos == 0 || t->state.shared_data->tokens[pos] != 2) {    // (behind an EOS the loop stops: no pass)
                         // q4_set_pass_stages with a guide: where the automaton's state behind ring[pos] leaves one live token, the next tokens are known
                         // before the model runs -- the forced run first, the model's drafter only where it is empty
                         if (sm->pass_stages && sm->guide) Q4_TRY(guide_forced_draft(sm, (const int*)t->state.shared_data->tokens, pos, room, draft, &nd));
+                        if (nd < dmin) nd = 0;
                         verify_forced = nd > 0;
                         if (!nd) nd = ask_drafter(sm, (const int*)t->state.shared_data->tokens, pos + 1, room, t->config.vocab_size, draft);
+                        if (nd < dmin) nd = 0;
                     }
                 }
                 const int k = np ? np : nd ? 1 : q4_steps_that_fit(pos - off, num_prompt_tokens - off, steps - off, &t->config, sampler);

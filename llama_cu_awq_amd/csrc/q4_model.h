@@ -46,6 +46,7 @@ struct Model {
     bool pass_logprobs = false;     // q4_set_pass_logprobs: prompt and verify passes (and q4_score_ids through prompt passes) also while the records are on
     bool pass_gqa = false;          // q4_set_pass_gqa: prompt and verify passes also for the grouped-query 4096-wide shape (prompt_pass_covers)
     bool pass_kv8 = false;          // q4_set_pass_kv8: prompt and verify passes also for a model with the FP8 cache (prompt_pass_covers; prompt_pass_kv8.h)
+    bool pass_13b = false;          // q4_set_pass_13b: prompt and verify passes also for Llama-2-13B's shape, dim 5120 / hidden 13824 (prompt_pass_covers)
     bool pass_stages = false;       // q4_set_pass_stages: verify passes also with a guide, DRY or the sampling controls on (their row forms), prompt passes also with a guide or the adaptive truncation on
     ClsScreen screen;               // the int8 screening copy of wcls (cls_screen.h), base null: none -- the shape has no strips form, or the allocation failed
     const q4_guide* guide = nullptr;   // q4_set_guide: null off. The ring and the block are allocated with the model's first guide and live as long as the model

@@ -83,7 +83,7 @@ int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* samp
     if (n > pass_bin_end(pos) - pos) n = pass_bin_end(pos) - pos;
     if (n > pass_bound(p) - pos) n = pass_bound(p) - pos;
     // (state by position: the steps put it to NONE per prompt group; with q4_set_pass_stages on run_prompt_pass does the same)
-    if (n < 2 || (!m->pass_stages && (guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m))) || !prompt_pass_covers(p, m)) return 0;
+    if (n < prompt_pass_min(p) || (!m->pass_stages && (guide_stage.on(sampler, m) || adaptive_stage.on(sampler, m))) || !prompt_pass_covers(p, m)) return 0;
     PassAttention plan;
     return pass_attention_plan(p, &t->state, pos, n, &plan) ? n : 0;
 }
@@ -102,7 +102,7 @@ int prompt_pass_tokens(const Transformer* t, const Model* m, const Sampler* samp
 bool verify_covers(const Transformer* t, const Model* m, const Sampler* sampler, int pos, int n_draft, int steps, int off) {
     if (g_fusion < 3 || off != 0 || !m || !pass_records_ok(&t->config, m) || n_draft < 1 || n_draft > VERIFY_MAX_DRAFT || pos < 0) return false;
     const Config* p = &t->config;
-    if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps) return false;
+    if (pos + n_draft >= pass_bin_end(pos) || pos + n_draft >= pass_bound(p) || pos + n_draft >= steps || n_draft + 1 < prompt_pass_min(p)) return false;
     if (sampler && sampler->temperature != 0.0f) {
         // q4_set_speculative_sampled: the pass under the sampler -- the row form of its two launches (the on-chip vocabulary, a finite temperature above 0;
         // a negative one keeps the one-block softmax of the step) and a vocabulary that is the model's
@@ -293,6 +293,22 @@ int q4_get_pass_kv8(const Transformer* t) {
     return m && m->pass_kv8 ? 1 : 0;
 }
 int q4_parse_pass_kv8(const char* text, int* on) {     // the CLI's Q4_PASS_KV8: "0" or "1", nothing else
+    if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
+    *on = text[0] - '0';
+    return Q4_OK;
+}
+// Passes for Llama-2-13B's shape (prompt_pass_covers: dim 5120, hidden 13824): per model, off by default. No captured graph contains a pass: nothing to drop.
+int q4_set_pass_13b(Transformer* t, int on) {
+    Model* m = t ? model_of(&t->state) : nullptr;
+    if (!m) return Q4_ERR_ARG;
+    m->pass_13b = on != 0;
+    return Q4_OK;
+}
+int q4_get_pass_13b(const Transformer* t) {
+    const Model* m = t ? model_of(&t->state) : nullptr;
+    return m && m->pass_13b ? 1 : 0;
+}
+int q4_parse_pass_13b(const char* text, int* on) {     // the CLI's Q4_PASS_13B: "0" or "1", nothing else
     if (!text || !on || (text[0] != '0' && text[0] != '1') || text[1]) return Q4_ERR_ARG;
     *on = text[0] - '0';
     return Q4_OK;

@@ -45,7 +45,7 @@ struct VerifyDrafts { int n; int tok[VERIFY_MAX_DRAFT]; };
 // *out from draft[0 .. n_draft). Q4_ERR_ARG: draft null, n_draft outside [1, VERIFY_MAX_DRAFT], an id outside [0, vocab) (vocab < 0: ids are not checked)
 int verify_drafts(const int* draft, int n_draft, int vocab, VerifyDrafts* out);
 
-// Geometry the classifier launch of a pass takes: dim 4096 (eight 1 KiB pieces per vocabulary row) and a vocabulary that is a multiple of 8 -- both forms
+// Geometry the classifier launch of a pass takes: dim 4096 or 5120 (eight or ten 1 KiB pieces per vocabulary row) and a vocabulary that is a multiple of 8 -- both forms
 // classifier_with_final_norm can take for such a model (strips, or rmsnorm_kernel + gemv_f16_kernel) round the same sums in the same order.
 bool verify_cls_covers(int dim, int vocab);
 // logits [n][vocab] = wcls . rmsnorm(x[t], rms_w) for rows t < n <= PROMPT_PASS_MAX, x [n][dim]; on the launch stream

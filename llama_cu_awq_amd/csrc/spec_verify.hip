@@ -17,12 +17,18 @@ namespace q4 {
 // wave_sum and one rounding -- gemv_f16_kernel's and cls_strip_kernel's arithmetic (gemv_strip_cls.h), so a row's logits are the bits either writes for
 // that row alone. x in LDS and not in registers: eight rows of 32 VGPRs do not fit beside the weights; two weight rows per read of x halve the LDS
 // traffic (n x 8 KiB of LDS reads per 16 KiB of weights: at n = 8 four times the HBM stream's bytes, under a third of the LDS's rate).
-constexpr int VC_WAVES = 16, VC_NS = 8, VC_CHUNKS = VC_NS * 64;
-static size_t verify_cls_lds(int n) { return (size_t)n * VC_CHUNKS * 16 + 2 * VC_CHUNKS * 4; }
+// NC: 8-half chunks of a row -- 512 (dim 4096) or 640 (dim 5120, q4_set_pass_13b: ten pieces per row, gemv_f16_kernel's and cls_strip_kernel<10>'s
+// chain; the block normalises one row per round with its first ten waves, the canonical sum over 640 partials).
+constexpr int VC_WAVES = 16;
+static size_t verify_cls_lds(int n, int nc) { return (size_t)n * nc * 16 + 2 * (size_t)nc * 4; }
 
+template <int NC>
 __global__ void __launch_bounds__(VC_WAVES * 64) verify_cls_kernel(const u32x4* __restrict__ x, const u32x4* __restrict__ rms_w, const u32x4* __restrict__ wcls,
                                                                     q4_half* __restrict__ out, const int n, const int dim, const int d, const unsigned rbase,
                                                                     const unsigned rrem) {
+    constexpr int VC_CHUNKS = NC, VC_NS = NC / 64;
+    constexpr bool TWO = 2 * NC == VC_WAVES * 64;                                     // two rows per round, one per half of the block; else one, on the first NC threads
+    static_assert(NC % 64 == 0 && NC <= VC_WAVES * 64 && (TWO || 2 * NC > VC_WAVES * 64), "chunks of a row against the block");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4* xn = reinterpret_cast<u32x4*>(smem);                                       // [n][VC_CHUNKS]: chunk j = s * 64 + lane of row t
     float* part = reinterpret_cast<float*>(smem + (size_t)n * VC_CHUNKS * 16);        // [2][VC_CHUNKS]
@@ -32,15 +38,16 @@ __global__ void __launch_bounds__(VC_WAVES * 64) verify_cls_kernel(const u32x4* 
     const int nr = (int)(rbase + (blockIdx.x < rrem ? 1u : 0u));
     if (nr == 0) return;                                                              // (the whole block)
 
-    const unsigned c = tid & (VC_CHUNKS - 1);
-    const int half = wave >> 3;
+    const unsigned c = TWO ? tid & (VC_CHUNKS - 1) : (tid < (unsigned)VC_CHUNKS ? tid : (unsigned)VC_CHUNKS - 1u);
+    const int half = TWO ? wave >> 3 : 0;
+    const bool stager = TWO || tid < (unsigned)VC_CHUNKS;                             // (wave-uniform: NC is whole waves)
     const u32x4 wraw = rms_w[c];
-    for (int t0 = 0; t0 < n; t0 += 2) {
+    for (int t0 = 0; t0 < n; t0 += TWO ? 2 : 1) {
         const int t = t0 + half;
-        const bool act = t < n;                                                       // (wave-uniform)
+        const bool act = stager && t < n;                                             // (wave-uniform)
         u32x4 xraw = {0u, 0u, 0u, 0u};
         if (act) xraw = x[(size_t)t * VC_CHUNKS + c];
-        part[half * VC_CHUNKS + c] = sumsq8(xraw, 0.f);
+        if (stager) part[half * VC_CHUNKS + c] = sumsq8(xraw, 0.f);
         __syncthreads();
         if (act) xn[t * VC_CHUNKS + c] = rms_apply8(xraw, wraw, rms_scale_from_partials<VC_CHUNKS>(part + half * VC_CHUNKS, VC_CHUNKS, dim));
         __syncthreads();
@@ -80,16 +87,20 @@ __global__ void __launch_bounds__(VC_WAVES * 64) verify_cls_kernel(const u32x4* 
     }
 }
 
-bool verify_cls_covers(int dim, int vocab) { return dim == VC_CHUNKS * 8 && vocab >= 8 && (vocab & 7) == 0; }
+bool verify_cls_covers(int dim, int vocab) { return (dim == 4096 || dim == 5120) && vocab >= 8 && (vocab & 7) == 0; }
 
-int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n) {
-    if (!verify_cls_covers(dim, vocab) || n < 1 || n > PROMPT_PASS_MAX) return Q4_ERR_UNSUPPORTED_SIZE;
-    Q4_TRY(lds_opt_in((const void*)verify_cls_kernel, verify_cls_lds(PROMPT_PASS_MAX)));
+template <int NC>
+static int launch_verify_cls_nc(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n) {
+    Q4_TRY(lds_opt_in((const void*)verify_cls_kernel<NC>, verify_cls_lds(PROMPT_PASS_MAX, NC)));
     const unsigned nb = (unsigned)cu_count();
-    Q4_LAUNCH(verify_cls_kernel, dim3(nb), dim3(VC_WAVES * 64), verify_cls_lds(n), reinterpret_cast<const u32x4*>(x), reinterpret_cast<const u32x4*>(rms_w),
+    Q4_LAUNCH(verify_cls_kernel<NC>, dim3(nb), dim3(VC_WAVES * 64), verify_cls_lds(n, NC), reinterpret_cast<const u32x4*>(x), reinterpret_cast<const u32x4*>(rms_w),
               reinterpret_cast<const u32x4*>(wcls), logits, n, dim, vocab, (unsigned)vocab / nb, (unsigned)vocab % nb);
     Q4_LAUNCH_CHECK();
     return Q4_OK;
+}
+int launch_verify_cls(q4_half* logits, const q4_half* x, const q4_half* rms_w, const q4_half* wcls, int dim, int vocab, int n) {
+    if (!verify_cls_covers(dim, vocab) || n < 1 || n > PROMPT_PASS_MAX) return Q4_ERR_UNSUPPORTED_SIZE;
+    return dim == 4096 ? launch_verify_cls_nc<512>(logits, x, rms_w, wcls, dim, vocab, n) : launch_verify_cls_nc<640>(logits, x, rms_w, wcls, dim, vocab, n);
 }
 
 // ---- accept -----------------------------------------------------------------------------------------------------------------------------------------

@@ -81,6 +81,11 @@ GEOMETRIES = {
     # the Mistral-7B / Llama-3-8B layer, twice: 32 query heads over 8 K / V heads (kv_mul 4) at head 128, hidden 14336 (gate / up and down as strips),
     # pass_long's context -- every graph bin up to 4096 with grouped-query attention at width 4096 (tests/test_gqa7b_gpu.py)
     "gqa7b_pair": (4096, 14336, 2, 32, 8, 512, 2304, 500000.0),
+    # the Llama-2-13B layer, twice: dim 5120 (K = 5120: two whole k-slots and the shared half slot), forty 128-wide heads, hidden 13824, pass_long's
+    # context -- prompt and verify passes at this width (q4_set_pass_13b, tests/test_pass_13b_gpu.py) in every graph bin up to 4096
+    "k5120_pair": (5120, 13824, 2, 40, 40, 512, 2304, 10000.0),
+    # ... once, with Llama-2's vocabulary: the verify pass's classifier beside the step's strips form (125 rows per CU) and the sampled pass
+    "k5120_cls": (5120, 13824, 1, 40, 40, 32000, 300, 10000.0),
 }
 
 
