@@ -839,6 +839,54 @@ int q4_snapshot_check(const void* host, size_t bytes, struct q4_snapshot_info* o
  * byte of the first run to last byte of the last) that overlap. */
 int q4_copy_runs(void* dst, const void* src, long long outer, long long dst_stride, long long src_stride, long long run_bytes);
 
+/* ---- batched decoding (q4_batch.hip; not in the reference) ------------------------------------------
+ * A batch holds up to Q4_BATCH_MAX_SLOTS sequences ("slots") over ONE Transformer's weights; one pass advances every open slot by one position on one read
+ * of the weights (the rows of a prompt pass, each row another sequence). A slot owns an fp16 K / V cache of the model's geometry, a token ring, a position,
+ * a seed and a logits row. Everything a slot produces -- tokens, K / V rows, the logits of its last position -- is byte for byte what the same checkpoint
+ * produces when it runs that sequence alone (q4_generate_ids with rng_seed = the slot's seed), whatever the other slots do. The model's own sequence (its
+ * cache, ring, position, logits) is not touched. Passes run eagerly on the q4 stream; no captured graph contains one. There is no EOS rule: a host closes
+ * a slot when it has seen enough. Delete a batch before its Transformer.
+ * Admitted (q4_batch_covers; anything else: Q4_ERR_UNSUPPORTED_SIZE from q4_batch_new, nothing launched): dim 4096 in 128-wide heads -- Llama-2-7B's layer
+ * shape, or the grouped-query one with four query heads per K / V head and a hidden size whose down projection runs the shared-half-slot form (Mistral-7B,
+ * Llama-3-8B) --, a vocabulary that is a multiple of 8, the fp16 cache, no guide, no log-probability records. A step under a Sampler with a logit stage on
+ * (sampling controls, bias, DRY, adaptive truncation), with a guide or records switched on since, at a fusion level below 3, or with a temperature the row
+ * sampler does not take (q4_verify_sample_rows: vocabulary <= 32768, a finite temperature > 0) is refused the same way. A call that returns Q4_ERR_HIP
+ * leaves the batch unusable: delete it. */
+#define Q4_BATCH_MAX_SLOTS 8
+typedef struct q4_batch q4_batch;                       /* opaque */
+int q4_batch_covers(const Transformer* t);              /* 1 where q4_batch_new would build a batch, else 0 */
+/* n_slots in 1 .. Q4_BATCH_MAX_SLOTS (else Q4_ERR_ARG); allocates n_slots caches of 2 x n_layers x seq_len x kv_dim halves and the pass's scratch, and
+ * releases what it had allocated when an allocation fails (Q4_ERR_ALLOC). The caches start zeroed. */
+int q4_batch_new(q4_batch** out, Transformer* t, int n_slots);
+int q4_batch_delete(q4_batch* b);                       /* synchronises the q4 stream first */
+/* Opens a closed slot at position 0 on prompt[0 .. n_prompt): while the slot is inside its prompt its row carries the next prompt token and the token
+ * computed for that row is discarded, as a prompt step does; the pass at position n_prompt - 1 produces the first generated token. seed: the slot's coin
+ * stream, one coin per position from 0 (q4_generate_ids' rule). Q4_ERR_ARG: a null pointer, a slot outside the batch or already open, n_prompt outside
+ * 1 .. seq_len, a token outside the vocabulary. */
+int q4_batch_open(q4_batch* b, int slot, const int* prompt, int n_prompt, unsigned long long seed);
+/* Opens a closed slot behind a prefix someone already ingested: the snapshot's rows are copied into the slot's cache (q4_kv_copy.hip's launch, in stream
+ * order) and the slot starts at position n_pos of the snapshot on prompt[0 .. n_prompt), whose first n_pos tokens must be the snapshot's and n_prompt > n_pos;
+ * the coin stream stands where n_pos steps leave it. This is how a host uses prompt passes on the model's own sequence for long prompts. Q4_ERR_ARG:
+ * q4_batch_open's, q4_snapshot_restore's (fingerprint, geometry, rope_theta, K / V format, n_pos above seq_len), or a prompt that does not begin with the
+ * snapshot's tokens. */
+int q4_batch_restore(q4_batch* b, int slot, const q4_snapshot* s, const int* prompt, int n_prompt, unsigned long long seed);
+int q4_batch_close(q4_batch* b, int slot);              /* the slot's rows and logits stay readable until it is opened again; Q4_ERR_ARG: not open */
+/* One pass over the weights: every open slot advances by one position. tokens_out [Q4_BATCH_MAX_SLOTS]: the slot's generated token, or -1 for a closed
+ * slot, a slot outside the batch and a slot still inside its prompt. sampler: temperature 0 greedy (the step's argmax and tie-breaking), else the
+ * temperature / top-p sampler's row form with each slot's own coin; its rng_state is not used. Synchronises. Q4_ERR_ARG: a null pointer, or an open slot
+ * that stands at seq_len (close it); nothing ran. No open slot: Q4_OK, nothing ran. */
+int q4_batch_step(q4_batch* b, Sampler* sampler, int* tokens_out);
+/* Up to `steps` passes queued back to back -- tokens stay on the device between passes -- and one synchronise at the end; stops early in front of a pass
+ * in which an open slot would stand at seq_len. out [steps][Q4_BATCH_MAX_SLOTS]: row i is q4_batch_step's tokens_out of pass i; *n_out: passes run. */
+int q4_batch_generate(q4_batch* b, Sampler* sampler, int steps, int* out, int* n_out);
+/* What the tests read; each synchronises. q4_batch_pos: the slot's position on the device (negative: -Q4_ERR_ARG); logits: the vocab halves of the slot's
+ * last position (fp16 probabilities behind a sampled pass, as a sampled step leaves them); a K / V row of the slot's cache; the device addresses of the
+ * slot's K and V caches, each [n_layers][seq_len][kv_dim] halves. */
+int q4_batch_pos(const q4_batch* b, int slot);
+int q4_batch_get_logits(const q4_batch* b, int slot, q4_half* host_out);
+int q4_batch_get_kv_row(const q4_batch* b, int slot, int layer, int pos, q4_half* host_k, q4_half* host_v);
+int q4_batch_cache(const q4_batch* b, int slot, q4_half** key_cache, q4_half** value_cache);
+
 /* ---- context shift (q4_kv_shift.hip; not in the reference) ----------------------------------------
  * A sequence ends at seq_len: the K / V cache has that many rows. Context shift (the StreamingLLM / llama.cpp operation) keeps the first n_keep
  * positions, discards the n_discard = D positions behind them, slides everything above down by D and goes on at position n_pos - D: V rows move bit

@@ -212,6 +212,8 @@ SYMBOLS = [
     "q4_set_pass_kv8", "q4_get_pass_kv8", "q4_parse_pass_kv8", "q4_set_pass_13b", "q4_get_pass_13b", "q4_parse_pass_13b",
     "q4_set_pass_stages", "q4_get_pass_stages", "q4_parse_pass_stages", "q4_guide_mask_rows", "q4_dry_penalty_rows", "q4_process_logits_rows",
     "q4_guide_forced_run", "q4_spec_stats_forced",
+    "q4_batch_covers", "q4_batch_new", "q4_batch_delete", "q4_batch_open", "q4_batch_restore", "q4_batch_close", "q4_batch_step", "q4_batch_generate",
+    "q4_batch_pos", "q4_batch_get_logits", "q4_batch_get_kv_row", "q4_batch_cache",
 ]
 
 _lib = None
@@ -430,6 +432,19 @@ def lib():
         L.q4_snapshot_import.argtypes = [C.POINTER(vp), vp, C.c_size_t]
         L.q4_snapshot_check.argtypes = [vp, C.c_size_t, C.POINTER(SnapshotInfo)]
         L.q4_copy_runs.argtypes = [vp, vp, ll, ll, ll, ll]
+    if hasattr(L, "q4_batch_new"):                 # (older builds under tools/ab.py do not have it)
+        L.q4_batch_covers.argtypes = [vp]
+        L.q4_batch_new.argtypes = [C.POINTER(vp), vp, i]
+        L.q4_batch_delete.argtypes = [vp]
+        L.q4_batch_open.argtypes = [vp, i, vp, i, C.c_ulonglong]
+        L.q4_batch_restore.argtypes = [vp, i, vp, vp, i, C.c_ulonglong]
+        L.q4_batch_close.argtypes = [vp, i]
+        L.q4_batch_step.argtypes = [vp, vp, vp]
+        L.q4_batch_generate.argtypes = [vp, vp, i, vp, C.POINTER(i)]
+        L.q4_batch_pos.argtypes = [vp, i]
+        L.q4_batch_get_logits.argtypes = [vp, i, vp]
+        L.q4_batch_get_kv_row.argtypes = [vp, i, i, i, vp, vp]
+        L.q4_batch_cache.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp)]
     if hasattr(L, "q4_shift_context"):             # (older builds under tools/ab.py do not have it)
         L.q4_shift_context.argtypes = [vp, i, i, i, i]
         L.q4_set_context_shift.argtypes = [vp, i, i]
@@ -1370,6 +1385,90 @@ class Transformer:
         if us < 0:
             raise Q4Error("bench_kernel_graph failed: " + lib().q4_last_error().decode())
         return us
+
+
+BATCH_MAX_SLOTS = 8
+
+
+class Batch:
+    """q4_batch: up to BATCH_MAX_SLOTS sequences over one Transformer's weights, every open one advanced by one position per pass over the weights
+    (csrc/q4_batch.h). A slot's tokens, K / V rows and logits are byte for byte those of the same checkpoint running that sequence alone with the slot's
+    seed. The model's sampler decides greedy or temperature / top-p; its own sequence is not touched. delete() the batch before the Transformer closes."""
+
+    def __init__(self, transformer, slots):
+        self.t = transformer
+        self.slots = int(slots)
+        h = C.c_void_p()
+        check(lib().q4_batch_new(C.byref(h), transformer.h, self.slots))
+        self.h = h.value
+
+    @staticmethod
+    def covers(transformer):
+        return bool(lib().q4_batch_covers(transformer.h))
+
+    def open(self, slot, prompt, seed=1):
+        """q4_batch_open: the slot starts at position 0 on `prompt`; seed: its coin stream (Transformer(seed=...) of the run alone)"""
+        p = np.ascontiguousarray(prompt, dtype=np.int32)
+        check(lib().q4_batch_open(self.h, int(slot), p.ctypes.data, p.shape[0], int(seed)))
+
+    def restore(self, slot, snap, prompt, seed=1):
+        """q4_batch_restore: the slot starts at position snap.n_pos behind the snapshot's rows; `prompt` begins with the snapshot's tokens and is longer"""
+        p = np.ascontiguousarray(prompt, dtype=np.int32)
+        check(lib().q4_batch_restore(self.h, int(slot), snap.h, p.ctypes.data, p.shape[0], int(seed)))
+
+    def step(self):
+        """q4_batch_step: one pass; int32 [BATCH_MAX_SLOTS], the generated token per slot or -1 (closed, or still inside its prompt)"""
+        out = np.empty(BATCH_MAX_SLOTS, dtype=np.int32)
+        check(lib().q4_batch_step(self.h, self.t.sampler, out.ctypes.data))
+        return out
+
+    def generate(self, steps):
+        """q4_batch_generate: up to `steps` passes queued back to back, one synchronise; int32 [passes run, BATCH_MAX_SLOTS]"""
+        out = np.empty((int(steps), BATCH_MAX_SLOTS), dtype=np.int32)
+        n = C.c_int()
+        check(lib().q4_batch_generate(self.h, self.t.sampler, int(steps), out.ctypes.data, C.byref(n)))
+        return out[: n.value]
+
+    def pos(self, slot):
+        n = lib().q4_batch_pos(self.h, int(slot))
+        if n < 0:
+            check(-n)
+        return n
+
+    def logits(self, slot):
+        out = np.empty(self.t.config.vocab_size, dtype=np.float16)
+        check(lib().q4_batch_get_logits(self.h, int(slot), out.ctypes.data))
+        return out
+
+    def kv_row(self, slot, layer, pos):
+        cfg = self.t.config
+        kv_dim = cfg.dim * cfg.n_kv_heads // cfg.n_heads
+        k = np.empty(kv_dim, dtype=np.float16)
+        v = np.empty(kv_dim, dtype=np.float16)
+        check(lib().q4_batch_get_kv_row(self.h, int(slot), int(layer), int(pos), k.ctypes.data, v.ctypes.data))
+        return k, v
+
+    def cache(self, slot):
+        """(key_cache, value_cache) device addresses of the slot's caches, each [n_layers][seq_len][kv_dim] halves"""
+        k, v = C.c_void_p(), C.c_void_p()
+        check(lib().q4_batch_cache(self.h, int(slot), C.byref(k), C.byref(v)))
+        return k.value, v.value
+
+    def close(self, slot):
+        """q4_batch_close: the slot's rows and logits stay readable until it is opened again"""
+        check(lib().q4_batch_close(self.h, int(slot)))
+
+    def delete(self):
+        """q4_batch_delete: the whole batch, every slot's cache with it"""
+        if getattr(self, "h", None):
+            check(lib().q4_batch_delete(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.delete()
+        except Exception:
+            pass
 
 
 class Tokenizer:

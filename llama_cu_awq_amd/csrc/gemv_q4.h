@@ -68,6 +68,7 @@ struct GemvArgs {
     int early;                 // waves in the first `early` slots of a SIMD issue their weight loads before the staging ends
     unsigned* bump;            // QKV: epoch word of the FOLLOWING attention + o-proj launch, advanced once by block (0, 0)
     int kv_stage;              // QKV: out[1] / out[2] are ROWS (the FP8 cache's fp16 staging rows, attention_kv8.h), not caches: no loff + pos * N
+    q4_half* const* row_kv;    // QKV of a batch pass (prompt_gemv_kernel<.., ROWS>; q4_batch.h): [2][8] cache bases by row, K then V, in place of out[1] / out[2]; pPos is then the rows' [8] positions
 };
 
 // In-launch hand-off (layer_attn.hip: attention -> o-proj as ONE launch) with data-tagged granules: a vector

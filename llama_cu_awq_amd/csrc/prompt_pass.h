@@ -56,5 +56,16 @@ int pass_logit_rows(Model* m, const Config* p);
 int pass_side_rows(Model* m, const Config* p);
 int pass_draft_view(Model* m, const Config* p);   // Model::pass.view, [seq_len] ints: the draft view of a verify pass with logit stages (spec_verify.h)
 int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n);
+// A scratch that is not a model's (the batch's, q4_batch.h): the rows of prompt_pass_rows in *b; the split passes' records grown to `floats` (synchronises
+// where an older area may still be read); what pass_release does for a model's
+int pass_scratch_rows(PassScratch* b, const Config* p);
+int pass_records_of(PassScratch* b, size_t floats);
+void pass_scratch_release(PassScratch* b);
+// The rows one launch of a batch pass runs, by value in its arguments: n rows of the pass, row[i] their indices; nsp_of_bin[i] (the merge launch): the chunk
+// count the step merges at row i's position, 0: those up to the position itself (PassAttention::nsp_of_bin)
+struct PassRowList { int n; int row[PROMPT_PASS_MAX]; int nsp_of_bin[PROMPT_PASS_MAX]; };
+// The batch pass's side of this file (q4_batch.h): its admission by shape, and the layer loop over n rows of different sequences (their comments there)
+bool batch_pass_covers(const Config* p, const Model* m);
+int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv);
 
 }  // namespace q4

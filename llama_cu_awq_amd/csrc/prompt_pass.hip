@@ -12,6 +12,8 @@
 // Llama-2-13B's shape (q4_set_pass_13b; DESIGN.md 3.7 "13B"): K = dim = 5120 is two whole k-slots and the step's shared half slot (HALF without a K
 // split) in the q/k/v, o-proj and gate/up launches -- a column pair per wave in the latter two --, the norm over 640 chunk partials and 128 zeros, the
 // down projection in the K split's shared-half-slot form as for the grouped-query shape.
+// A batch pass (q4_batch.h): the rows are the current positions of DIFFERENT sequences -- the q/k/v launch and the attention launches in their
+// row forms (ROWS: a row's position and cache from per-row tables; a launch names the rows it runs), o-proj / gate-up / down as above (batch_pass_layers).
 //
 // The arithmetic is the per-token path's, bit for bit: a column's value in the int4 GEMV family is fixed by the staging (q4_stage_chunk on units negated by
 // parity), the per-lane chain over its k-slots in slot order (fma(scale, q4_dot_unit, c)), reduce4_q4 (a row's total depends on that row's input alone) and
@@ -65,9 +67,13 @@ constexpr size_t prompt_gemv_lds() {      // G tokens' permuted x and x-only sum
 // in lanes 0 - 31 in every step kernel: gemv_q4_body, attention_oproj16_kernel's o-proj role, both strips kernels).
 // STAGE (q/k/v of a model with the FP8 cache, GemvArgs::kv_stage): out[1] / out[2] are the pass's fp16 staging rows [ntok][N] -- token t's K / V row goes
 // to row t, not into a cache at loff + pos * N (prompt_pass_kv8.h appends them). A template flag: the fp16 instantiations are the code they were.
-template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false, bool STAGE = false>
+// ROWS (q/k/v of a batch pass, q4_batch.h: the rows belong to different sequences): row t sits at position a.pPos[t] -- its rotation-table row and its
+// cache row -- instead of *a.pPos + t, and its K / V row goes into the cache a.row_kv[t] (K) / a.row_kv[PROMPT_PASS_MAX + t] (V) at loff + pos * N.
+// Which rotation and which address a row gets is all that changes: its sums are the ones above. A template flag again.
+template <int MODE, int SLOTS, int COLS, bool NORM, int KS, int G, int NW, bool GQA = false, bool HALF = false, bool STAGE = false, bool ROWS = false>
 __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, const int ntok) {
     constexpr int NMAT = ModeTraits<MODE>::NMAT;
+    static_assert(!ROWS || (MODE == MODE_QKV && !STAGE), "per-row positions and caches: q/k/v into fp16 caches");
     static_assert(!GQA || MODE == MODE_QKV, "per-matrix widths: q/k/v");
     static_assert(!STAGE || MODE == MODE_QKV, "staging rows: q/k/v");
     static_assert(!HALF || (COLS % 2 == 0 && (KS == 1 || (MODE == MODE_PLAIN && COLS == 2))), "shared half slot: column pairs; with the K split one pair per wave");
@@ -120,7 +126,7 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
     for (int c = 0; c < COLS; c++) colc[c] = col[c] < N ? col[c] : N - 1;
 
     int p0 = 0;
-    if (MODE == MODE_QKV) p0 = *a.pPos;
+    if (MODE == MODE_QKV && !ROWS) p0 = *a.pPos;
 
     // ---- the first activations, the norm weights, then every weight / zero / scale of the wave (gemv_q4_body's loads: clamped, bounded descriptors).
     // A normalising kernel (K = 4096: one chunk per thread) holds a whole group's chunks; the others hold one token's and fetch the next while they stage.
@@ -264,13 +270,19 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
         const bool out_lane = writer && (MODE == MODE_QKV || row < COLS) && (KS == 1 || khalf == 0) && n_out < N;
         uint16_t resid[G];
         float2 rot[G];
+        int posr[ROWS ? G : 1];                              // ROWS: the group's positions
 #pragma unroll
         for (int g = 0; g < G; g++) {
             resid[g] = 0;
             rot[g] = float2{1.f, 0.f};
+            if constexpr (ROWS) posr[g] = a.pPos[g < ng ? t0 + g : t0];
             if (g < ng) {
                 if (MODE == MODE_PLAIN && a.accum && out_lane) resid[g] = a.out[0][(size_t)(t0 + g) * N + n_out];
-                if (MODE == MODE_QKV && mat0 < 2) rot[g] = a.rope_table[(size_t)(p0 + t0 + g) * (a.head_size >> 1) + qkv_i];
+                if constexpr (ROWS) {
+                    if (mat0 < 2) rot[g] = a.rope_table[(size_t)posr[g] * (a.head_size >> 1) + qkv_i];
+                } else {
+                    if (MODE == MODE_QKV && mat0 < 2) rot[g] = a.rope_table[(size_t)(p0 + t0 + g) * (a.head_size >> 1) + qkv_i];
+                }
             }
         }
 
@@ -360,10 +372,13 @@ __global__ void __launch_bounds__(NW * 64) prompt_gemv_kernel(const GemvArgs a, 
                 val *= uu;                                   // :272
                 if (out_lane) a.out[0][(size_t)t * N + n_out] = f2h(val);
             } else {                                         // MODE_QKV: rows = pair0 first, pair1 first, pair0 second, pair1 second
-                const int pos = p0 + t;
+                const int pos = ROWS ? posr[ROWS ? g : 0] : p0 + t;
                 q4_half* out = mat0 == 0 ? a.out[0] + (size_t)t * N : a.out[mat0] + (size_t)a.loff + (size_t)pos * N;
                 if constexpr (STAGE) {
                     if (mat0 != 0) out = a.out[mat0] + (size_t)t * N;
+                }
+                if constexpr (ROWS) {
+                    if (mat0 != 0) out = a.row_kv[(mat0 - 1) * PROMPT_PASS_MAX + t] + (size_t)a.loff + (size_t)pos * N;
                 }
                 const float mine = reduce4_q4(colsum[0][0], colsum[0][1], colsum[0][2], colsum[0][3]) * 1048576.f;
                 float r = mine;
@@ -400,6 +415,31 @@ __global__ void __launch_bounds__(LA16_WAVES * 64) prompt_attention_kernel(const
     }
 }
 
+// The row form for a batch pass (q4_batch.h): the rows of one pass belong to different sequences, so a launch names the rows it runs (the ones whose
+// step takes this attention form) and every row reads its own cache -- kv[row] (K) / kv[PROMPT_PASS_MAX + row] (V) plus the layer's offset. Block b of
+// listed row i is prompt_attention_kernel's block b of token t = list.row[i]: the same unit at the same position over that sequence's rows.
+__global__ void __launch_bounds__(LA16_WAVES * 64) prompt_attention_rows_kernel(const AttArgs a0, const int* pos_arr, u32x2v* sink, const unsigned sink_stride,
+                                                                                const unsigned nheads, const unsigned natt, const int dim, const PassRowList list,
+                                                                                q4_half* const* kv, const long long loff) {
+    const unsigned t = (unsigned)list.row[blockIdx.x / natt], b = blockIdx.x % natt;
+    AttArgs a = a0;
+    a.pPos = pos_arr + t;
+    a.q = a0.q + (size_t)t * dim;
+    a.output = a0.output + (size_t)t * dim;
+    a.key_cache = kv[t] + loff;
+    a.value_cache = kv[PROMPT_PASS_MAX + t] + loff;
+    Handoff ho = {};
+    ho.pub = sink + (size_t)t * sink_stride;
+    const int pos = __builtin_amdgcn_readfirstlane(pos_arr[t]);
+    if (pos < 128) {
+        a.lds_scores = 128;
+        attention_body<16, 2, LA16_WAVES, 2, false, 4, 0, 8>(a, (int)(b % nheads), ho, (int)(b / nheads));
+    } else {
+        a.lds_scores = 256;
+        attention_body<16, 4, LA16_WAVES, 2, false, 4, 128, 8>(a, (int)(b % nheads), ho, (int)(b / nheads));
+    }
+}
+
 // Attention of a pass whose tokens sit in the split-context bins (positions >= 256 where the step runs forms 4 / 2 / 3 inside attention_oproj_kernel:
 // one block of LA_WAVES waves per (head, chunk of 64 / 128 / 256 positions), a flash-decode record per chunk, the records merged in chunk order). Block
 // (h, sp) requests the chunk's K and V rows ONCE -- split_live's request order and policy, clamped to the last row the pass may read -- and loops over the
@@ -421,8 +461,22 @@ struct PassSplitArgs {
     size_t tok_stride;           // floats between two tokens' record areas
     float alpha;
 };
-template <int U>
-__global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(const PassSplitArgs a) {
+// ROWS, the row form for a batch pass (q4_batch.h): one block per (head, chunk, listed row) runs this body for ONE token -- row t = list.row[z] with its
+// own q, position, record area and cache (row_kv[t] / row_kv[PROMPT_PASS_MAX + t] plus the layer's offset) -- so a row's records are the ones a one-token pass of
+// that sequence writes. a.key_cache / a.value_cache are then not read; a.nsp: the chunks this launch lays the records out by, the most of its rows' counts.
+// A template flag: without it the three trailing arguments are not read and the kernel is the code it was.
+template <int U, bool ROWS = false>
+__global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(const PassSplitArgs a0, const PassRowList list, q4_half* const* row_kv, const long long loff) {
+    PassSplitArgs a = a0;
+    if constexpr (ROWS) {
+        const int t = list.row[blockIdx.z];
+        a.records = a0.records + (size_t)t * a0.tok_stride;
+        a.q = a0.q + (size_t)t * a0.dim;
+        a.key_cache = row_kv[t] + loff;
+        a.value_cache = row_kv[PROMPT_PASS_MAX + t] + loff;
+        a.pos = a0.pos + t;
+        a.ntok = 1;
+    }
     constexpr int LPR = 16, NW = LA_WAVES, R = 64 / LPR, stride = NW * R, CHUNK = stride * U, HS = LPR * 8;
     __shared__ __attribute__((aligned(16))) float lds[32 + NW * HS];
     float* red_max = lds;
@@ -538,6 +592,16 @@ __global__ void __launch_bounds__(128) prompt_merge_kernel(q4_half* xb, const fl
         combine_partials<false>(xb + (size_t)t * dim + (size_t)h * head_size, base, head_size, n_merge, n);
 }
 
+// ... of the listed rows of a batch pass: row t = list.row[y] merges list.nsp_of_bin[y] chunks (0: those up to its own position), the step's count at its position
+__global__ void __launch_bounds__(128) prompt_merge_rows_kernel(q4_half* xb, const float* records, const int* pos, int dim, int head_size, int nsp, size_t tok_stride,
+                                                                const PassRowList list, int chunk) {
+    const int h = blockIdx.x, t = list.row[blockIdx.y];
+    const int n_merge = list.nsp_of_bin[blockIdx.y] ? list.nsp_of_bin[blockIdx.y] : (pos[t] + chunk) / chunk;
+    const float* base = records + (size_t)t * tok_stride + (size_t)h * nsp * (head_size + ATT_REC_PAD);
+    for (int n = threadIdx.x; n < head_size; n += blockDim.x)
+        combine_partials<false>(xb + (size_t)t * dim + (size_t)h * head_size, base, head_size, n_merge, n);
+}
+
 // the n tokens' embedding rows, and the positions of the pass for its attention blocks
 __global__ void prompt_embed_kernel(q4_half* xs, const q4_half* table, int dim, const int* tokens, const int* pPos, int* pos_arr) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
@@ -560,14 +624,16 @@ __global__ void __launch_bounds__(1024) prompt_finish_kernel(q4_half* x, const q
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-void pass_release(Model* m) {
-    for (void* d : {m->pass.slab, (void*)m->pass.records, (void*)m->pass.logit_rows, (void*)m->pass.lp_side, (void*)m->pass.view, (void*)m->pass.kv_stage})
+void pass_scratch_release(PassScratch* b) {
+    for (void* d : {b->slab, (void*)b->records, (void*)b->logit_rows, (void*)b->lp_side, (void*)b->view, (void*)b->kv_stage})
         if (d) (void)hipFree(d);
-    m->pass = PassScratch{};
+    *b = PassScratch{};
 }
+void pass_release(Model* m) { pass_scratch_release(&m->pass); }
 
-int prompt_pass_rows(Model* m, const Config* p) {
-    PassScratch& b = m->pass;
+int prompt_pass_rows(Model* m, const Config* p) { return pass_scratch_rows(&m->pass, p); }
+int pass_scratch_rows(PassScratch* scratch, const Config* p) {
+    PassScratch& b = *scratch;
     if (!b.slab) {
         const size_t T = PROMPT_PASS_MAX, dim = p->dim, hidden = p->hidden_dim;
         const size_t sink_words = line_area_words(dim / 2);      // 32-bit words of one token's granule area
@@ -624,7 +690,7 @@ static int pass_kv_stage_rows(Model* m, int kv_dim) {
 
 // The split passes' flash-decode records: the pass's own buffer (never RunState::att, whose words are validated by tag), allocated on the first split
 // pass of the model for the longest context it can meet -- PROMPT_PASS_MAX tokens x heads x chunks x (head_size + ATT_REC_PAD) floats.
-static int pass_records_of(PassScratch* b, size_t floats) {
+int pass_records_of(PassScratch* b, size_t floats) {
     if (b->record_floats >= floats) return Q4_OK;
     if (b->records) {
         Q4_HIP(hipStreamSynchronize(g_stream));              // a pass that reads the old area may still be in flight
@@ -676,16 +742,14 @@ static bool pass_13b_covers(const Config* p, const Model* m) {
 #define Q4_PP13_MIN 4
 #endif
 int prompt_pass_min(const Config* p) { return p->dim == 5120 ? Q4_PP13_MIN : 2; }
-bool prompt_pass_covers(const Config* p, const Model* m) {
-    if (!p || !m || !m->rope_table || !m->sync) return false;
-    if (p->dim == 5120) return pass_13b_covers(p, m);
-    if (m->kv_format != Q4_KV_FP16) {       // the FP8 cache: q4_set_pass_kv8, and a head the append and attention launches of prompt_pass_kv8.hip take (128, checked below)
-        if (m->kv_format != Q4_KV_FP8 || !m->pass_kv8 || !m->k_exp || !m->v_exp || !kv8_head_size_ok(p->n_heads > 0 ? p->dim / p->n_heads : 0)) return false;
-    }
+// The two 4096-wide layer shapes the pass kernels restate, in ONE place for the passes' admission and the batch's (batch_pass_covers): 128-wide heads;
+// multi-head with a hidden size the FFN pair launch takes (the down projection as the two-part K split in three k-slots, no shared half slot: Llama-2-7B),
+// or -- gqa: the caller admits grouped-query models -- four query heads per K / V head and the half-slot down form (Mistral-7B, Llama-3-8B: what the tests run)
+static bool pass_shape_4096_covers(const Config* p, bool gqa) {
     const int dim = p->dim, hidden = p->hidden_dim;
     if (dim != 4096 || p->n_heads * 128 != dim || (hidden & 31)) return false;
-    if (p->n_heads != p->n_kv_heads) {      // grouped-query: q4_set_pass_gqa, four query heads per K / V head and the half-slot down form (Mistral-7B, Llama-3-8B: what the tests run)
-        if (!m->pass_gqa || p->n_kv_heads < 1 || p->n_heads != 4 * p->n_kv_heads) return false;
+    if (p->n_heads != p->n_kv_heads) {
+        if (!gqa || p->n_kv_heads < 1 || p->n_heads != 4 * p->n_kv_heads) return false;
         return pass_down_half_covers(dim, hidden) && stream_cu_count() == cu_count();
     }
     if (!ffn_pair_covers(dim, hidden)) return false;
@@ -694,6 +758,67 @@ bool prompt_pass_covers(const Config* p, const Model* m) {
     if (divUp(ku, 64) != 3 || ku - 128 <= 32 || ku * 2 < g.pw4) return false;        // the two-part K split in three k-slots, no shared half slot
     return stream_cu_count() == cu_count();
 }
+bool prompt_pass_covers(const Config* p, const Model* m) {
+    if (!p || !m || !m->rope_table || !m->sync) return false;
+    if (p->dim == 5120) return pass_13b_covers(p, m);
+    if (m->kv_format != Q4_KV_FP16) {       // the FP8 cache: q4_set_pass_kv8, and a head the append and attention launches of prompt_pass_kv8.hip take (128, checked below)
+        if (m->kv_format != Q4_KV_FP8 || !m->pass_kv8 || !m->k_exp || !m->v_exp || !kv8_head_size_ok(p->n_heads > 0 ? p->dim / p->n_heads : 0)) return false;
+    }
+    return pass_shape_4096_covers(p, m->pass_gqa);      // (grouped-query: q4_set_pass_gqa)
+}
+
+constexpr int TB = PP_WAVES * 64;
+constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
+constexpr size_t SMEM_DOWN_HALF = prompt_gemv_lds<4, 2, false, PP_DOWN_HALF_G>();
+static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024 && (SMEM_DOWN_HALF <= 64 * 1024 || PP_DOWN_HALF_G > 1), "no LDS opt-in in the shipped form");
+constexpr size_t SMEM_NORM13 = prompt_gemv_lds<3, 1, true, PP13_G>(), SMEM_QKV13 = prompt_gemv_lds<3, 1, true, PP13_QKV_G>(), SMEM_O13 = prompt_gemv_lds<3, 1, false, 4>();
+static_assert(SMEM_NORM13 <= 64 * 1024 && SMEM_O13 <= 64 * 1024, "no LDS opt-in in the shipped form");
+
+// The three launches of a layer behind attention -- o-proj + residual, rmsnorm + gate/up + SiLU, down projection + residual -- over rows 0 .. n - 1 of a
+// scratch. A row's values depend on that row alone, so the prompt and verify passes and the batch pass (q4_batch.h: rows of different sequences) share them.
+static int pass_layer_tail(const Config* p, const PerLayerWeight* L, const PassScratch* b, int n) {
+    const int dim = p->dim, hidden = p->hidden_dim;
+    const bool down_half = !ffn_pair_covers(dim, hidden);    // (prompt_pass_covers: then the shared-half-slot form)
+    const bool k13 = dim == 5120;                            // (prompt_pass_covers: q4_set_pass_13b's shape, K = 5120 in two k-slots and the shared half slot)
+    if (SMEM_DOWN_HALF > 64 * 1024)     // (an experiment build only)
+        Q4_TRY(lds_opt_in((const void*)prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>, SMEM_DOWN_HALF));
+    {   // o-proj + residual (K = 5120: a column pair per wave, the shared half slot)
+        GemvArgs a = {};
+        fill_geom(a, dim, dim);
+        fill_mat(a.m[0], &L->wq_o);
+        a.out[0] = b->x; a.x = b->xb; a.accum = 1;
+        if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 1, 4, PP13_O_WAVES, false, true>), dim3(dim / (PP13_O_WAVES * 2)), dim3(PP13_O_WAVES * 64), SMEM_O13, a, n);
+        else Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 2, 1, false, 1, 4, PP_WAVES>), dim3(dim / PP_WAVES), dim3(TB), SMEM_O, a, n);
+        Q4_LAUNCH_CHECK();
+    }
+    {   // rmsnorm + gate/up + SiLU (K = 5120: a column pair of gate and of up per wave, the strips' pair units)
+        GemvArgs a = {};
+        fill_geom(a, dim, hidden);
+        fill_mat(a.m[0], &L->wq_gate); fill_mat(a.m[1], &L->wq_up);
+        a.out[0] = b->hb; a.x = b->x; a.rms_w = L->rms_ffn_weight;
+        if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 3, 2, true, 1, PP13_G, PP13_FFN_WAVES, false, true>), dim3(hidden / (PP13_FFN_WAVES * 2)), dim3(PP13_FFN_WAVES * 64), SMEM_NORM13, a, n);
+        else Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
+        Q4_LAUNCH_CHECK();
+    }
+    if (down_half) {   // down projection + residual, the shared-half-slot form: two k-parts of three slots and a shared one, a column pair per wave
+        GemvArgs a = {};
+        fill_geom(a, hidden, dim);
+        fill_mat(a.m[0], &L->wq_down);
+        a.ku = (divUp(a.pw4, 2) + 3) & ~3;
+        a.out[0] = b->x; a.x = b->hb; a.accum = 1;
+        Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN_HALF, a, n);
+        Q4_LAUNCH_CHECK();
+    } else {   // down projection + residual: two k-parts, part 0 then part 1
+        GemvArgs a = {};
+        fill_geom(a, hidden, dim);
+        fill_mat(a.m[0], &L->wq_down);
+        a.ku = (divUp(a.pw4, 2) + 3) & ~3;
+        a.out[0] = b->x; a.x = b->hb; a.accum = 1;
+        Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 2, 2, PP_WAVES>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN, a, n);
+        Q4_LAUNCH_CHECK();
+    }
+    return Q4_OK;
+}
 
 // The layer loop of a pass, shared by the prompt pass below and the verify pass (spec_verify.hip): rows 0 .. n - 1 of the model's scratch rows hold the
 // positions' residual streams going in (and pos[t] their positions), and their final residual streams coming out. pos0: the position of row 0 as the
@@ -701,9 +826,8 @@ bool prompt_pass_covers(const Config* p, const Model* m) {
 // read the positions from pos[].
 int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w, Model* m, int pos0, int n) {
     if (!prompt_pass_covers(p, m) || n < 2 || n > PROMPT_PASS_MAX) return Q4_ERR_ARG;
-    const int dim = p->dim, hidden = p->hidden_dim, head_size = dim / p->n_heads;
+    const int dim = p->dim, head_size = dim / p->n_heads;
     const int kv_mul = p->n_heads / p->n_kv_heads, kv_dim = dim / kv_mul;
-    const bool down_half = !ffn_pair_covers(dim, hidden);    // (prompt_pass_covers: then the shared-half-slot form)
     const bool k13 = dim == 5120;                            // (prompt_pass_covers: q4_set_pass_13b's shape, K = 5120 in two k-slots and the shared half slot)
     Q4_TRY(prompt_pass_rows(m, p));
     PassScratch* const b = &m->pass;
@@ -727,14 +851,6 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
         const int most = divUp(p->seq_len, 64) > plan.nsp ? divUp(p->seq_len, 64) : plan.nsp;      // the smallest chunk's count over the whole context
         Q4_TRY(pass_records_of(b, (size_t)PROMPT_PASS_MAX * p->n_heads * most * rec));
     }
-    constexpr int TB = PP_WAVES * 64;
-    constexpr size_t SMEM_NORM = prompt_gemv_lds<2, 1, true, 4>(), SMEM_O = prompt_gemv_lds<2, 1, false, 4>(), SMEM_DOWN = prompt_gemv_lds<3, 2, false, 2>();
-    constexpr size_t SMEM_DOWN_HALF = prompt_gemv_lds<4, 2, false, PP_DOWN_HALF_G>();
-    static_assert(SMEM_NORM <= 64 * 1024 && SMEM_DOWN <= 64 * 1024 && (SMEM_DOWN_HALF <= 64 * 1024 || PP_DOWN_HALF_G > 1), "no LDS opt-in in the shipped form");
-    constexpr size_t SMEM_NORM13 = prompt_gemv_lds<3, 1, true, PP13_G>(), SMEM_QKV13 = prompt_gemv_lds<3, 1, true, PP13_QKV_G>(), SMEM_O13 = prompt_gemv_lds<3, 1, false, 4>();
-    static_assert(SMEM_NORM13 <= 64 * 1024 && SMEM_O13 <= 64 * 1024, "no LDS opt-in in the shipped form");
-    if (SMEM_DOWN_HALF > 64 * 1024)     // (an experiment build only)
-        Q4_TRY(lds_opt_in((const void*)prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>, SMEM_DOWN_HALF));
     const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
     const unsigned natt = (unsigned)p->n_heads * 4u;
     for (int l = 0; l < p->n_layers; l++) {
@@ -789,9 +905,10 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
         } else if (split) {   // attention in the split-context bins: one block per (head, chunk) loops over the tokens, then the step's merge per (head, token)
             const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, kv_dim, kv_mul, plan.nsp, tok_stride, alpha};
             const dim3 grid((unsigned)p->n_heads, (unsigned)plan.nsp);
-            if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a);
-            else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a);
-            else Q4_LAUNCH(prompt_split_attention_kernel<8>, grid, dim3(LA_WAVES * 64), 0, a);
+            const PassRowList none = {};
+            if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
+            else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
+            else Q4_LAUNCH(prompt_split_attention_kernel<8>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
             Q4_LAUNCH_CHECK();
             Q4_LAUNCH(prompt_merge_kernel, dim3((unsigned)p->n_heads, (unsigned)n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
                       plan.nsp, tok_stride, plan.nsp_of_bin, plan.chunk);
@@ -802,41 +919,82 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
                       (unsigned)p->n_heads, natt, dim);
             Q4_LAUNCH_CHECK();
         }
-        {   // o-proj + residual (K = 5120: a column pair per wave, the shared half slot)
+        Q4_TRY(pass_layer_tail(p, L, b, n));
+    }
+    return Q4_OK;
+}
+
+// ---- the batch pass (q4_batch.h) ----------------------------------------------------------------------------------------------
+// The shapes a batch pass takes: prompt_pass_covers' two 4096-wide shapes with the fp16 cache -- Llama-2-7B's, and the grouped-query one whatever
+// q4_set_pass_gqa says (the switch guards the token loop's passes; a batch is asked for by name). Admit what is tested.
+bool batch_pass_covers(const Config* p, const Model* m) {
+    if (!p || !m || !m->rope_table || !m->sync || m->kv_format != Q4_KV_FP16 || p->n_heads < 1) return false;
+    if (p->n_heads != p->n_kv_heads && (p->dim + 2 * (p->dim / 4)) / 4 % PP_QKV_GQA_WAVES) return false;      // (the grouped-query q/k/v grid: whole blocks)
+    return pass_shape_4096_covers(p, true) && verify_cls_covers(p->dim, p->vocab_size);
+}
+
+// The layer loop over the n rows of a batch pass: rows 0 .. n - 1 of the batch's scratch hold the rows' residual streams going in and coming out,
+// b->pos[t] (device) their positions, kv (device) their cache bases; pos_host[t]: the positions as the host knows them -- a slot advances by one per
+// pass, so the host always does -- from which each row's attention form is planned as the step at that position would take it (pass_attention_plan with
+// one position). Per layer: q/k/v in its ROWS form, at most one V-slice launch and one split + merge pair per chunk size present among the rows, then
+// pass_layer_tail. Every launch names its rows by value; nothing waits in-launch.
+int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv) {
+    if (!batch_pass_covers(p, m) || n < 1 || n > PROMPT_PASS_MAX || !b->slab || !kv) return Q4_ERR_ARG;
+    const int dim = p->dim, head_size = dim / p->n_heads;
+    const int kv_mul = p->n_heads / p->n_kv_heads, kv_dim = dim / kv_mul;
+    PassRowList vslice = {};
+    struct SplitRows { PassRowList list; int chunk, nsp; } split[3] = {{{}, 64, 0}, {{}, 128, 0}, {{}, 256, 0}};
+    for (int t = 0; t < n; t++) {
+        PassAttention plan = {};
+        if (pos_host[t] < 0 || pos_host[t] >= p->seq_len || !pass_attention_plan(p, s, pos_host[t], 1, &plan)) return Q4_ERR_ARG;
+        if (!att_is_split(plan.form)) { vslice.row[vslice.n++] = t; continue; }
+        SplitRows* f = plan.chunk == 64 ? &split[0] : plan.chunk == 128 ? &split[1] : plan.chunk == 256 ? &split[2] : nullptr;
+        if (!f || head_size != 128) return Q4_ERR_ARG;
+        f->list.nsp_of_bin[f->list.n] = plan.nsp_of_bin;
+        f->list.row[f->list.n++] = t;
+        if (plan.nsp > f->nsp) f->nsp = plan.nsp;
+    }
+    const int rec = head_size + ATT_REC_PAD;
+    int most = divUp(p->seq_len, 64);
+    for (const SplitRows& f : split) if (f.nsp > most) most = f.nsp;
+    if (split[0].list.n || split[1].list.n || split[2].list.n) Q4_TRY(pass_records_of(b, (size_t)PROMPT_PASS_MAX * p->n_heads * most * rec));
+    const float alpha = (float)(1.0 / sqrt((double)head_size));                     // llama2_q4.cu:273
+    const unsigned natt = (unsigned)p->n_heads * 4u;
+    for (int l = 0; l < p->n_layers; l++) {
+        const PerLayerWeight* L = &w->layers[l];
+        const long long loff = (long long)l * p->seq_len * kv_dim;
+        {   // rmsnorm + q/k/v + RoPE, row t rotated by its own position, its K / V row into its own sequence's cache
             GemvArgs a = {};
             fill_geom(a, dim, dim);
-            fill_mat(a.m[0], &L->wq_o);
-            a.out[0] = b->x; a.x = b->xb; a.accum = 1;
-            if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 1, 4, PP13_O_WAVES, false, true>), dim3(dim / (PP13_O_WAVES * 2)), dim3(PP13_O_WAVES * 64), SMEM_O13, a, n);
-            else Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 2, 1, false, 1, 4, PP_WAVES>), dim3(dim / PP_WAVES), dim3(TB), SMEM_O, a, n);
+            a.N_kv = kv_mul > 1 ? kv_dim : 0;
+            fill_mat(a.m[0], &L->wq_q); fill_mat(a.m[1], &L->wq_k); fill_mat(a.m[2], &L->wq_v);
+            a.out[0] = b->q; a.row_kv = kv;
+            a.x = b->x; a.rms_w = L->rms_att_weight; a.pPos = b->pos; a.loff = loff;
+            a.rope = 1; a.head_size = head_size; a.rope_theta = p->rope_theta; a.rope_table = m->rope_table;
+            if (kv_mul > 1) Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_GQA_WAVES, true, false, false, true>), dim3((dim + 2 * kv_dim) / 4 / PP_QKV_GQA_WAVES), dim3(PP_QKV_GQA_WAVES * 64), SMEM_NORM, a, n);
+            else Q4_LAUNCH((prompt_gemv_kernel<MODE_QKV, 2, 4, true, 1, 4, PP_QKV_WAVES, false, false, false, true>), dim3(3 * dim / (PP_QKV_WAVES * 4)), dim3(PP_QKV_WAVES * 64), SMEM_NORM, a, n);
             Q4_LAUNCH_CHECK();
         }
-        {   // rmsnorm + gate/up + SiLU (K = 5120: a column pair of gate and of up per wave, the strips' pair units)
-            GemvArgs a = {};
-            fill_geom(a, dim, hidden);
-            fill_mat(a.m[0], &L->wq_gate); fill_mat(a.m[1], &L->wq_up);
-            a.out[0] = b->hb; a.x = b->x; a.rms_w = L->rms_ffn_weight;
-            if (k13) Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 3, 2, true, 1, PP13_G, PP13_FFN_WAVES, false, true>), dim3(hidden / (PP13_FFN_WAVES * 2)), dim3(PP13_FFN_WAVES * 64), SMEM_NORM13, a, n);
-            else Q4_LAUNCH((prompt_gemv_kernel<MODE_FFN, 2, 3, true, 1, 4, PP_WAVES>), dim3(divUp(hidden, PP_WAVES * 3)), dim3(TB), SMEM_NORM, a, n);
+        if (vslice.n) {   // the rows below bin 512: the V-slice units, each row over its own cache
+            const AttArgs a = {b->xb, b->q, nullptr, nullptr, head_size, kv_mul, kv_dim, b->pos, alpha, 256, nullptr};
+            Q4_LAUNCH(prompt_attention_rows_kernel, dim3((unsigned)vslice.n * natt), dim3(LA16_WAVES * 64), LA16_LDS, a, (const int*)b->pos, (u32x2v*)b->sink, (unsigned)b->sink_stride,
+                      (unsigned)p->n_heads, natt, dim, vslice, kv, loff);
             Q4_LAUNCH_CHECK();
         }
-        if (down_half) {   // down projection + residual, the shared-half-slot form: two k-parts of three slots and a shared one, a column pair per wave
-            GemvArgs a = {};
-            fill_geom(a, hidden, dim);
-            fill_mat(a.m[0], &L->wq_down);
-            a.ku = (divUp(a.pw4, 2) + 3) & ~3;
-            a.out[0] = b->x; a.x = b->hb; a.accum = 1;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 4, 2, false, 2, PP_DOWN_HALF_G, PP_WAVES, false, true>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN_HALF, a, n);
+        for (const SplitRows& f : split) {   // the rows in the split-context bins, by chunk size: one block per (head, chunk, row), then the step's merge per (head, row)
+            if (!f.list.n) continue;
+            const size_t tok_stride = (size_t)p->n_heads * f.nsp * rec;
+            const PassSplitArgs a = {b->records, b->q, nullptr, nullptr, b->pos, 1, dim, kv_dim, kv_mul, f.nsp, tok_stride, alpha};
+            const dim3 grid((unsigned)p->n_heads, (unsigned)f.nsp, (unsigned)f.list.n);
+            if (f.chunk == 64) Q4_LAUNCH((prompt_split_attention_kernel<2, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
+            else if (f.chunk == 128) Q4_LAUNCH((prompt_split_attention_kernel<4, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
+            else Q4_LAUNCH((prompt_split_attention_kernel<8, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
             Q4_LAUNCH_CHECK();
-        } else {   // down projection + residual: two k-parts, part 0 then part 1
-            GemvArgs a = {};
-            fill_geom(a, hidden, dim);
-            fill_mat(a.m[0], &L->wq_down);
-            a.ku = (divUp(a.pw4, 2) + 3) & ~3;
-            a.out[0] = b->x; a.x = b->hb; a.accum = 1;
-            Q4_LAUNCH((prompt_gemv_kernel<MODE_PLAIN, 3, 2, false, 2, 2, PP_WAVES>), dim3(dim / (PP_WAVES / 2 * 2)), dim3(TB), SMEM_DOWN, a, n);
+            Q4_LAUNCH(prompt_merge_rows_kernel, dim3((unsigned)p->n_heads, (unsigned)f.list.n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
+                      f.nsp, tok_stride, f.list, f.chunk);
             Q4_LAUNCH_CHECK();
         }
+        Q4_TRY(pass_layer_tail(p, L, b, n));
     }
     return Q4_OK;
 }

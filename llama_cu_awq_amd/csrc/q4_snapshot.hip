@@ -18,6 +18,7 @@
 #include <new>
 #include <vector>
 #include "q4_model.h"
+#include "q4_batch.h"
 using namespace q4;
 
 using SnapInfo = struct q4_snapshot_info;     // (the C ABI gives the record and the function that fills it one name: the tag needs its keyword)
@@ -102,6 +103,10 @@ int check_blob(const void* host, size_t bytes, SnapInfo* out, Layout* lay) {
 }
 
 }  // namespace
+
+// what q4_batch_restore (q4_batch.hip) reads of a snapshot
+const void* q4::snapshot_rows(const q4_snapshot* s) { return s->dev; }
+const int* q4::snapshot_token_ids(const q4_snapshot* s) { return s->tokens.data(); }
 
 extern "C" {
 
