@@ -871,15 +871,32 @@ int q4_batch_open(q4_batch* b, int slot, const int* prompt, int n_prompt, unsign
  * snapshot's tokens. */
 int q4_batch_restore(q4_batch* b, int slot, const q4_snapshot* s, const int* prompt, int n_prompt, unsigned long long seed);
 int q4_batch_close(q4_batch* b, int slot);              /* the slot's rows and logits stay readable until it is opened again; Q4_ERR_ARG: not open */
-/* One pass over the weights: every open slot advances by one position. tokens_out [Q4_BATCH_MAX_SLOTS]: the slot's generated token, or -1 for a closed
- * slot, a slot outside the batch and a slot still inside its prompt. sampler: temperature 0 greedy (the step's argmax and tie-breaking), else the
+/* Several prompt positions of a slot per pass (chunked prefill), opt-in. max_rows_per_slot in 1 .. Q4_BATCH_MAX_SLOTS, else Q4_ERR_ARG and nothing
+ * changes; the default 1 is one row per slot, launch for launch what a batch without this call runs. May be changed between passes. Above 1 the rows a pass
+ * has spare -- Q4_BATCH_MAX_SLOTS minus the open slots -- go to slots inside their prompts (q4_batch_plan_rows); everything a slot produces stays byte
+ * for byte the run alone's. q4_batch_get_prefill: the value in force (negative: -Q4_ERR_ARG). */
+int q4_batch_set_prefill(q4_batch* b, int max_rows_per_slot);
+int q4_batch_get_prefill(const q4_batch* b);
+/* The schedule of one pass, a pure host function (no device call; q4_batch_step and q4_batch_generate plan every pass with it). open / pos / n_prompt
+ * [n_slots]: per slot whether it is open, its position, its prompt length. rows_per_slot [n_slots] receives the rows each slot takes: 1 for every open
+ * slot; then, in slot order, the spare rows to open slots with pos < n_prompt - 1, each up to min(max_rows_per_slot, n_prompt - pos) rows in all while
+ * spare rows last. A slot's rows are the consecutive positions pos .. pos + rows - 1, adjacent and ascending in the pass, slots in slot order; the last may
+ * be the generating row n_prompt - 1. Returns the pass's row count (0 .. Q4_BATCH_MAX_SLOTS), or -Q4_ERR_ARG: a null pointer, n_slots or
+ * max_rows_per_slot outside 1 .. Q4_BATCH_MAX_SLOTS. */
+int q4_batch_plan_rows(const int* open, const int* pos, const int* n_prompt, int n_slots, int max_rows_per_slot, int* rows_per_slot);
+/* One pass over the weights: every open slot advances by one position -- a slot inside its prompt by up to q4_batch_set_prefill's rows, when the pass
+ * has rows to spare. A slot produces at most one token per pass: only its last row can be a generating row. tokens_out [Q4_BATCH_MAX_SLOTS]: the slot's
+ * generated token, or -1 for a closed slot, a slot outside the batch and a slot still inside its prompt. A row standing where the step's attention has no
+ * row form (without graphs: positions 256 .. 510) refuses the whole pass with Q4_ERR_UNSUPPORTED_SIZE, nothing moved. sampler: temperature 0 greedy (the step's argmax and tie-breaking), else the
  * temperature / top-p sampler's row form with each slot's own coin; its rng_state is not used. Synchronises. Q4_ERR_ARG: a null pointer, or an open slot
  * that stands at seq_len (close it); nothing ran. No open slot: Q4_OK, nothing ran. */
 int q4_batch_step(q4_batch* b, Sampler* sampler, int* tokens_out);
 /* Up to `steps` passes queued back to back -- tokens stay on the device between passes -- and one synchronise at the end; stops early in front of a pass
- * in which an open slot would stand at seq_len. out [steps][Q4_BATCH_MAX_SLOTS]: row i is q4_batch_step's tokens_out of pass i; *n_out: passes run. */
+ * in which an open slot would stand at seq_len. out [steps][Q4_BATCH_MAX_SLOTS]: row i is q4_batch_step's tokens_out of pass i (at most one token per
+ * slot and pass, however many prompt positions the slot advanced by); *n_out: passes run. */
 int q4_batch_generate(q4_batch* b, Sampler* sampler, int steps, int* out, int* n_out);
-/* What the tests read; each synchronises. q4_batch_pos: the slot's position on the device (negative: -Q4_ERR_ARG); logits: the vocab halves of the slot's
+/* What the tests read; each synchronises. q4_batch_pos: the slot's position on the device (negative: -Q4_ERR_ARG) -- behind a pass it stands past every
+ * row the slot took, one or several positions on; logits: the vocab halves of the slot's
  * last position (fp16 probabilities behind a sampled pass, as a sampled step leaves them); a K / V row of the slot's cache; the device addresses of the
  * slot's K and V caches, each [n_layers][seq_len][kv_dim] halves. */
 int q4_batch_pos(const q4_batch* b, int slot);

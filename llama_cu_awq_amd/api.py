@@ -213,7 +213,7 @@ SYMBOLS = [
     "q4_set_pass_stages", "q4_get_pass_stages", "q4_parse_pass_stages", "q4_guide_mask_rows", "q4_dry_penalty_rows", "q4_process_logits_rows",
     "q4_guide_forced_run", "q4_spec_stats_forced",
     "q4_batch_covers", "q4_batch_new", "q4_batch_delete", "q4_batch_open", "q4_batch_restore", "q4_batch_close", "q4_batch_step", "q4_batch_generate",
-    "q4_batch_pos", "q4_batch_get_logits", "q4_batch_get_kv_row", "q4_batch_cache",
+    "q4_batch_pos", "q4_batch_get_logits", "q4_batch_get_kv_row", "q4_batch_cache", "q4_batch_set_prefill", "q4_batch_get_prefill", "q4_batch_plan_rows",
 ]
 
 _lib = None
@@ -445,6 +445,13 @@ def lib():
         L.q4_batch_get_logits.argtypes = [vp, i, vp]
         L.q4_batch_get_kv_row.argtypes = [vp, i, i, i, vp, vp]
         L.q4_batch_cache.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "q4_batch_set_prefill"):         # (likewise)
+        L.q4_batch_set_prefill.argtypes = [vp, i]
+        L.q4_batch_get_prefill.argtypes = [vp]
+        L.q4_batch_plan_rows.argtypes = [vp, vp, vp, i, i, vp]
+        if _use_prof:
+            L.q4_set_batch_run_form.argtypes = [i]
+            L.q4_set_batch_run_form.restype = None
     if hasattr(L, "q4_shift_context"):             # (older builds under tools/ab.py do not have it)
         L.q4_shift_context.argtypes = [vp, i, i, i, i]
         L.q4_set_context_shift.argtypes = [vp, i, i]
@@ -1395,12 +1402,71 @@ class Batch:
     (csrc/q4_batch.h). A slot's tokens, K / V rows and logits are byte for byte those of the same checkpoint running that sequence alone with the slot's
     seed. The model's sampler decides greedy or temperature / top-p; its own sequence is not touched. delete() the batch before the Transformer closes."""
 
-    def __init__(self, transformer, slots):
+    def __init__(self, transformer, slots, prefill_rows=1):
         self.t = transformer
         self.slots = int(slots)
         h = C.c_void_p()
         check(lib().q4_batch_new(C.byref(h), transformer.h, self.slots))
         self.h = h.value
+        if int(prefill_rows) != 1:
+            self.set_prefill(prefill_rows)
+
+    def set_prefill(self, n):
+        """q4_batch_set_prefill: a slot inside its prompt takes up to `n` rows (consecutive positions) of a pass that has rows to spare; 1: one per slot"""
+        check(lib().q4_batch_set_prefill(self.h, int(n)))
+
+    def prefill(self):
+        return lib().q4_batch_get_prefill(self.h)
+
+    @staticmethod
+    def plan_rows(open_, pos, n_prompt, max_rows_per_slot):
+        """q4_batch_plan_rows, the schedule of one pass (host arithmetic, no device): (rows in the pass, int32 rows per slot)"""
+        o, p, n = (np.ascontiguousarray(x, dtype=np.int32) for x in (open_, pos, n_prompt))
+        rows = np.zeros(len(o), dtype=np.int32)
+        total = lib().q4_batch_plan_rows(o.ctypes.data, p.ctypes.data, n.ctypes.data, len(o), int(max_rows_per_slot), rows.ctypes.data)
+        if total < 0:
+            check(-total)
+        return total, rows
+
+    def run(self, requests, max_new_tokens, eos=None, seeds=None):
+        """A host loop over step(): `requests` (token lists) are opened in free slots in order as slots fall free, each generates until it emits `eos`
+        (kept as its last token) or has max_new_tokens, then its slot is closed and the next request takes it. Returns each request's generated tokens in
+        request order. ValueError, nothing opened: a seed list of another length, max_new_tokens below 1, an empty request or one that does not fit the
+        context with its new tokens. Every slot of the batch must be closed going in (an open one: Q4Error from the first open that meets it). However
+        the loop ends -- also on a pass that raises, e.g. a row where no row form exists -- the slots this call opened are closed again."""
+        requests = [[int(x) for x in r] for r in requests]
+        seeds = [1] * len(requests) if seeds is None else [int(s) for s in seeds]
+        new = int(max_new_tokens)
+        if len(seeds) != len(requests):
+            raise ValueError("Batch.run: %d seeds for %d requests" % (len(seeds), len(requests)))
+        if new < 1:
+            raise ValueError("Batch.run: max_new_tokens must be at least 1")
+        for r in requests:
+            if not r or len(r) + new > self.t.config.seq_len + 1:
+                raise ValueError("Batch.run: a request of %d tokens and %d new ones does not fit the context" % (len(r), new))
+        out = [[] for _ in requests]
+        owner = [None] * self.slots
+        queued = 0
+        try:
+            while queued < len(requests) or any(o is not None for o in owner):
+                for slot in range(self.slots):
+                    if owner[slot] is None and queued < len(requests):
+                        self.open(slot, requests[queued], seed=seeds[queued])
+                        owner[slot] = queued
+                        queued += 1
+                toks = self.step()
+                for slot, req in enumerate(owner):
+                    if req is None or toks[slot] < 0:
+                        continue
+                    out[req].append(int(toks[slot]))
+                    if len(out[req]) >= new or (eos is not None and int(toks[slot]) == int(eos)):
+                        self.close(slot)
+                        owner[slot] = None
+        finally:
+            for slot, req in enumerate(owner):
+                if req is not None:
+                    self.close(slot)
+        return out
 
     @staticmethod
     def covers(transformer):

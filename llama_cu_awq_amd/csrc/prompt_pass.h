@@ -64,8 +64,11 @@ void pass_scratch_release(PassScratch* b);
 // The rows one launch of a batch pass runs, by value in its arguments: n rows of the pass, row[i] their indices; nsp_of_bin[i] (the merge launch): the chunk
 // count the step merges at row i's position, 0: those up to the position itself (PassAttention::nsp_of_bin)
 struct PassRowList { int n; int row[PROMPT_PASS_MAX]; int nsp_of_bin[PROMPT_PASS_MAX]; };
+// ... and, for the split launch's run form, beside a PassRowList of the runs' first rows: len[i] adjacent rows of one sequence from row[i] on
+struct PassRunList { int len[PROMPT_PASS_MAX]; };
 // The batch pass's side of this file (q4_batch.h): its admission by shape, and the layer loop over n rows of different sequences (their comments there)
 bool batch_pass_covers(const Config* p, const Model* m);
-int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv);
+int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv,
+                      const int* seq);
 
 }  // namespace q4

@@ -464,18 +464,26 @@ struct PassSplitArgs {
 // ROWS, the row form for a batch pass (q4_batch.h): one block per (head, chunk, listed row) runs this body for ONE token -- row t = list.row[z] with its
 // own q, position, record area and cache (row_kv[t] / row_kv[PROMPT_PASS_MAX + t] plus the layer's offset) -- so a row's records are the ones a one-token pass of
 // that sequence writes. a.key_cache / a.value_cache are then not read; a.nsp: the chunks this launch lays the records out by, the most of its rows' counts.
-// A template flag: without it the three trailing arguments are not read and the kernel is the code it was.
-template <int U, bool ROWS = false>
-__global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(const PassSplitArgs a0, const PassRowList list, q4_half* const* row_kv, const long long loff) {
+// A template value: with SPLIT_PASS the three trailing arguments are not read and the kernel is the code it was.
+// SPLIT_RUNS, the run form for a batch pass whose slots carry several rows (q4_batch_set_prefill): one block per (head, chunk, listed run). A run is
+// runs.len[z] adjacent rows of ONE sequence at consecutive positions, the first of them row t = list.row[z] (the last argument, which the other two
+// values do not read -- it trails so that theirs sit where they sat): the block takes that row's q, position and
+// record area as token 0's and the sequence's cache, and runs the token loop below over the run -- the chunk's K / V rows requested once for all of its
+// rows, size_last from the run's last row, token i's records into row t + i's own area, a masked lane's V row the token's own (vown). This is the body the
+// prompt pass holds to the step's bytes; a run of one row is the row form's block.
+enum { SPLIT_PASS = 0, SPLIT_ROWS = 1, SPLIT_RUNS = 2 };
+template <int U, int ROWS = SPLIT_PASS>
+__global__ void __launch_bounds__(LA_WAVES * 64) prompt_split_attention_kernel(const PassSplitArgs a0, const PassRowList list, q4_half* const* row_kv, const long long loff,
+                                                                               const PassRunList runs) {
     PassSplitArgs a = a0;
-    if constexpr (ROWS) {
+    if constexpr (ROWS != SPLIT_PASS) {
         const int t = list.row[blockIdx.z];
         a.records = a0.records + (size_t)t * a0.tok_stride;
         a.q = a0.q + (size_t)t * a0.dim;
         a.key_cache = row_kv[t] + loff;
         a.value_cache = row_kv[PROMPT_PASS_MAX + t] + loff;
         a.pos = a0.pos + t;
-        a.ntok = 1;
+        a.ntok = ROWS == SPLIT_RUNS ? runs.len[blockIdx.z] : 1;
     }
     constexpr int LPR = 16, NW = LA_WAVES, R = 64 / LPR, stride = NW * R, CHUNK = stride * U, HS = LPR * 8;
     __shared__ __attribute__((aligned(16))) float lds[32 + NW * HS];
@@ -906,9 +914,9 @@ int prompt_pass_layers(const Config* p, RunState* s, const TransformerWeights* w
             const PassSplitArgs a = {b->records, b->q, s->key_cache + loff, s->value_cache + loff, b->pos, n, dim, kv_dim, kv_mul, plan.nsp, tok_stride, alpha};
             const dim3 grid((unsigned)p->n_heads, (unsigned)plan.nsp);
             const PassRowList none = {};
-            if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
-            else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
-            else Q4_LAUNCH(prompt_split_attention_kernel<8>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll);
+            if (plan.chunk == 64) Q4_LAUNCH(prompt_split_attention_kernel<2>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll, PassRunList{});
+            else if (plan.chunk == 128) Q4_LAUNCH(prompt_split_attention_kernel<4>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll, PassRunList{});
+            else Q4_LAUNCH(prompt_split_attention_kernel<8>, grid, dim3(LA_WAVES * 64), 0, a, none, (q4_half* const*)nullptr, 0ll, PassRunList{});
             Q4_LAUNCH_CHECK();
             Q4_LAUNCH(prompt_merge_kernel, dim3((unsigned)p->n_heads, (unsigned)n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
                       plan.nsp, tok_stride, plan.nsp_of_bin, plan.chunk);
@@ -934,22 +942,42 @@ bool batch_pass_covers(const Config* p, const Model* m) {
 }
 
 // The layer loop over the n rows of a batch pass: rows 0 .. n - 1 of the batch's scratch hold the rows' residual streams going in and coming out,
-// b->pos[t] (device) their positions, kv (device) their cache bases; pos_host[t]: the positions as the host knows them -- a slot advances by one per
-// pass, so the host always does -- from which each row's attention form is planned as the step at that position would take it (pass_attention_plan with
+// b->pos[t] (device) their positions, kv (device) their cache bases; pos_host[t]: the positions as the host knows them -- a slot advances by its row
+// count per pass (q4_batch_plan_rows), so the host always does -- from which each row's attention form is planned as the step at that position would take it (pass_attention_plan with
 // one position). Per layer: q/k/v in its ROWS form, at most one V-slice launch and one split + merge pair per chunk size present among the rows, then
 // pass_layer_tail. Every launch names its rows by value; nothing waits in-launch.
-int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv) {
+// seq (q4_batch_set_prefill: a slot may carry several rows): seq[t] names row t's sequence, the rows of one sequence adjacent and at consecutive ascending
+// positions; nullptr: every row another sequence. Adjacent rows of one sequence inside one chunk-size list form a run; a list with a run of two or more
+// rows takes the split launch's run form (one block per (head, chunk, run): the chunk's K / V rows loaded once per run), any other list the row form.
+#ifdef Q4_PROFILING            // the profiling build only: q4_set_batch_run_form(0) runs every list in the row form (tools/bench_batch_prefill.py)
+static int g_batch_run_form = 1;
+static bool batch_run_form() { return g_batch_run_form != 0; }
+#else
+static constexpr bool batch_run_form() { return true; }
+#endif
+int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeights* w, Model* m, PassScratch* b, const int* pos_host, int n, q4_half* const* kv,
+                      const int* seq) {
     if (!batch_pass_covers(p, m) || n < 1 || n > PROMPT_PASS_MAX || !b->slab || !kv) return Q4_ERR_ARG;
     const int dim = p->dim, head_size = dim / p->n_heads;
     const int kv_mul = p->n_heads / p->n_kv_heads, kv_dim = dim / kv_mul;
     PassRowList vslice = {};
-    struct SplitRows { PassRowList list; int chunk, nsp; } split[3] = {{{}, 64, 0}, {{}, 128, 0}, {{}, 256, 0}};
+    // list: the rows of this chunk size (the row form and the merge); heads / runs: the first row and the length of each run among them
+    struct SplitRows { PassRowList list; int chunk, nsp; PassRowList heads; PassRunList runs; bool run_form; } split[3] = {};
+    split[0].chunk = 64; split[1].chunk = 128; split[2].chunk = 256;
     for (int t = 0; t < n; t++) {
         PassAttention plan = {};
         if (pos_host[t] < 0 || pos_host[t] >= p->seq_len || !pass_attention_plan(p, s, pos_host[t], 1, &plan)) return Q4_ERR_ARG;
+        if (seq && t > 0 && seq[t] == seq[t - 1] && pos_host[t] != pos_host[t - 1] + 1) return Q4_ERR_ARG;
         if (!att_is_split(plan.form)) { vslice.row[vslice.n++] = t; continue; }
         SplitRows* f = plan.chunk == 64 ? &split[0] : plan.chunk == 128 ? &split[1] : plan.chunk == 256 ? &split[2] : nullptr;
         if (!f || head_size != 128) return Q4_ERR_ARG;
+        if (seq && f->list.n && f->list.row[f->list.n - 1] == t - 1 && seq[t] == seq[t - 1]) {
+            f->runs.len[f->heads.n - 1]++;
+            f->run_form = batch_run_form();
+        } else {
+            f->runs.len[f->heads.n] = 1;
+            f->heads.row[f->heads.n++] = t;
+        }
         f->list.nsp_of_bin[f->list.n] = plan.nsp_of_bin;
         f->list.row[f->list.n++] = t;
         if (plan.nsp > f->nsp) f->nsp = plan.nsp;
@@ -985,10 +1013,17 @@ int batch_pass_layers(const Config* p, const RunState* s, const TransformerWeigh
             if (!f.list.n) continue;
             const size_t tok_stride = (size_t)p->n_heads * f.nsp * rec;
             const PassSplitArgs a = {b->records, b->q, nullptr, nullptr, b->pos, 1, dim, kv_dim, kv_mul, f.nsp, tok_stride, alpha};
-            const dim3 grid((unsigned)p->n_heads, (unsigned)f.nsp, (unsigned)f.list.n);
-            if (f.chunk == 64) Q4_LAUNCH((prompt_split_attention_kernel<2, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
-            else if (f.chunk == 128) Q4_LAUNCH((prompt_split_attention_kernel<4, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
-            else Q4_LAUNCH((prompt_split_attention_kernel<8, true>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff);
+            if (f.run_form) {   // ... one block per (head, chunk, run) where a sequence has several rows here; the merge stays per row, each with its own chunk count
+                const dim3 grid((unsigned)p->n_heads, (unsigned)f.nsp, (unsigned)f.heads.n);
+                if (f.chunk == 64) Q4_LAUNCH((prompt_split_attention_kernel<2, SPLIT_RUNS>), grid, dim3(LA_WAVES * 64), 0, a, f.heads, kv, loff, f.runs);
+                else if (f.chunk == 128) Q4_LAUNCH((prompt_split_attention_kernel<4, SPLIT_RUNS>), grid, dim3(LA_WAVES * 64), 0, a, f.heads, kv, loff, f.runs);
+                else Q4_LAUNCH((prompt_split_attention_kernel<8, SPLIT_RUNS>), grid, dim3(LA_WAVES * 64), 0, a, f.heads, kv, loff, f.runs);
+            } else {
+                const dim3 grid((unsigned)p->n_heads, (unsigned)f.nsp, (unsigned)f.list.n);
+                if (f.chunk == 64) Q4_LAUNCH((prompt_split_attention_kernel<2, SPLIT_ROWS>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff, PassRunList{});
+                else if (f.chunk == 128) Q4_LAUNCH((prompt_split_attention_kernel<4, SPLIT_ROWS>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff, PassRunList{});
+                else Q4_LAUNCH((prompt_split_attention_kernel<8, SPLIT_ROWS>), grid, dim3(LA_WAVES * 64), 0, a, f.list, kv, loff, PassRunList{});
+            }
             Q4_LAUNCH_CHECK();
             Q4_LAUNCH(prompt_merge_rows_kernel, dim3((unsigned)p->n_heads, (unsigned)f.list.n), dim3(128), 0, b->xb, (const float*)b->records, (const int*)b->pos, dim, head_size,
                       f.nsp, tok_stride, f.list, f.chunk);
@@ -1026,3 +1061,8 @@ int run_prompt_pass(const Config* p, RunState* s, const TransformerWeights* w, M
 }
 
 }  // namespace q4
+
+#ifdef Q4_PROFILING
+// a measurement knob of the profiling build (q4_kernels.hip lists the others): 0 runs every split-context list of a batch pass in the row form
+extern "C" void q4_set_batch_run_form(int on) { q4::g_batch_run_form = on; }
+#endif

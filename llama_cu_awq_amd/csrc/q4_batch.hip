@@ -1,10 +1,13 @@
 // q4_batch.hip -- batched decoding (q4_batch.h): the batch object, its scheduler and its three small launches. A pass is
-//   1. batch_embed_kernel: row r <- the embedding of slot map.slot[r]'s pending token (ring[slot][pos]), the rows' positions and cache bases for the layers;
-//   2. batch_pass_layers (prompt_pass.hip): the pass layer loop in its row forms;
-//   3. the verify pass's classifier over the n rows (spec_verify.hip), under a sampler the row form of its two launches (q4_sampling.hip);
-//   4. batch_pick_kernel: per row the step's argmax (or the sampler's token), the slot's logits row, its next ring entry and its position.
+//   1. batch_embed_kernel: row r <- the embedding of ring[slot][pos + off] for (slot, off) = (map.slot[r], map.off[r]), the rows' positions and cache bases for the layers;
+//   2. batch_pass_layers (prompt_pass.hip): the pass layer loop in its row forms (split-context attention of a slot's several rows: the run form);
+//   3. the verify pass's classifier (spec_verify.hip) over each slot's LAST row -- gathered first (batch_gather_kernel) when a slot carries several --,
+//      under a sampler the row form of its two launches (q4_sampling.hip);
+//   4. batch_pick_kernel: per slot the step's argmax (or the sampler's token), the slot's logits row, its next ring entry and its position.
 // Every dependency is a launch boundary on the q4 stream: no launch waits, polls or uses an atomic, and a slot's words have one writer per launch.
-// The host never reads a position back to plan a pass: a slot advances by exactly one per pass, so its position -- and with it each row's attention
+// Which slot takes how many rows is q4_batch_plan_rows' schedule: one per open slot and, with q4_batch_set_prefill above 1, the spare rows to slots inside
+// their prompts as consecutive positions. A row at position p + 1 attends over the K / V row its slot's row at p wrote in the same pass's q/k/v launch.
+// The host never reads a position back to plan a pass: a slot advances by its planned row count, so its position -- and with it each row's attention
 // form -- is known on the host; the kernels take the positions from the device words all the same. Not in the reference (one sequence, one step per token).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -47,6 +50,8 @@ struct q4_batch {
     // launches are queued: a pass that fails half-way with Q4_ERR_HIP leaves the two apart -- the batch is then dead: delete it.
     bool open[BATCH_MAX_SLOTS] = {};
     int pos[BATCH_MAX_SLOTS] = {};
+    int n_prompt[BATCH_MAX_SLOTS] = {};
+    int prefill = 1;                     // q4_batch_set_prefill: the most rows one slot takes in a pass
     unsigned long long rng[BATCH_MAX_SLOTS] = {};
 };
 
@@ -57,22 +62,24 @@ __global__ void batch_embed_kernel(q4_half* xs, const q4_half* table, int dim, c
                                    q4_half* k, q4_half* v, size_t cache_halves, int* pos_rows) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
     const int slot = map.slot[r];
-    const int pos = w->pos[slot];
+    const int pos = w->pos[slot] + map.off[r];
     if (u == 0) {
         pos_rows[r] = pos;
         w->kv[r] = k + (size_t)slot * cache_halves;
         w->kv[BATCH_MAX_SLOTS + r] = v + (size_t)slot * cache_halves;
-        w->coin[r] = map.coin[r];
+        if (r < map.m) w->coin[r] = map.coin[r];            // (by slot of the pass, for the sampler's rows: block r is its only writer)
     }
     if (u >= (dim >> 3)) return;
     const int token = ring[(size_t)slot * ring_stride + pos];
     reinterpret_cast<u32x4*>(xs + (size_t)r * dim)[u] = reinterpret_cast<const u32x4*>(table + (size_t)token * dim)[u];
 }
 
-// One block per row. The row's token: argmax_kernel's rule (q4_kernels.hip; verify_accept_kernel restates it the same way) -- 16-byte loads, the first
+// One block per slot of the pass, on the classifier's row r of that slot's last row (map.last[r]; the slot's earlier rows of the pass are prompt rows
+// whose tokens a prompt step discards: nobody computes them). The row's token: argmax_kernel's rule (q4_kernels.hip; verify_accept_kernel restates it the same way) -- 16-byte loads, the first
 // maximum inside a thread, value then lower index across threads, 0 for a row without a finite or +inf entry -- or, GIVEN, what the row form of the sampler
 // left in win[r] (the row then holds fp16 probabilities, which is what a sampled step leaves in RunState::logits). Then what the step leaves for this
-// sequence: the logits row, ring[pos + 1] unless that entry is still a prompt token (the computed token is discarded, as a prompt step's), the position.
+// sequence: the logits row, ring[pos + cnt] unless that entry is still a prompt token (the computed token is discarded, as a prompt step's), the position
+// advanced by the slot's cnt rows.
 // log: where this pass's tokens_out go ([BATCH_MAX_SLOTS] by slot; the host has put -1 into the others).
 template <bool GIVEN>
 __global__ void __launch_bounds__(1024) batch_pick_kernel(const q4_half* rows, const int size, const BatchRowMap map, BatchWords* w, int* ring, int ring_stride,
@@ -80,7 +87,7 @@ __global__ void __launch_bounds__(1024) batch_pick_kernel(const q4_half* rows, c
     __shared__ float sval[16];
     __shared__ int sidx[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x;
-    const int slot = map.slot[r];
+    const int slot = map.slot[map.last[r]];
     const int n8 = size >> 3;                                // (the vocabulary is a multiple of 8: verify_cls_covers)
     const q4_half* row = rows + (size_t)r * size;
     q4_half* keep = logits + (size_t)slot * size;
@@ -118,12 +125,19 @@ __global__ void __launch_bounds__(1024) batch_pick_kernel(const q4_half* rows, c
                 if (sval[i] > max_val || (sval[i] == max_val && sidx[i] < max_pos)) { max_val = sval[i]; max_pos = sidx[i]; }
             token = max_pos == 0x7fffffff ? 0 : max_pos;     // all NaN / -inf
         }
-        const int pos = w->pos[slot];
-        const bool gen = pos + 1 >= w->n_prompt[slot];
-        if (gen) ring[(size_t)slot * ring_stride + pos + 1] = token;
+        const int next = w->pos[slot] + map.cnt[r];          // the slot's rows of this pass were positions pos .. next - 1, this one the last
+        const bool gen = next >= w->n_prompt[slot];
+        if (gen) ring[(size_t)slot * ring_stride + next] = token;
         log[slot] = gen ? token : -1;
-        w->pos[slot] = pos + 1;
+        w->pos[slot] = next;
     }
+}
+
+// A pass in which a slot carries several rows: the residual streams of the slots' last rows, gathered into map.m contiguous rows for the classifier
+__global__ void batch_gather_kernel(q4_half* dst, const q4_half* xs, int dim, const BatchRowMap map) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    if (u >= (dim >> 3)) return;
+    reinterpret_cast<u32x4*>(dst + (size_t)j * dim)[u] = reinterpret_cast<const u32x4*>(xs + (size_t)map.last[j] * dim)[u];
 }
 
 // a slot's words when it opens; -1 into a pass's tokens_out
@@ -159,14 +173,23 @@ int queue_pass(q4_batch* b, Model* m, Sampler* sampler, int* log) {
     const bool sampled = sampler->temperature != 0.0f;
     if (sampled) Q4_TRY(sample_rows_prepare(sampler));      // (scratch on first use and the LDS opt-in: in front of the pass's first launch)
     BatchRowMap map = {};
-    int pos_rows[BATCH_MAX_SLOTS];
-    unsigned long long rng[BATCH_MAX_SLOTS];                 // the coin streams behind this pass: the slots' once the pass is queued
+    int pos_rows[BATCH_MAX_SLOTS], seq[BATCH_MAX_SLOTS], count[BATCH_MAX_SLOTS], open[BATCH_MAX_SLOTS];
+    unsigned long long rng[BATCH_MAX_SLOTS];                 // by slot of the pass: the coin streams behind this pass, the slots' once the pass is queued
+    for (int s = 0; s < b->n_slots; s++) open[s] = b->open[s] ? 1 : 0;
+    if (q4_batch_plan_rows(open, b->pos, b->n_prompt, b->n_slots, b->prefill, count) < 0) return Q4_ERR_ARG;
     for (int s = 0; s < b->n_slots; s++) {
-        if (!b->open[s]) continue;
-        rng[map.n] = b->rng[s];
-        map.slot[map.n] = s;
-        map.coin[map.n] = random_f32(&rng[map.n]);           // one coin per position, drawn whether or not the pass samples (q4_generate_ids' rule)
-        pos_rows[map.n++] = b->pos[s];
+        if (!count[s]) continue;
+        const int j = map.m++;
+        rng[j] = b->rng[s];
+        for (int i = 0; i < count[s]; i++) {
+            map.coin[j] = random_f32(&rng[j]);               // one coin per position, drawn whether or not the pass samples (q4_generate_ids' rule): the last row's stays
+            map.slot[map.n] = s;
+            map.off[map.n] = i;
+            seq[map.n] = s;
+            pos_rows[map.n++] = b->pos[s] + i;
+        }
+        map.last[j] = map.n - 1;
+        map.cnt[j] = count[s];
     }
     // every row's attention as the step at its position would run it: a position whose step form no pass restates (without graphs: the one-block form at
     // 256 .. 510) refuses the whole pass in front of its first launch
@@ -181,16 +204,25 @@ int queue_pass(q4_batch* b, Model* m, Sampler* sampler, int* log) {
     Q4_LAUNCH(batch_embed_kernel, dim3(divUp(dim >> 3, 256), map.n), dim3(256), 0, sc->x, w->token_embedding_table, dim, map, b->words, (const int*)b->ring, ring_stride,
               b->k, b->v, b->cache_halves, sc->pos);
     Q4_LAUNCH_CHECK();
-    Q4_TRY(batch_pass_layers(p, &b->t->state, w, m, &b->scratch, pos_rows, map.n, b->words->kv));
-    Q4_TRY(launch_verify_cls(b->rows, sc->x, w->rms_final_weight, w->wcls, dim, vocab, map.n));
+    const bool several = map.n > map.m;                      // some slot carries more than one row
+    Q4_TRY(batch_pass_layers(p, &b->t->state, w, m, &b->scratch, pos_rows, map.n, b->words->kv, several ? seq : nullptr));
+    // the classifier only where a token or a slot's logits row needs it -- every slot's last row: those rows' residual streams gathered into sc->q (free
+    // behind the layers); one row per slot: they are rows 0 .. n - 1 of sc->x as they stand
+    const q4_half* last_x = sc->x;
+    if (several) {
+        Q4_LAUNCH(batch_gather_kernel, dim3(divUp(dim >> 3, 256), map.m), dim3(256), 0, sc->q, (const q4_half*)sc->x, dim, map);
+        Q4_LAUNCH_CHECK();
+        last_x = sc->q;
+    }
+    Q4_TRY(launch_verify_cls(b->rows, last_x, w->rms_final_weight, w->wcls, dim, vocab, map.m));
     if (sampled) {
-        Q4_TRY(launch_sample_rows(sampler, b->rows, vocab, map.n, b->words->coin, nullptr, b->words->win));
-        Q4_LAUNCH(batch_pick_kernel<true>, dim3(map.n), dim3(1024), 0, (const q4_half*)b->rows, vocab, map, b->words, b->ring, ring_stride, b->logits, log);
+        Q4_TRY(launch_sample_rows(sampler, b->rows, vocab, map.m, b->words->coin, nullptr, b->words->win));
+        Q4_LAUNCH(batch_pick_kernel<true>, dim3(map.m), dim3(1024), 0, (const q4_half*)b->rows, vocab, map, b->words, b->ring, ring_stride, b->logits, log);
     } else {
-        Q4_LAUNCH(batch_pick_kernel<false>, dim3(map.n), dim3(1024), 0, (const q4_half*)b->rows, vocab, map, b->words, b->ring, ring_stride, b->logits, log);
+        Q4_LAUNCH(batch_pick_kernel<false>, dim3(map.m), dim3(1024), 0, (const q4_half*)b->rows, vocab, map, b->words, b->ring, ring_stride, b->logits, log);
     }
     Q4_LAUNCH_CHECK();
-    for (int r = 0; r < map.n; r++) { b->pos[map.slot[r]]++; b->rng[map.slot[r]] = rng[r]; }
+    for (int j = 0; j < map.m; j++) { const int s = map.slot[map.last[j]]; b->pos[s] += map.cnt[j]; b->rng[s] = rng[j]; }
     return Q4_OK;
 }
 
@@ -208,6 +240,7 @@ int open_slot(q4_batch* b, int slot, const int* prompt, int n_prompt, int pos, u
     Q4_LAUNCH_CHECK();
     b->open[slot] = true;
     b->pos[slot] = pos;
+    b->n_prompt[slot] = n_prompt;
     b->rng[slot] = seed;
     for (int i = 0; i < pos; i++) (void)random_f32(&b->rng[slot]);
     return Q4_OK;
@@ -256,6 +289,33 @@ int q4_batch_new(q4_batch** out, Transformer* t, int n_slots) {
     *out = b;
     return Q4_OK;
 }
+
+// The schedule of a pass, on the host alone (no HIP call): one row for every open slot first, so nobody starves; then the spare rows, in slot order, to
+// the slots still in front of their last prompt position (pos < n_prompt - 1) -- each up to min(max_rows_per_slot, n_prompt - pos) rows in all, consecutive
+// positions from pos, the last of them at most the generating row n_prompt - 1. A decoding slot never takes more than one: its next token does not exist yet.
+int q4_batch_plan_rows(const int* open, const int* pos, const int* n_prompt, int n_slots, int max_rows_per_slot, int* rows_per_slot) {
+    if (!open || !pos || !n_prompt || !rows_per_slot || n_slots < 1 || n_slots > BATCH_MAX_SLOTS || max_rows_per_slot < 1 || max_rows_per_slot > BATCH_MAX_SLOTS)
+        return -Q4_ERR_ARG;
+    int total = 0;
+    for (int s = 0; s < n_slots; s++) total += rows_per_slot[s] = open[s] ? 1 : 0;
+    for (int s = 0; s < n_slots && total < BATCH_MAX_SLOTS; s++) {
+        if (!open[s] || pos[s] < 0 || pos[s] >= n_prompt[s] - 1) continue;
+        const int left = n_prompt[s] - pos[s];
+        int want = (left < max_rows_per_slot ? left : max_rows_per_slot) - 1;
+        if (want > BATCH_MAX_SLOTS - total) want = BATCH_MAX_SLOTS - total;
+        rows_per_slot[s] += want;
+        total += want;
+    }
+    return total;
+}
+
+int q4_batch_set_prefill(q4_batch* b, int max_rows_per_slot) {
+    if (!b || max_rows_per_slot < 1 || max_rows_per_slot > BATCH_MAX_SLOTS) return Q4_ERR_ARG;
+    b->prefill = max_rows_per_slot;
+    return Q4_OK;
+}
+
+int q4_batch_get_prefill(const q4_batch* b) { return b ? b->prefill : -Q4_ERR_ARG; }
 
 int q4_batch_delete(q4_batch* b) {
     if (!b) return Q4_ERR_ARG;
